@@ -20,8 +20,14 @@ carries `sharded` (+ `sharded_2p24`, `preflight`): configs[3] -- ONE 2^26-constr
 columns), with its own barrier-bracketed timing, the number of ranks RCCL reports and the comparison with the oracle's pin.  That
 leg runs rung by rung in FRESH child processes (sharded_ladder: stream-ordered RCCL -> host-synchronous RCCL -> torch's own
 communicator -> process-to-process over mapped memory), so a failing or hanging collective cannot cost the weak figure.
-N = 1 also reports, beside `value`: proof_wall_ms, quad_mix (half of the constraints quadratic), value_incl_h2d / incl_h2d
-(witness from pinned host memory; .caller_rands: the randomness rows too; .narrow_format), the verifier, cpu_baseline.
+A plain run sets up, warms up, times the --steps steps, writes the last step's outputs (--dump-outputs DIR) and prints the line.
+Everything else is measured with --full only: for N = 1 the one-proof latency probe (proof_wall_ms), quad_mix (half of the constraints
+quadratic), value_incl_h2d / incl_h2d (witness from pinned host memory; .caller_rands: the randomness rows too; .narrow_format), the
+verifier, the comparison with the oracle's pin, cpu_baseline; for N > 1 also the sharded leg.
+
+--dump-outputs DIR: DIR/<name>.npy (float32 / float64) of what the callers of the timed path received in the last timed step: the proof
+envelope of context 0 as little-endian 16-bit words, and per context the envelope's length and SHA-256, root, seeds, constant and
+self-check flags (full / sharded); a fixed seeded sample of the codeword columns (encode).  At most 64 MB in all.
 
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).
 """
@@ -43,6 +49,47 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ROOT = os.path.dirname(os.path.abspath(__file__))
 L_, K_, N_, T_ = 8000, 8192, 32768, 192
 NO_VERIFY = False
+FULL = False                    # --full: the legs and checks beside the headline figure
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs: all files together
+
+
+def sampled(name, values, budget, dtype):
+    """{name: values as dtype} (1-D), or -- when that is more than `budget` bytes -- a fixed seeded sample of the positions, sorted,
+    with the positions themselves as `<name>_index` (float64)"""
+    import numpy as np
+    values = np.ravel(values)
+    per = np.dtype(dtype).itemsize
+    if values.size * per <= budget:
+        return {name: values.astype(dtype)}
+    m = budget // (per + 8)
+    idx = np.sort(np.random.default_rng(0).choice(values.size, size=m, replace=False))
+    return {name: values[idx].astype(dtype), name + "_index": idx.astype(np.float64)}
+
+
+def proof_outputs(proofs, infos):
+    """the envelopes (bytes) and ProofInfo structs a caller received: the first envelope in full as 16-bit words (exact in float32;
+    a seeded sample if it does not fit), every envelope's length and SHA-256, and the per-proof values of ProofInfo"""
+    import numpy as np
+    per_proof = lambda f: np.array([list(bytes(getattr(i, f))) for i in infos], dtype=np.float32)
+    out = {"proof_len": np.array([len(p) for p in proofs], dtype=np.float64),
+           "proof_sha256": np.array([list(hashlib.sha256(p).digest()) for p in proofs], dtype=np.float32),
+           "root": per_proof("root"), "stage1_seed": per_proof("stage1_seed"), "stage2_seed": per_proof("stage2_seed"),
+           "const_sum": per_proof("const_sum"),
+           "rows": np.array([i.rows for i in infos], dtype=np.float64),
+           "valid": np.array([[i.valid_code, i.valid_linear, i.valid_quad] for i in infos], dtype=np.float32)}
+    p = proofs[0] + b"\0" * (len(proofs[0]) % 2)
+    out.update(sampled("proof", np.frombuffer(p, dtype="<u2"), DUMP_BYTES - sum(a.nbytes for a in out.values()), np.float32))
+    return out
+
+
+def dump_outputs(dirname, outs):
+    import numpy as np
+    total = sum(a.nbytes for a in outs.values())
+    if total > DUMP_BYTES or any(a.dtype not in (np.float32, np.float64) for a in outs.values()):
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes / a non-float array" % total)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in outs.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def load_pkg():
@@ -77,6 +124,14 @@ class EncodeWorkload:
     def encodes_per_step(self):
         return self.rows
 
+    def outputs(self):
+        """the codewords of the last step (rows x n x 8 32-bit limbs, exact in float64) at a fixed seeded sample of the n positions"""
+        import numpy as np
+        cws = self.ctx.download(self.cws, (self.rows, N_, 8))
+        cols = max(1, min(N_, (DUMP_BYTES - 8 * N_) // (self.rows * 8 * 8)))
+        idx = np.sort(np.random.default_rng(0).choice(N_, size=cols, replace=False))
+        return {"codewords": cws[:, idx, :].astype(np.float64), "codewords_columns": idx.astype(np.float64)}
+
     def describe(self):
         return {"workload": "configs[1]: 2^%d-constraint synthetic BN254 witness, RS-encode only (INTT_k + NTT_4k)"
                             % (self.constraints.bit_length() - 1),
@@ -108,6 +163,7 @@ class FullWorkload:
         self.traces = [c.synth_prepare(self.n_lin, self.n_quad, synth_seed=1, generated_at=0) for c in self.ctxs]
         self.rows = -(-self.n_lin // L_) + 3 * -(-self.n_quad // L_)
         self.last = None
+        self.last_infos = {}
         self.pool = None
         if inflight > 1:
             from concurrent.futures import ThreadPoolExecutor
@@ -119,6 +175,7 @@ class FullWorkload:
         (addr, length), info = self.ctxs[i].synth_prove(self.traces[i], copy=False)     # proof bytes stay in the pinned buffer
         if not (info.valid_code and info.valid_linear and info.valid_quad):
             raise SystemExit("prover self-check failed")
+        self.last_infos[i] = info
         if i == 0:
             self.last_info = info
         return (addr, length, info.ms_stage1, info.ms_stage2, info.ms_stage3, info.ms_total)
@@ -132,8 +189,14 @@ class FullWorkload:
         if self.pool is None:
             for _ in range(steps):
                 self.last = self._one(0)
+            self.last_all = [self.last]
         else:                                   # ctypes releases the GIL for the duration of each call
-            self.last = list(self.pool.map(lambda i: [self._one(i) for _ in range(steps)][-1], range(self.inflight)))[0]
+            self.last_all = list(self.pool.map(lambda i: [self._one(i) for _ in range(steps)][-1], range(self.inflight)))
+            self.last = self.last_all[0]
+
+    def outputs(self):
+        """every context's last envelope (still in its pinned buffer) and ProofInfo"""
+        return proof_outputs([C.string_at(x[0], x[1]) for x in self.last_all], [self.last_infos[i] for i in range(self.inflight)])
 
     def single_proof_ms(self, reps=3):
         """wall time of one proof with nothing else in flight (latency figure next to the throughput figure)"""
@@ -178,7 +241,7 @@ class FullWorkload:
                         best = (v.ms_total, wall, bool(v.accept))
                 d.update(verifier_accepts=best[2], verify_ms=best[0], verify_ms_with_python_copies=best[1])
             pin_path = os.path.join(ROOT, "tests", "golden", "full_pin_2p%d%s.json" % (lg, "_q%d" % self.quad_percent if self.quad_percent else ""))
-            if os.path.exists(pin_path):                      # the oracle's reference-structured prover on this exact job
+            if FULL and os.path.exists(pin_path):             # the oracle's reference-structured prover on this exact job
                 with open(pin_path) as f:
                     pin = json.load(f)
                 d["proof_equals_oracle_pin"] = bool(d["proof_sha256"] == pin["proof_sha256"] and bytes(info.root).hex() == pin["root"])
@@ -327,6 +390,9 @@ class ShardedWorkload:
             raise SystemExit("prover self-check failed")
         self.last = (addr, length, info.ms_stage1, info.ms_stage2, info.ms_stage3, info.ms_total)
         self.last_info = info
+
+    def outputs(self):
+        return proof_outputs([C.string_at(self.last[0], self.last[1])], [self.last_info])
 
     def describe(self):
         d = {"workload": "configs[3]-style: ONE 2^%d-constraint trace row-sharded over the GPUs, full proof"
@@ -566,6 +632,25 @@ def sharded_ladder(a, group, rank, world, local_rank, workload="sharded"):
         if n_ok == world:
             break
     return results, attempts
+
+
+def sharded_leg_in_children(a, group, rank, world, local_rank):
+    """sharded_ladder under a last-resort watchdog: if the PARENTS' own collectives hang (a peer parent died), say so and leave"""
+    import threading
+    done = threading.Event()
+
+    def watchdog():
+        if done.wait(a.sharded_budget + a.sharded_timeout + 60):
+            return
+        sys.stderr.write("bench.py: the sharded leg's launcher did not return (a rank of the bench itself is gone?)\n")
+        sys.stderr.flush()
+        os._exit(1)
+
+    threading.Thread(target=watchdog, daemon=True).start()
+    try:
+        return sharded_ladder(a, group, rank, world, local_rank)
+    finally:
+        done.set()
 
 
 def rocm_smi_topo():
@@ -812,9 +897,13 @@ def main():
     ap.add_argument("--h2d-narrow", type=int, default=8, choices=[0, 4, 8], help="also time a small-witness trace shipped in the narrow row "
                     "format with this many bytes per witness slot (0: skip)")
     ap.add_argument("--inflight", type=int, default=2, help="full workload: proofs (traces) proved concurrently per GPU in one step")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline figure: the latency probe, "
+                    "the verifier, the oracle pin, quad_mix, incl_h2d, cpu_baseline (N = 1) and the sharded leg (N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path returned in its last step as DIR/<name>.npy")
     a = ap.parse_args()
-    global NO_VERIFY
-    NO_VERIFY = a.no_verify
+    global NO_VERIFY, FULL
+    FULL = a.full
+    NO_VERIFY = a.no_verify or not a.full
     log2c = a.log2_constraints if a.log2_constraints is not None else (20 if a.workload == "encode" else 24)
     if a.gpus_sweep:
         sys.exit(gpus_sweep(a, sys.argv[1:]))
@@ -836,18 +925,32 @@ def main():
         return run_stub(a, lig_dist)
 
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a GPU: the HIP path has no CPU fallback")
     if os.environ.get("LIG_BENCH_SHARE_GPU") == "1":
         # test mode (tests/test_gpu_sharded.py): all ranks on GPU 0 of a one-GPU box, collectives through the process-to-process
         # communicator (LIG_COMM=ipc) over a gloo rendezvous -- RCCL cannot put two ranks on one device.  Not a benchmark.
         local_rank = 0
-    if world > 1 and torch.cuda.device_count() <= local_rank:
-        raise SystemExit("bench.py: rank %d of %d has no GPU of its own (%d visible)" % (local_rank, world, torch.cuda.device_count()))
-    torch.cuda.set_device(local_rank)
-    pkg = load_pkg()
-    group = lig_dist.Group(a.backend or "nccl")          # RCCL over xGMI; a no-op object when WORLD_SIZE == 1
+
+    def open_device():
+        if not torch.cuda.is_available():
+            raise SystemExit("bench.py needs a GPU: the HIP path has no CPU fallback")
+        if world > 1 and torch.cuda.device_count() <= local_rank:
+            raise SystemExit("bench.py: rank %d of %d has no GPU of its own (%d visible)" % (local_rank, world, torch.cuda.device_count()))
+        torch.cuda.set_device(local_rank)
+
+    backend = a.backend or "nccl"
+    sharded_due = a.workload == "full" and not a.no_sharded_leg and ((a.full and world > 1) or a.sharded_leg)
+    # The sharded leg's child processes open the GPU themselves.  When the process group does not live on the device (gloo), the leg runs
+    # before this process opens it, so that the children are the only processes on the device: with every rank on one GPU
+    # (LIG_BENCH_SHARE_GPU) the parents would double the number of processes that hold it.  RCCL's process group needs the device first.
+    ladder_first = sharded_due and backend != "nccl"
+    if not ladder_first:
+        open_device()
+    group = lig_dist.Group(backend)          # RCCL over xGMI; a no-op object when WORLD_SIZE == 1
     dist = group.dist
+    ladder = sharded_leg_in_children(a, group, rank, world, local_rank) if sharded_due else None
+    if ladder_first:
+        open_device()
+    pkg = load_pkg()
 
     ctx = pkg.Context(L_, K_, N_, device=local_rank)
     if a.workload == "sharded":
@@ -863,7 +966,7 @@ def main():
     for _ in range(a.warmup):
         wl.step()
     single_ms, single_prof, single_prof512 = None, None, None
-    if hasattr(wl, "single_proof_ms") and not a.no_latency_probe:      # latency probe: one proof at a time, dominant kernel bracketed as well
+    if hasattr(wl, "single_proof_ms") and a.full and not a.no_latency_probe:      # latency probe: one proof at a time, dominant kernel bracketed as well
         ctx.profile_enable(True)
         single_ms = wl.single_proof_ms()
         single_prof = ctx.profile_read()
@@ -891,6 +994,8 @@ def main():
         launches += a_; prows += b_; kms += c_; launches512 += d_; kms512 += e_
         pc.profile_enable(False)
     dt = group.max_over_ranks(dt)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, wl.outputs())
 
     # what the workload says about itself (incl. the untimed verifier run on the last proof), then its contexts go: every
     # context holds three HIP streams, and idle streams still occupy slots of the 4 hardware queues the next leg's streams map to
@@ -900,7 +1005,7 @@ def main():
     # the quadratic mix (optional): the same number of constraints, half of them quadratic -- three committed rows
     # per 8000 quadratic slots instead of one, so constraints/s differs from the all-linear figure by up to 3x
     quad_mix = None
-    if a.workload == "full" and a.quad_mix and not a.quad_percent and world == 1:
+    if a.full and a.workload == "full" and a.quad_mix and not a.quad_percent and world == 1:
         try:
             qw = FullWorkload(ctx, 1 << log2c, pkg, max(1, a.inflight), local_rank, quad_percent=a.quad_mix)
             qw.run(2)
@@ -921,7 +1026,7 @@ def main():
 
     # PCIe-inclusive figure: the same proofs with the witness matrix starting in pinned host memory (caller-rows entry)
     incl = None
-    if a.workload == "full" and not a.no_h2d and world == 1:      # informational, N = 1 only (like cpu_baseline): keeps the scaling runs lean
+    if a.full and a.workload == "full" and not a.no_h2d and world == 1:      # informational, N = 1 only (like cpu_baseline): keeps the scaling runs lean
         try:
             hw = RowsFromHostWorkload(ctx, 1 << log2c, pkg, max(1, a.h2d_inflight), local_rank)
             hw.run(3)                                   # warm-up: the second message matrix is allocated by the first prefetch, pages are touched
@@ -1110,30 +1215,14 @@ def main():
                 incl["caller_rands"]["same_proof_bytes"] = incl["caller_rands"]["proof_sha256"] == out["config"].get("proof_sha256")
     else:
         out = None
-    if a.workload == "full" and not a.no_sharded_leg and (world > 1 or a.sharded_leg):
-        # The sharded leg is the one part of this script that needs real peers (RCCL over xGMI).  It runs in child processes, rung
-        # by rung (sharded_ladder): whatever happens there -- an error on one rank, a hung collective, a crash -- the weak-scaling
-        # figure measured above is already in `out` and is printed.
-        ctx.close()                                         # the children use the GPU now (close() again below is a no-op)
-        import threading
-        done = threading.Event()
-
-        def watchdog():           # last resort: the PARENTS' own collectives hang (a peer parent died): print what there is and leave
-            if done.wait(a.sharded_budget + a.sharded_timeout + 60):
-                return
-            if out is not None:
-                out.setdefault("sharded", {"error": "the sharded leg's launcher did not return (a rank of the bench itself is gone?); the weak-scaling figures above are unaffected"})
-                sys.stdout.flush()
-                print(json.dumps(out), flush=True)
-            os._exit(0 if out is not None else 1)
-
-        threading.Thread(target=watchdog, daemon=True).start()
+    if ladder is not None:
+        # The sharded leg ran in child processes, rung by rung (sharded_ladder), before the weak leg: whatever happened there -- an
+        # error on one rank, a hung collective, a crash -- the weak-scaling figure above was measured all the same and is printed.
         try:
             pre = preflight(group, pkg, torch, local_rank, world)
         except (RuntimeError, OSError, pkg.LigError) as e:
             pre = {"error": repr(e)[:300]}
-        results, attempts = sharded_ladder(a, group, rank, world, local_rank)
-        done.set()
+        results, attempts = ladder
         if out is not None:
             sizes = [int(x) for x in str(a.sharded_log2).split(",") if x]
             main_size = 26 if 26 in sizes else sizes[-1]
@@ -1151,7 +1240,7 @@ def main():
                     out["sharded_2p%d" % lg] = results.get(str(lg)) or {"error": "not delivered"}
             out["preflight"] = pre
     if out is not None:
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(wl.name)
         result = json.dumps(out)
     else:

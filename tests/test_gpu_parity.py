@@ -524,12 +524,13 @@ def test_batched_prover_chunk_boundaries(amd, n_linear, n_quad):
         ol.lib().lo_proof_free(C.byref(pr))
 
 
-def test_hip_encode_and_leaves_equal_the_wgsl_kernels_executing(ctx512):
+def test_hip_encode_and_leaves_equal_the_wgsl_kernels_executing(request):
     """ingest hook (round 6): when tests/golden/wgsl_encode_k512.json exists (dumped from the reference's webgpu_context,
-    tools/make_wgsl_pin.py) the HIP encoder and column hash must reproduce the WGSL kernels' codewords and leaves bit for bit"""
+    tools/make_wgsl_pin.py) the HIP encoder and column hash must reproduce the WGSL kernels' codewords and leaves bit for bit.
+    Where the file is absent (no WebGPU runtime has produced it) the test skips before it opens the GPU."""
     import test_ref_pins as trp
     g, msgs, cws, leaves = trp._wgsl_fixture()
-    c = ctx512
+    c = request.getfixturevalue("ctx512")
     n, k = g["n"], g["k"]
     dm, dc = c.upload(msgs), c.malloc(32 * n * g["rows"])
     c.encode_rows(dm, dc, g["rows"])

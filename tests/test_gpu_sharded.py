@@ -220,13 +220,13 @@ def _bench(args, timeout=600, **envkw):
 
 
 TWO_ON_ONE = ["--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--log2-constraints", "22", "--sharded-steps", "2",
-              "--no-cpu-baseline", "--no-verify"]
+              "--no-cpu-baseline", "--no-verify", "--full"]
 
 
 def test_bench_py_gpus_2_on_one_gpu_runs_the_sharded_leg_with_real_peers(tmp_path):
     """`python bench.py --gpus 2` (its own launcher) with both ranks on the one GPU (LIG_BENCH_SHARE_GPU, collectives =
-    comm_ipc over a gloo rendezvous): the N > 1 code path of the bench -- weak leg on every rank, preflight, then ONE trace
-    sharded over the ranks in child processes, at two sizes -- prints one JSON line with n_gpus = 2 and a `sharded` object whose
+    comm_ipc over a gloo rendezvous), with --full: the N > 1 code path of the bench -- ONE trace sharded over the ranks in child
+    processes at two sizes, then the weak leg on every rank and preflight -- prints one JSON line with n_gpus = 2 and a `sharded` object whose
     envelope equals the oracle pin, delivered by the first rung of the ladder"""
     out = _bench(TWO_ON_ONE + ["--sharded-log2", "22,24"], LIG_BENCH_SHARE_GPU="1", LIG_COMM="ipc", LIG_COMM_TAG=mr.fresh_tag())
     assert out["n_gpus"] == 2 and out["scaling"] == "weak"

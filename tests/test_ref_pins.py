@@ -205,7 +205,8 @@ def test_sample_indices_equal_real_boost():
 def _wgsl_fixture():
     path = os.path.join(GOLD, "wgsl_encode_k512.json")
     if not os.path.exists(path):
-        pytest.skip("tests/golden/wgsl_encode_k512.json absent: dump it from a running webgpu_context (tools/make_wgsl_pin.py)")
+        pytest.skip("needs the output of the reference's WGSL kernels run on a WebGPU device (Dawn or a browser), which this machine lacks: "
+                    "tests/golden/wgsl_encode_k512.json absent, dump it from a running webgpu_context (tools/make_wgsl_pin.py)")
     with open(path) as f:
         g = json.load(f)
     msgs = np.stack([ol.to_limbs([(i * i + 7 + r) % ol.P for i in range(g["k"])]) for r in range(g["rows"])])
