@@ -271,6 +271,8 @@ enum {
     LIG_ROW_EQY = 7, LIG_ROW_BQX = 8, LIG_ROW_BQY = 9, LIG_ROW_BQZ = 10,
     LIG_ROW_DRAW_PAD = 0x80      /* or-ed in: slots [l, k) of this row are drawn from the encoding stream by the library */
 };
+/* lig_rows_job.elem_bytes values with the 0x80 prefix ("packed bits"): only this one is defined */
+enum { LIG_ELEM_BIT = 0x81 };    /* slot i < l = bit i % 8 of byte i / 8, LSB first (numpy.packbits(bitorder="little")) */
 typedef struct {
     uint64_t rows;                   /* committed rows, the 3 mask rows excluded */
     const uint8_t *kinds;            /* one byte per row (host memory) */
@@ -287,11 +289,15 @@ typedef struct {
      * generate them on the device (sampled under the encodes, as lig_synth_prove does) instead of reading them */
     const uint32_t *dense_rands_per_row;
     /* optional (NULL: every row is k full 32-byte elements): the NARROW row format.  One byte per row: 0 or 32 = the row as
-     * above; 4 or 8 = only the row's l data slots are supplied, each as a little-endian unsigned integer of that many bytes
-     * (real traces are mostly bits and machine words: 8x / 4x less to move over PCIe; the reference ships 32 bytes per slot,
-     * include/util/mpz_vector.hpp:108-127).  `msgs` then holds the rows back to back, a narrow row taking l * 4 (or 8)
-     * bytes; the library expands it on the device.  A narrow row must be LINEAR / QX / QY / QZ and flagged
-     * LIG_ROW_DRAW_PAD (its k - l pad slots are drawn by the library).  lig_rows_restart takes the same packed layout. */
+     * above; 1, 2, 4 or 8 = only the row's l data slots are supplied, each as a little-endian unsigned integer of that many
+     * bytes; LIG_ELEM_BIT = the l data slots are bits, slot i = bit i % 8 of byte i / 8, least significant bit first (real
+     * traces are mostly bits and machine words: up to 256x less to move over PCIe; the reference ships 32 bytes per slot,
+     * include/util/mpz_vector.hpp:108-127).  `msgs` then holds the rows back to back in commit order, a narrow row taking
+     * l * w bytes (ceil(l / 8) for bits) rounded up to a multiple of 4 -- every row starts 4-byte aligned; the padding bytes
+     * are ignored -- and a full row k * 32; the library expands them on the device.  A narrow row must be LINEAR / QX / QY / QZ
+     * and flagged LIG_ROW_DRAW_PAD (its k - l pad slots are drawn by the library).  Any other value is LIG_E_ARG.
+     * lig_rows_restart takes the same packed layout, as do lig_shard_rows_begin / _restart (there: one byte per row of the
+     * whole trace, `msgs` = this rank's rows only, packed back to back in commit order). */
     const uint8_t *elem_bytes;
 } lig_rows_job;
 int lig_rows_begin(lig_ctx *ctx, const lig_rows_job *job, lig_trace **out);
@@ -425,11 +431,12 @@ void lig_shard_destroy(lig_shard *shard);
  * public linear constant (NULL: minus the sum of all inner products, as lig_rows_prove).  Every rank obtains the envelope of
  * lig_rows_prove on the whole trace.  Replaces the per-row callbacks of include/zkp/nonbatch_context.hpp:445-471, :654-780,
  * :924-970 when the rows of one trace live on several GPUs.
- * The sharded entry takes full-width rows only: job->elem_bytes must be NULL (LIG_E_ARG otherwise).
+ * The narrow row format (job->elem_bytes, one byte per row of the WHOLE trace) is accepted: job->msgs then holds this rank's rows only,
+ * packed back to back in commit order; they are uploaded to a staging buffer and expanded on the device before stage 1.
  * LIFETIME: the local rows passed to lig_shard_rows_begin / lig_shard_rows_restart (host or device memory) are copied before the call
  * returns; randomness rows passed to lig_shard_rows_prove are consumed before it returns.  (Only with LIG_SHARD_UPLOADER=1 -- the round-4
- * path through the library's uploader thread, off by default: profiles/r05_rows_entry_hang.md -- host rows are read until
- * lig_shard_rows_commit has returned.)
+ * path through the library's uploader thread, off by default: profiles/r05_rows_entry_hang.md -- full-width host rows are read until
+ * lig_shard_rows_commit has returned; narrow rows always take the synchronous copy.)
  * FAILURE: a peer that dies, leaves or stops responding makes these calls return LIG_E_STATE (lig_comm.failed / .abort), they do not hang:
  * every wait on the error paths and in lig_shard_destroy is a bounded poll.  If kernels queued behind the failed collective still have
  * not drained 20 s after the communicator was aborted, the error text says "poisoned": the shard refuses further calls, lig_shard_destroy

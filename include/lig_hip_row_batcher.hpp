@@ -47,6 +47,10 @@ struct hip_proof_meta {
     // encoding stream at the row's position (witness_manager::pad_encoding_random, witness_manager.hpp:323-336, keyed by
     // encoding_seed): the library draws the same elements the row arrived with.
     bool narrow_rows = false;
+    // With narrow_rows: ship every such row in the NARROWEST width its data slots fit -- bits, 1, 2, 4 or 8 bytes per slot
+    // (LIG_ELEM_BIT / elem_bytes) -- on one GPU and on every rank of a sharded trace (shard_over).  Off: 8 bytes per slot on one
+    // GPU, full rows when sharded.
+    bool narrowest = false;
     // Rows the guest is expected to commit (0: unknown).  The staging is page-locked memory that grows geometrically when the
     // guest outruns it; a driver that proves the same program again (or knows its size) saves the re-allocations.
     size_t expected_rows = 0;
@@ -167,34 +171,23 @@ public:
         job.public_args = args.empty() ? nullptr : args.data();
         job.public_arg_lens = lens.empty() ? nullptr : lens.data();
         job.n_public_args = lens.size();
+        shipped_ = kinds_.size() * (size_t)k_ * 32;
         if (sharded_) { commit_sharded(job, root, stage1_seed); return; }
         std::vector<uint8_t> widths;
         if (meta_.narrow_rows) {
-            // packed IN PLACE: a narrow row shrinks to l x 8 bytes, rows only ever move towards the front of the staging
-            const size_t R = kinds_.size(), words = (size_t)k_ * 4;
+            // packed IN PLACE: a narrow row shrinks to l x (its width) bytes, rows only ever move towards the front of the staging
+            const size_t R = kinds_.size();
             widths.assign(R ? R : 1, 32);
             bool any = false;
-            for (size_t r = 0; r < R; r++) {
-                if (kinds_[r] > LIG_ROW_QZ) continue;                       // batch rows are device rows of full width
-                const uint64_t* rw = rows_.row(r);
-                bool fits = true;
-                for (uint32_t i = 0; i < l_ && fits; i++) fits = !(rw[4 * i + 1] | rw[4 * i + 2] | rw[4 * i + 3]);
-                if (fits) { widths[r] = 8; any = true; }
-            }
+            for (size_t r = 0; r < R; r++) any = (widths[r] = ship_width(r)) != 32 || any;
             if (any) {
-                uint64_t* out = rows_.row(0);
+                uint8_t* out = reinterpret_cast<uint8_t*>(rows_.row(0));
                 for (size_t r = 0; r < R; r++) {
-                    const uint64_t* rw = rows_.row(r);
-                    if (widths[r] == 8) {
-                        kinds_[r] |= LIG_ROW_DRAW_PAD;
-                        for (uint32_t i = 0; i < l_; i++) out[i] = rw[4 * i];
-                        out += l_;
-                    } else {
-                        if (out != rw) std::memmove(out, rw, words * 8);
-                        out += words;
-                    }
+                    if (widths[r] != 32) kinds_[r] |= LIG_ROW_DRAW_PAD;
+                    out = pack_row(rows_.row(r), widths[r], out);
                 }
                 job.elem_bytes = widths.data();
+                shipped_ = out - reinterpret_cast<uint8_t*>(rows_.row(0));
             }
         }
         if (trace_) {                                      // the next proof of the same program: every device buffer is reused
@@ -233,6 +226,8 @@ public:
     }
     size_t rows() const { return kinds_.size(); }
     size_t local_rows() const { return sharded_ ? n_local_ : kinds_.size(); }
+    // bytes of message rows the last commit() handed to the library (this rank's rows when sharded): what crosses the link
+    size_t shipped_bytes() const { return shipped_; }
 
 private:
     static constexpr size_t push_rows = 256;             // randomness rows per lig_rows_push_rands (64 MiB at k = 8192)
@@ -264,18 +259,68 @@ private:
         if (lig_shard_rows_plan(kinds_.data(), R, world_, &rounds, b.data(), b.size()) != LIG_OK) throw std::runtime_error("lig_shard_rows_plan failed");
         local_of_.assign(R, (size_t)-1);
         n_local_ = 0;
+        // narrowest: the widths of ALL rows (every rank sees the same rows), this rank's rows packed in place behind the compaction
+        std::vector<uint8_t> widths;
+        if (meta_.narrow_rows && meta_.narrowest) {
+            widths.assign(R ? R : 1, 32);
+            bool any = false;
+            for (size_t r = 0; r < R; r++) any = (widths[r] = ship_width(r)) != 32 || any;
+            if (any) {
+                for (size_t r = 0; r < R; r++) if (widths[r] != 32) kinds_[r] |= LIG_ROW_DRAW_PAD;
+                job.elem_bytes = widths.data();
+            }
+        }
+        uint8_t* out = reinterpret_cast<uint8_t*>(rows_.row(0));
         // this rank's rows, compacted IN PLACE to the front of the staging (commit order is kept, rows only move forward)
         for (uint64_t g = rank_; g < rounds * world_; g += world_)
             for (uint64_t r = b[g]; r < b[g + 1]; r++) {
-                if (n_local_ != r) std::memmove(rows_.row(n_local_), rows_.row(r), words * 8);
+                if (job.elem_bytes) out = pack_row(rows_.row(r), widths[r], out);
+                else if (n_local_ != r) std::memmove(rows_.row(n_local_), rows_.row(r), words * 8);
                 local_of_[r] = n_local_++;
             }
         job.msgs = n_local_ ? rows_.data() : nullptr;
+        shipped_ = job.elem_bytes ? (size_t)(out - reinterpret_cast<uint8_t*>(rows_.row(0))) : n_local_ * words * 8;
         if (shard_) { lig_shard_destroy(shard_); shard_ = nullptr; }
         check(lig_shard_rows_begin(ctx_, &job, rank_, world_, &comm_, &shard_), "lig_shard_rows_begin");
         check(lig_shard_rows_commit(shard_, root, stage1_seed), "lig_shard_rows_commit");
+        for (auto& kd : kinds_) kd &= 0x7f;               // (pass 2 compares plain kinds)
         begin_pass2(n_local_);
         std::memset(rands_.row(0), 0, (n_local_ ? n_local_ : 1) * words * 8);       // batch rows and rows without a callback keep zero rows
+    }
+    // the width row r of the staging is shipped in: 32 for batch rows and rows whose data slots need more than 8 bytes; else 8,
+    // or with `narrowest` the smallest of bits / 1 / 2 / 4 / 8 bytes that holds every data slot (the OR of the slots decides)
+    uint8_t ship_width(size_t r) const {
+        if (kinds_[r] > LIG_ROW_QZ) return 32;
+        const uint64_t* rw = const_cast<hip_row_staging&>(rows_).row(r);
+        uint64_t lo = 0, hi = 0;
+        for (uint32_t i = 0; i < l_ && !hi; i++) { lo |= rw[4 * i]; hi |= rw[4 * i + 1] | rw[4 * i + 2] | rw[4 * i + 3]; }
+        if (hi) return 32;
+        if (!meta_.narrowest) return 8;
+        return lo <= 1 ? (uint8_t)LIG_ELEM_BIT : lo <= 0xff ? 1 : lo <= 0xffff ? 2 : lo <= 0xffffffffu ? 4 : 8;
+    }
+    // row `rw` (k x 4 u64) in the packed layout of width w written at `out` <= rw (the same staging: the write never overtakes
+    // the read); returns the next row's start -- narrow rows take l x w bytes (bits: ceil(l / 8)) zero-padded to a multiple of 4
+    uint8_t* pack_row(const uint64_t* rw, uint8_t w, uint8_t* out) const {
+        if (w == 32) {
+            if ((const void*)out != (const void*)rw) std::memmove(out, rw, (size_t)k_ * 32);
+            return out + (size_t)k_ * 32;
+        }
+        size_t bytes = 0;
+        if (w == LIG_ELEM_BIT) {
+            for (uint32_t i = 0; i < l_; i += 8) {
+                uint8_t v = 0;
+                for (uint32_t j = 0; j < 8 && i + j < l_; j++) v |= (uint8_t)((rw[4 * (i + j)] & 1) << j);
+                out[bytes++] = v;
+            }
+        } else {
+            for (uint32_t i = 0; i < l_; i++) {
+                const uint64_t v = rw[4 * i];
+                std::memmove(out + bytes, &v, w);         // little endian host
+                bytes += w;
+            }
+        }
+        while (bytes % 4) out[bytes++] = 0;
+        return out + bytes;
     }
     void check(int rc, const char* what) const {
         if (rc != LIG_OK) throw std::runtime_error(std::string(what) + ": " + lig_last_error(ctx_));
@@ -331,7 +376,7 @@ private:
     lig_comm comm_{};
     lig_shard* shard_ = nullptr;
     std::vector<size_t> local_of_;
-    size_t n_local_ = 0;
+    size_t n_local_ = 0, shipped_ = 0;
 };
 
 // The verifier's counterpart (src/webgpu_verifier.cpp:263-452 with nonbatch_verifier_context, nonbatch_context.hpp:1081-1388):

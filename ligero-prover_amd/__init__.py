@@ -42,6 +42,7 @@ EXPORTS = [
 
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
 ROW_DRAW_PAD = 0x80
+ELEM_BIT = 0x81            # lig_rows_job.elem_bytes: the row's data slots are bits (LIG_ELEM_BIT)
 ARG_I64, ARG_STR, ARG_HEX = 0, 1, 2
 
 
@@ -292,16 +293,55 @@ def shard_plan(job, l, world):
 
 
 def pack_rows(rows, widths, l):
-    """rows (R, k, 8) uint32 + per-row width (4 / 8 / 32) -> the packed byte array of the narrow row format
-    (lig_rows_job.elem_bytes): a narrow row contributes its l data slots as little-endian integers of that width"""
+    """rows (R, k, 8) uint32 + per-row width (1 / 2 / 4 / 8 / 32 / ELEM_BIT) -> the packed byte array of the narrow row format
+    (lig_rows_job.elem_bytes): a narrow row contributes its l data slots as little-endian integers of that width (ELEM_BIT: bit
+    i % 8 of byte i / 8, LSB first), zero-padded to a multiple of 4 bytes; a row of width 0 / 32 all of its k slots"""
     parts = []
     for r, w in enumerate(widths):
+        w = int(w)
         if w in (0, 32):
             parts.append(np.ascontiguousarray(rows[r], dtype=np.uint32).tobytes())
-        else:
+            continue
+        if w == ELEM_BIT:
+            assert not rows[r, :l, 1:].any() and not (rows[r, :l, 0] > 1).any(), "row %d is not a bit row" % r
+            b = np.packbits(rows[r, :l, 0].astype(np.uint8), bitorder="little").tobytes()
+        elif w in (1, 2):
+            assert not rows[r, :l, 1:].any() and not (rows[r, :l, 0] >> (8 * w)).any(), "row %d does not fit %d-byte elements" % (r, w)
+            b = rows[r, :l, 0].astype("<u%d" % w).tobytes()
+        elif w in (4, 8):
             assert not rows[r, :l, w // 4:].any(), "row %d does not fit %d-byte elements" % (r, w)
-            parts.append(np.ascontiguousarray(rows[r, :l, :w // 4], dtype=np.uint32).tobytes())
+            b = np.ascontiguousarray(rows[r, :l, :w // 4], dtype=np.uint32).tobytes()
+        else:
+            raise ValueError("row %d: no such width %d" % (r, w))
+        parts.append(b + bytes(-len(b) % 4))
     return np.frombuffer(b"".join(parts), dtype=np.uint8).copy()
+
+
+def narrowest_widths(rows, kinds, l):
+    """-> uint8 widths for pack_rows / elem_bytes: the smallest width each LINEAR / QX / QY / QZ row of rows (R, k, 8) fits into
+    (ELEM_BIT if every data slot is 0 or 1, else 1, 2, 4, 8 bytes, else 32); every other row kind is 32"""
+    rows = np.asarray(rows)
+    kinds = np.asarray(kinds, dtype=np.uint8) & 0x7F
+    out = np.full(len(kinds), 32, dtype=np.uint8)
+    for r in range(len(kinds)):
+        if kinds[r] > 3:
+            continue
+        d = rows[r, :l]
+        if d[:, 2:].any():
+            continue
+        hi = int(d[:, 1].max()) if l else 0
+        lo = int(d[:, 0].max()) if l else 0
+        if hi:
+            out[r] = 8
+        elif lo <= 1:
+            out[r] = ELEM_BIT
+        elif lo <= 0xFF:
+            out[r] = 1
+        elif lo <= 0xFFFF:
+            out[r] = 2
+        else:
+            out[r] = 4
+    return out
 
 
 def shard_rows_plan(kinds, world):
@@ -511,15 +551,24 @@ class Context:
 
     # ---- one trace sharded over ranks, rows supplied by the caller (lig_shard_rows_*)
     def shard_rows_begin(self, kinds_all, local_msgs, rank, world, comm, on_device=False, encoding_seed=None, generated_at=0,
-                         public_args=None, dense_rands_per_row=None):
-        """kinds_all: the kinds of ALL committed rows; local_msgs: this rank's rows (lig_shard_rows_plan), (rows_local, k, 8) uint32"""
+                         public_args=None, dense_rands_per_row=None, elem_bytes=None):
+        """kinds_all: the kinds of ALL committed rows; local_msgs: this rank's rows (lig_shard_rows_plan), (rows_local, k, 8) uint32;
+        with elem_bytes (one width per row of the WHOLE trace): this rank's rows packed back to back (pack_rows of the local rows)"""
         kinds = np.ascontiguousarray(kinds_all, dtype=np.uint8)
         job = RowsJob()
         job.rows = len(kinds)
         job.kinds = kinds.ctypes.data if len(kinds) else None
         keep = (kinds,)
+        if elem_bytes is not None:
+            eb = np.ascontiguousarray(elem_bytes, dtype=np.uint8)
+            job.elem_bytes = eb.ctypes.data if len(eb) else None
+            keep += (eb,)
         if on_device:
             job.msgs = local_msgs.value if hasattr(local_msgs, "value") else int(local_msgs)
+        elif elem_bytes is not None:              # narrow format: the packed byte string
+            local_msgs = np.frombuffer(bytes(local_msgs), dtype=np.uint8).copy() if not isinstance(local_msgs, np.ndarray) else np.ascontiguousarray(local_msgs, dtype=np.uint8)
+            job.msgs = local_msgs.ctypes.data if local_msgs.size else None
+            keep += (local_msgs,)
         else:
             local_msgs = np.ascontiguousarray(local_msgs, dtype=np.uint32)
             job.msgs = local_msgs.ctypes.data if local_msgs.size else None
@@ -545,11 +594,11 @@ class Context:
         return t
 
     def shard_rows_restart(self, shard, local_msgs, on_device=False):
-        """the next trace of the same shape (after shard_rows_prove of the previous one)"""
+        """the next trace of the same shape (after shard_rows_prove of the previous one); a narrow shard takes the packed bytes"""
         if on_device:
             ptr, keep = (local_msgs if hasattr(local_msgs, "value") else C.c_void_p(int(local_msgs))), ()
         else:
-            local_msgs = np.ascontiguousarray(local_msgs, dtype=np.uint32)
+            local_msgs = np.ascontiguousarray(local_msgs, dtype=local_msgs.dtype if isinstance(local_msgs, np.ndarray) and local_msgs.dtype == np.uint8 else np.uint32)
             ptr, keep = C.c_void_p(local_msgs.ctypes.data if local_msgs.size else None), (local_msgs,)
         if hasattr(self, "_shard_keep"):
             self._shard_keep[shard.value] = keep

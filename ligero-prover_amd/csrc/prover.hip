@@ -22,28 +22,6 @@
 #include <mutex>
 #include <thread>
 
-namespace lig {
-// Narrow rows -> message rows: element i < l of row r is the little-endian integer of widths[r] (4 / 8) bytes at
-// packed + off[r] + i * widths[r]; slots l..k-1 are zeroed (their pads are drawn right after); a row of width 32 is copied.
-__global__ void __launch_bounds__(256) k_expand_rows(const uint8_t* __restrict__ packed, const uint64_t* __restrict__ off, const uint8_t* __restrict__ widths,
-                                                     size_t first_row, size_t rows, uint32_t l, uint32_t k, fr* __restrict__ out) {
-    const size_t total = rows * k;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = first_row + e / k;
-        const uint32_t i = (uint32_t)(e % k), w = widths[r];
-        const uint8_t* src = packed + off[r];
-        fr v = fr_zero();
-        if (w == 32) v = fr_load(reinterpret_cast<const fr*>(src) + i);
-        else if (i < l) {
-            const uint32_t* p = reinterpret_cast<const uint32_t*>(src + (size_t)i * w);
-            v.v[0] = p[0];
-            if (w == 8) v.v[1] = p[1];
-        }
-        fr_store(out + r * k + i, v);
-    }
-}
-}  // namespace lig
-
 struct lig_trace {
     lig_ctx* c = nullptr;
     lig_synth_job job;                  // synthetic jobs only (n_linear / n_quad / witness_key); pointers cleared
@@ -366,8 +344,7 @@ static int prove_stage1(lig_trace* T, lig_proof_info* info, const std::function<
         if (streamed) {
             if (T->up_by_thread) HIP_TRY(c, hipStreamWaitValue32(s_enc, T->up_flag_dev + ci, T->up_seq, hipStreamWaitValueGte, 0xffffffffu));
             else HIP_TRY(c, hipStreamWaitEvent(s_enc, T->ev_up[ci], 0));                   // this chunk's rows have arrived
-            if (T->narrow) hipLaunchKernelGGL(lig::k_expand_rows, dim3((uint32_t)std::min<size_t>((nb * k + 255) / 256, 4096)), dim3(256), 0, s_enc, T->packed_dev,
-                                              T->src_off_dev, T->widths_dev, b, nb, l, k, T->msgs);
+            if (T->narrow) lig::launch_expand_rows(s_enc, T->packed_dev, T->src_off_dev, T->widths_dev, b, nb, l, k, T->msgs);
             for (; pr_i < T->pad_runs.size() && T->pad_runs[pr_i].first < b + nb; pr_i++) {      // runs never straddle chunks (split in begin)
                 const PadRun& pr = T->pad_runs[pr_i];
                 lig::launch_rng_fill_rows(s_enc, c->rk_dev, pr.pos, T->msgs + pr.first * (size_t)k, pr.count, pad, k, l, 1, pad);
@@ -1039,8 +1016,7 @@ static int rows_load(lig_ctx* c, lig_trace* T, const void* msgs, bool on_device)
         T->alt_pending = true;
     }
     if (on_device) {
-        if (T->narrow) hipLaunchKernelGGL(lig::k_expand_rows, dim3((uint32_t)std::min<size_t>((R * k + 255) / 256, 8192)), dim3(256), 0, c->stream, (const uint8_t*)msgs,
-                                          T->src_off_dev, T->widths_dev, (size_t)0, R, c->l, k, dst);
+        if (T->narrow) lig::launch_expand_rows(c->stream, (const uint8_t*)msgs, T->src_off_dev, T->widths_dev, 0, R, c->l, k, dst);
         else HIP_TRY(c, hipMemcpyAsync(dst, msgs, R * (size_t)k * 32, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(c, hipGetLastError());
         return LIG_OK;
@@ -1117,11 +1093,11 @@ static int rows_begin_impl(lig_ctx* c, const lig_rows_job* job, lig_trace* T) {
         T->widths.assign(R ? R : 1, 32);
         for (size_t r = 0; r < R; r++) {
             const uint8_t w = job->elem_bytes[r] ? job->elem_bytes[r] : 32;
-            if (w != 4 && w != 8 && w != 32) FAIL(c, LIG_E_ARG, "rows job: elem_bytes must be 0, 4, 8 or 32");
+            if (!lig::narrow_row_bytes(w, l, k)) FAIL(c, LIG_E_ARG, "rows job: elem_bytes must be 0, 1, 2, 4, 8, 32 or LIG_ELEM_BIT");
             if (w != 32 && (T->rows[r].kind > 3 || !draw[r])) FAIL(c, LIG_E_ARG, "rows job: a narrow row must be LINEAR / QX / QY / QZ with LIG_ROW_DRAW_PAD");
             T->narrow = T->narrow || w != 32;
             T->widths[r] = w;
-            T->src_off[r + 1] = T->src_off[r] + (w == 32 ? (uint64_t)k * 32 : (uint64_t)l * w);
+            T->src_off[r + 1] = T->src_off[r] + lig::narrow_row_bytes(w, l, k);
         }
     }
     TRY(trace_alloc(c, T));

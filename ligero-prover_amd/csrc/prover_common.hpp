@@ -39,6 +39,20 @@ void launch_rand_rlc(hipStream_t s, const uint32_t* rk60_dev, uint64_t first, fr
 void launch_lin_interleave(hipStream_t s, fr* out, const fr* accH, const fr* accC, uint32_t k);
 void launch_rlc_combine(hipStream_t s, fr* acc, const fr* part, uint32_t groups, uint32_t count);
 void launch_copy_from_host(hipStream_t s, uint8_t* dst_dev, const uint8_t* src_mapped, size_t bytes);
+// narrow caller rows (lig_rows_job.elem_bytes, expand.hip): rows [first_row, first_row + rows) of the packed matrix -- row r at
+// packed + off_dev[r], width widths_dev[r] -- into out + r * k, full width; slots l..k-1 of a narrow row are zeroed
+void launch_expand_rows(hipStream_t s, const uint8_t* packed, const uint64_t* off_dev, const uint8_t* widths_dev, size_t first_row,
+                        size_t rows, uint32_t l, uint32_t k, fr* out);
+// packed bytes of one row of width w (0 = not a width of the format): 32 -> all k slots; bits, 1, 2, 4, 8 -> the l data slots,
+// rounded up to a multiple of 4 so that every row starts 4-byte aligned
+inline uint64_t narrow_row_bytes(uint32_t w, uint32_t l, uint32_t k) {
+    switch (w) {
+        case 32: return (uint64_t)k * 32;
+        case LIG_ELEM_BIT: return ((uint64_t)l + 31) / 32 * 4;
+        case 1: case 2: case 4: case 8: return ((uint64_t)l * w + 3) & ~(uint64_t)3;
+        default: return 0;
+    }
+}
 }  // namespace lig
 
 // ---- host rows -> device through the library's uploader thread (prover.hip; one thread per device, shared by every trace and

@@ -63,6 +63,11 @@ struct lig_shard {
     uint32_t up_seq = 0, rand_seq = 0;
     bool rows_by_thread = false;               // the local rows of the trace being committed are arriving through the uploader
     std::atomic<int> up_pending{0}, up_failed{0}, up_abort{0};
+    // narrow row format (lig_rows_job.elem_bytes): packed byte offset of every LOCAL row (+1 entry) and its width, on the device; the
+    // staging buffer host rows are copied to (device rows are expanded from where they are)
+    bool narrow = false;
+    std::vector<uint64_t> src_off;
+    uint64_t* src_off_dev = nullptr; uint8_t* widths_dev = nullptr; uint8_t* packed_dev = nullptr;
     bool used_comm = false;                    // a collective has been issued with buffers of this shard as send buffers
     bool exchange_even_alone = false;          // LIG_SHARD_FORCE_EXCHANGE: run pack + all-to-all with world == 1 too (tests)
     size_t chunk_rows(size_t g) const { return g < G ? gb[g + 1] - gb[g] : 0; }
@@ -323,7 +328,8 @@ void lig_shard_destroy(lig_shard* S) {
     S->c->sha.erase(S->sha_state);
     for (void* p : {(void*)S->msgs, (void*)S->cw, (void*)S->maskcw, (void*)S->send, (void*)S->recv, (void*)S->randb, (void*)S->rhalf, (void*)S->acc,
                     (void*)S->parts, (void*)S->accp, (void*)S->accg, (void*)S->dots, (void*)S->smp, (void*)S->smpg, (void*)S->sha_state,
-                    (void*)S->leaves_slice, (void*)S->leaves, (void*)S->nodes, (void*)S->tri_dev, (void*)S->coef_dev})
+                    (void*)S->leaves_slice, (void*)S->leaves, (void*)S->nodes, (void*)S->tri_dev, (void*)S->coef_dev, (void*)S->src_off_dev,
+                    (void*)S->widths_dev, (void*)S->packed_dev})
         (void)hipFree(p);
     for (int i = 0; i < 2; i++)
         for (hipEvent_t e : {S->ev_enc[i], S->ev_comm[i], S->ev_hash[i]}) if (e) (void)hipEventDestroy(e);
@@ -823,6 +829,21 @@ static int shard_rows_load(lig_shard* S, const void* local_msgs, bool on_device)
     S->rows_by_thread = false;
     if (!S->Rl) return LIG_OK;
     const size_t row_bytes = (size_t)c->k * 32;
+    if (S->narrow) {
+        // narrow rows: the packed bytes are copied to the staging buffer synchronously (the lifetime contract holds unchanged; the
+        // uploader path is not taken even with LIG_SHARD_UPLOADER=1), device rows are read where they are; then expanded into
+        // S->msgs on the main stream, ahead of everything lig_shard_rows_commit queues there
+        const uint8_t* src = (const uint8_t*)local_msgs;
+        if (!on_device) {
+            if (!S->packed_dev) HIP_TRY(c, hipMalloc((void**)&S->packed_dev, S->src_off[S->Rl] ? S->src_off[S->Rl] : 16));   // first host rows
+            if (S->src_off[S->Rl]) HIP_TRY(c, hipMemcpyAsync(S->packed_dev, local_msgs, S->src_off[S->Rl], hipMemcpyHostToDevice, c->stream));
+            src = S->packed_dev;
+        }
+        lig::launch_expand_rows(c->stream, src, S->src_off_dev, S->widths_dev, 0, S->Rl, c->l, c->k, S->msgs);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's memory is no longer referenced
+        return LIG_OK;
+    }
     // Host rows are copied HERE, synchronously (as in round 3).  Round 4 had moved them onto the library's uploader thread with a stream
     // memory wait per round (what lig_rows_* does on ONE GPU, where it buys the link rate): with several PROCESSES on one device -- the only
     // way this entry runs on the one-GPU test box -- a DMA transfer that is started while the process's main stream holds a pending
@@ -846,12 +867,38 @@ static int shard_rows_load(lig_shard* S, const void* local_msgs, bool on_device)
     return LIG_OK;
 }
 
+// the narrow row format: widths of all rows checked as lig_rows_begin does, packed offsets of the local rows (commit order); the staging
+// buffer of host rows is allocated by the first load from host memory (device rows are expanded where they are)
+static int shard_narrow_setup(lig_shard* S, const lig_rows_job* job, uint32_t l, uint32_t k) {
+    lig_ctx* c = S->c;
+    std::vector<uint8_t> widths(S->R);
+    for (size_t r = 0; r < S->R; r++) {
+        const uint8_t w = job->elem_bytes[r] ? job->elem_bytes[r] : 32;
+        if (!lig::narrow_row_bytes(w, l, k)) FAIL(c, LIG_E_ARG, "sharded rows job: elem_bytes must be 0, 1, 2, 4, 8, 32 or LIG_ELEM_BIT");
+        if (w != 32 && (S->rows[r].kind > 3 || !S->draw[r])) FAIL(c, LIG_E_ARG, "sharded rows job: a narrow row must be LINEAR / QX / QY / QZ with LIG_ROW_DRAW_PAD");
+        widths[r] = w;
+        S->narrow = S->narrow || w != 32;
+    }
+    if (!S->narrow) return LIG_OK;                     // every row full width: the plain path
+    const size_t Rl = S->Rl;
+    std::vector<uint8_t> local_w(Rl ? Rl : 1, 32);
+    S->src_off.assign(Rl + 1, 0);
+    for (size_t lr = 0; lr < Rl; lr++) {
+        local_w[lr] = widths[S->grow[lr]];
+        S->src_off[lr + 1] = S->src_off[lr] + lig::narrow_row_bytes(local_w[lr], l, k);
+    }
+    HIP_TRY(c, hipMalloc((void**)&S->src_off_dev, (Rl + 1) * sizeof(uint64_t)));
+    HIP_TRY(c, hipMalloc((void**)&S->widths_dev, local_w.size()));
+    HIP_TRY(c, hipMemcpy(S->src_off_dev, S->src_off.data(), (Rl + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(S->widths_dev, local_w.data(), local_w.size(), hipMemcpyHostToDevice));
+    return LIG_OK;
+}
+
 int lig_shard_rows_begin(lig_ctx* c, const lig_rows_job* job, uint32_t rank, uint32_t world, const lig_comm* comm, lig_shard** out) {
     CHECK_CTX(c);
     if (!job || !out || !comm || world == 0 || rank >= world) return LIG_E_ARG;
     if (!comm->all_to_all || !comm->all_gather) return LIG_E_ARG;
     if (job->rows && !job->kinds) FAIL(c, LIG_E_ARG, "sharded rows job: null kinds");
-    if (job->elem_bytes) FAIL(c, LIG_E_ARG, "sharded rows job: the narrow row format (elem_bytes) is not supported here, pass full-width rows");
     const uint32_t l = c->l, k = c->k, n = c->n, t = 192;
     if (l >= k || l < 2 || t > n || k - l < t || k % world) FAIL(c, LIG_E_ARG, "sharded trace: need 2 <= l <= k - 192 and world | k");
     *out = nullptr;
@@ -882,6 +929,7 @@ int lig_shard_rows_begin(lig_ctx* c, const lig_rows_job* job, uint32_t rank, uin
         S->code_ord[r + 1] = S->code_ord[r] + has_code_check(S->rows[r].kind);
     }
     int rc = shard_alloc(c, rank, world, S);
+    if (rc == LIG_OK && job->elem_bytes) rc = shard_narrow_setup(S, job, l, k);
     if (rc == LIG_OK) rc = shard_rows_load(S, job->msgs, job->msgs_on_device != 0);
     if (rc != LIG_OK) return fail(rc);
     *out = S;
