@@ -349,6 +349,57 @@ void lig_vtrace_destroy(lig_vtrace *trace);
  * coefficient rows of the synthetic stream, for callers that feed lig_rows_prove from the device. */
 int lig_rng_fill_rows(lig_ctx *ctx, const uint8_t *key32, uint64_t first_elem, const uint32_t *per_row_host, size_t rows, void *out);
 
+/* ==== sparse linear constraints: the linear-test randomness rows formed by the library (csrc/linear.hip).  The randomness rows a
+ * caller hands to lig_rows_prove are not random data: every linear constraint c draws ONE element r_c from the linear random engine
+ * (witness_manager::generate_linear_random, include/zkp/backend/witness_manager.hpp:344-348; the engine is keyed by the stage-1 seed,
+ * include/zkp/nonbatch_context.hpp:105-112) and adds a * r_c to the randomness of each witness it touches (witness_add_random /
+ * witness_sub_random, :356-372), b_c * r_c to the public constant (constsum_add / _sub, :374-388).  For constraints
+ * sum_j a_cj * w[slot_cj] = b_c:
+ *     Rn[slot s] = sum over terms (c, s, a) of a * r_c            const_sum = - sum_c b_c * r_c
+ * Which constraint touches which slot with which coefficient does not depend on the seed: the caller describes it ONCE as a term
+ * list of integers, the library draws r_c and forms matrix and constant on the GPU, for the prover and for the verifier.  Nothing of
+ * the randomness crosses the host link per proof, and a caller whose constraint structure is fixed no longer re-runs its guest
+ * between stage 1 and stage 2.  All pointers are host memory, copied before the call that takes the system returns. ==== */
+enum { LIG_COEF_ONE = 0xFFFFFFFFu, LIG_COEF_NEG_ONE = 0xFFFFFFFEu };   /* coefficient "indices" that need no table entry */
+typedef struct { uint32_t slot; uint32_t coef; } lig_lin_term;
+/* slot = row * l + column: row = index among the job's committed rows (masks excluded), column < l;
+ * coef = index into coefs[], or LIG_COEF_ONE / LIG_COEF_NEG_ONE */
+typedef struct {
+    uint32_t struct_bytes;              /* sizeof(lig_linear_system) as the caller sees it; smaller than the library's: LIG_E_ARG */
+    uint32_t reserved;
+    uint64_t n_constraints, n_terms;    /* n_terms < 2^32 */
+    const uint32_t *term_begin;         /* n_constraints + 1 entries, non-decreasing, [0] = 0, [n_constraints] = n_terms */
+    const lig_lin_term *terms;          /* constraint c owns terms [term_begin[c], term_begin[c+1]); may be empty; a slot may repeat */
+    const uint32_t *rhs_constraint;     /* n_rhs constraint numbers, strictly ascending: the constraints with b_c != 0 */
+    const uint32_t *rhs_coef;           /* n_rhs coefficient indices: b_c */
+    uint64_t n_rhs;
+    const uint8_t *coefs; uint64_t n_coefs;   /* n_coefs x 32 bytes, canonical elements (>= p is LIG_E_ARG) */
+    uint64_t first_random;              /* constraint c draws element first_random + c of the stream keyed by stage1_seed */
+} lig_linear_system;
+/* host only, no context: every rule above; every slot / l < rows and on a row of kind LINEAR / QX / QY / QZ (batch-kind rows carry no
+ * linear-test randomness, nonbatch_context.hpp:782-850); every coefficient index < n_coefs or one of the two specials;
+ * rows * l < 2^32.  LIG_E_ARG otherwise.  Every entry below runs this before anything is launched: an index out of range never
+ * reaches a kernel. */
+int lig_linear_check(const lig_linear_system *sys, const uint8_t *kinds, uint64_t rows, uint32_t l);
+/* any time after lig_rows_begin and before lig_rows_prove (before or after lig_rows_commit): uploads the structure and regroups it
+ * by slot once; it survives lig_rows_restart (same shape, same constraints) and is freed by lig_trace_destroy; a second call
+ * replaces it; sys == NULL removes it.  LIG_E_ARG for a system lig_linear_check rejects and for a job with dense_rands_per_row;
+ * LIG_E_STATE when randomness rows have already been pushed (lig_rows_push_rands*).
+ * With a system set, lig_rows_prove(rands = NULL) forms the randomness matrix on the device (side stream, under the first encodes of
+ * stage 2) and runs stage 2 on it exactly as on an uploaded matrix.  const_sum == NULL then means the system's constant
+ * -sum_c b_c r_c (returned in info->const_sum): info->valid_linear is a real check of the statement.  A non-NULL const_sum is used
+ * as given.  While a system is set, lig_rows_prove(rands != NULL) is LIG_E_ARG and lig_rows_push_rands* is LIG_E_STATE. */
+int lig_rows_set_linear(lig_trace *trace, const lig_linear_system *sys);
+/* the verifier's side, between lig_rows_verify_begin and _finish: lig_rows_verify_finish(trace, NULL, 0, NULL, out) then forms
+ * matrix and constant itself -- the sound verifier of a rows job: it needs nothing but the envelope and the public structure.
+ * (A non-NULL const_sum is used as given; rands != NULL with a system set is LIG_E_ARG.)  sys == NULL removes the system. */
+int lig_rows_verify_set_linear(lig_vtrace *trace, const lig_linear_system *sys);
+/* stand-alone: rands_dev (rows x k x 32 bytes of device memory) <- the randomness matrix for the stream keyed by key32, const_sum <-
+ * the constant; blocking.  Slots [l, k) of every row, rows no term touches and batch-kind rows come out zero, as
+ * process_reset_linear_row leaves them (witness_manager.hpp:211-214).  For a caller with its own stage-2 driver. */
+int lig_linear_form(lig_ctx *ctx, const lig_linear_system *sys, const uint8_t *kinds, uint64_t rows, const uint8_t key32[32],
+                    void *rands_dev, uint8_t const_sum[32]);
+
 /* ==== proof file framing (src/webgpu_prover.cpp:437-457 writes gzip(level 6) of the serialized envelope with
  * Boost.iostreams; src/webgpu_verifier.cpp:249-253 reads it back).  Host-only helpers on zlib: the output is a standard
  * gzip member that any gzip reader (the reference's gzip_decompressor included) accepts; compressed BYTES depend on the

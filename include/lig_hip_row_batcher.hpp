@@ -85,6 +85,34 @@ private:
     uint64_t* base_ = nullptr;
 };
 
+// A deep copy of a lig_linear_system (include/lig_hip.h): the shims keep the caller's description until there is a trace to set it on.
+class hip_linear_system_copy {
+public:
+    void assign(const lig_linear_system& s) {
+        if (s.struct_bytes < sizeof(lig_linear_system)) throw std::invalid_argument("set_linear_system: struct_bytes too small");
+        if (!s.term_begin || (s.n_terms && !s.terms) || (s.n_rhs && (!s.rhs_constraint || !s.rhs_coef)) || (s.n_coefs && !s.coefs))
+            throw std::invalid_argument("set_linear_system: null array");
+        term_begin_.assign(s.term_begin, s.term_begin + s.n_constraints + 1);
+        terms_.assign(s.terms, s.terms + s.n_terms);
+        rhs_c_.assign(s.rhs_constraint, s.rhs_constraint + s.n_rhs);
+        rhs_b_.assign(s.rhs_coef, s.rhs_coef + s.n_rhs);
+        coefs_.assign(s.coefs, s.coefs + s.n_coefs * 32);
+        sys_ = s;
+        sys_.struct_bytes = sizeof(lig_linear_system);
+        sys_.term_begin = term_begin_.data(); sys_.terms = terms_.data(); sys_.rhs_constraint = rhs_c_.data(); sys_.rhs_coef = rhs_b_.data();
+        sys_.coefs = coefs_.data();
+        set_ = true;
+    }
+    bool is_set() const { return set_; }
+    const lig_linear_system* get() const { return &sys_; }
+private:
+    bool set_ = false;
+    lig_linear_system sys_{};
+    std::vector<uint32_t> term_begin_, rhs_c_, rhs_b_;
+    std::vector<lig_lin_term> terms_;
+    std::vector<uint8_t> coefs_;
+};
+
 class hip_row_batcher {
 public:
     hip_row_batcher(lig_ctx* ctx, hip_proof_meta meta)
@@ -102,8 +130,22 @@ public:
     // randomness rows of those.  Call before commit(); `comm` from lig_rccl_comm_create (or lig_ipc_comm_create) must outlive
     // the batcher.  Every rank's prove() returns the same envelope as an unsharded batcher would.
     void shard_over(uint32_t rank, uint32_t world, const lig_comm* comm) {
-        if (pass_ != 1 || !comm || !world || rank >= world) throw std::invalid_argument("hip_row_batcher::shard_over");
+        if (pass_ != 1 || !comm || !world || rank >= world || linear_.is_set()) throw std::invalid_argument("hip_row_batcher::shard_over");
         sharded_ = true; rank_ = rank; world_ = world; comm_ = *comm;
+    }
+
+    // The linear constraints of the program as a sparse term list (lig_linear_system): the library then
+    // forms the linear-test randomness rows and the public constant on the GPU.  Pass 2 -- the second run of the guest -- is no
+    // longer needed: prove() may follow commit() directly (callbacks of a pass 2 that is replayed all the same are only counted),
+    // and prove(nullptr) takes the system's own constant.  Any time before prove(); copied; kept across reset() for the next proof
+    // of the same program, where the structure stays resident on the device.  Not with shard_over().
+    void set_linear_system(const lig_linear_system& sys) {
+        if (pass_ == 3) throw std::logic_error("hip_row_batcher::set_linear_system after prove (reset() first)");
+        if (sharded_) throw std::invalid_argument("hip_row_batcher::set_linear_system: not available on a sharded trace");
+        if (pass_ == 2 && pushed_) throw std::logic_error("hip_row_batcher::set_linear_system: randomness rows have already been handed over");
+        linear_.assign(sys);
+        linear_on_trace_ = false;
+        if (pass_ == 2) apply_linear();
     }
 
     // ---- the callbacks of nonbatch_context_base (nonbatch_context.hpp:78-86).  `rand` rows are null in pass 1.
@@ -192,10 +234,11 @@ public:
         }
         if (trace_) {                                      // the next proof of the same program: every device buffer is reused
             if (same_shape(job)) check(lig_rows_restart(trace_, job.msgs, 0), "lig_rows_restart");
-            else { lig_trace_destroy(trace_); trace_ = nullptr; }
+            else { lig_trace_destroy(trace_); trace_ = nullptr; linear_on_trace_ = false; }
         }
         if (!trace_) check(lig_rows_begin(ctx_, &job, &trace_), "lig_rows_begin");
         shape_kinds_ = kinds_; shape_widths_ = widths; shape_meta_ = meta_;
+        apply_linear();                                   // (a trace that was restarted keeps the structure it has)
         check(lig_rows_commit(trace_, root, stage1_seed), "lig_rows_commit");
         for (auto& kd : kinds_) kd &= 0x7f;               // (pass 2 compares plain kinds)
         begin_pass2(kinds_.size());
@@ -206,12 +249,13 @@ public:
     // (owned by the batcher, valid until it is destroyed or reset); `info` (optional) receives the prover's self-check.
     const uint8_t* prove(const uint8_t const_sum[32], size_t* proof_len, lig_proof_info* info = nullptr) {
         if (pass_ != 2) throw std::logic_error("hip_row_batcher::prove before commit");
-        if (next_ != kinds_.size()) throw std::logic_error("hip_row_batcher::prove: pass 2 replayed " + std::to_string(next_) + " of " + std::to_string(kinds_.size()) + " rows");
+        const bool linear = linear_.is_set() && !sharded_;
+        if (!linear && next_ != kinds_.size()) throw std::logic_error("hip_row_batcher::prove: pass 2 replayed " + std::to_string(next_) + " of " + std::to_string(kinds_.size()) + " rows");
         const uint8_t* proof = nullptr;
         lig_proof_info local;
         if (sharded_) check(lig_shard_rows_prove(shard_, rands_.data(), 0, const_sum, &proof, proof_len, info ? info : &local), "lig_shard_rows_prove");
         else {
-            push_rands(kinds_.size());                     // the tail; everything else went out while the guest was running
+            if (!linear) push_rands(kinds_.size());        // the tail; everything else went out while the guest was running
             check(lig_rows_prove(trace_, nullptr, 0, const_sum, &proof, proof_len, info ? info : &local), "lig_rows_prove");
         }
         pass_ = 3;
@@ -247,8 +291,13 @@ private:
     // randomness rows [pushed_, upto) are complete: hand them to the library while the guest goes on.  Only the rows that HAVE a
     // randomness row are in the staging (packed) and go over the link; the library zero-fills the others on the device
     // (lig_rows_push_rands_sparse) -- batch rows never have one, quadratic rows often do not.
+    void apply_linear() {
+        if (!linear_.is_set() || linear_on_trace_ || !trace_) return;
+        check(lig_rows_set_linear(trace_, linear_.get()), "lig_rows_set_linear");
+        linear_on_trace_ = true;
+    }
     void push_rands(size_t upto) {
-        if (sharded_ || upto <= pushed_) return;
+        if (sharded_ || upto <= pushed_ || linear_.is_set()) return;
         check(lig_rows_push_rands_sparse(trace_, pushed_, upto - pushed_, present_.data() + pushed_, rands_.row(pushed_present_)), "lig_rows_push_rands_sparse");
         pushed_ = upto; pushed_present_ = n_present_;
     }
@@ -338,7 +387,8 @@ private:
         } else if (pass_ == 2) {
             // the guest is deterministic: pass 2 must replay the callbacks of pass 1 in the same order
             if (next_ >= kinds_.size() || kinds_[next_] != kind) throw std::logic_error("hip_row_batcher: pass 2 diverges from pass 1");
-            if (sharded_) {                                                          // dense local matrix: only the rows of this rank's chunks are kept
+            if (linear_.is_set()) {                                                  // the library forms the randomness rows: the replay is only counted
+            } else if (sharded_) {                                                   // dense local matrix: only the rows of this rank's chunks are kept
                 const size_t slot = local_of_[next_];
                 if (slot != (size_t)-1 && !in_slot && rand) std::memcpy(rands_.row(slot), rand, words * 8);
             } else if (in_slot ? slot_has_rand : rand != nullptr) {                   // packed: this row takes the next slot
@@ -371,6 +421,8 @@ private:
     std::vector<uint8_t> kinds_, shape_kinds_, shape_widths_;
     hip_row_staging rows_, rands_;
     lig_trace* trace_ = nullptr;
+    hip_linear_system_copy linear_;
+    bool linear_on_trace_ = false;                        // trace_ holds linear_ (it stays resident across lig_rows_restart)
     bool sharded_ = false;
     uint32_t rank_ = 0, world_ = 1;
     lig_comm comm_{};
@@ -394,6 +446,12 @@ public:
 
     // the row kinds of the public constraint stream, in commit order (a dry run of the guest, or the prover's kinds)
     void expect_rows(const std::vector<uint8_t>& kinds) { kinds_ = kinds; }
+    // the public linear constraints as a sparse term list: finish(nullptr) then forms randomness matrix and constant itself -- no
+    // run of the guest, nothing but the envelope and the public structure.  Before or after begin(); copied.
+    void set_linear_system(const lig_linear_system& sys) {
+        linear_.assign(sys);
+        if (vt_ && lig_rows_verify_set_linear(vt_, linear_.get()) != LIG_OK) throw std::runtime_error(std::string("lig_rows_verify_set_linear: ") + lig_last_error(ctx_));
+    }
     // parse the envelope, re-derive both seeds and the sample indices; false: malformed envelope / wrong indices (reject)
     bool begin(const uint8_t* proof, size_t len, uint8_t stage1_seed[32], lig_verify_info* info = nullptr) {
         std::vector<uint8_t> args;
@@ -409,7 +467,9 @@ public:
         lig_verify_info local;
         const int rc = lig_rows_verify_begin(ctx_, &job, proof, len, &vt_, stage1_seed, info ? info : &local);
         if (rc != LIG_OK) throw std::runtime_error(std::string("lig_rows_verify_begin: ") + lig_last_error(ctx_));
-        rands_.assign(kinds_.size() * (size_t)k_ * 4, 0);
+        if (vt_ && linear_.is_set() && lig_rows_verify_set_linear(vt_, linear_.get()) != LIG_OK)
+            throw std::runtime_error(std::string("lig_rows_verify_set_linear: ") + lig_last_error(ctx_));
+        if (!linear_.is_set()) rands_.assign(kinds_.size() * (size_t)k_ * 4, 0);
         next_ = 0;
         return vt_ != nullptr;
     }
@@ -422,19 +482,20 @@ public:
     // the seven predicates of webgpu_verifier.cpp:412-442; returns accept
     bool finish(const uint8_t const_sum[32], lig_verify_info* info = nullptr) {
         if (!vt_) throw std::logic_error("hip_row_verifier::finish without a successful begin");
-        if (next_ != kinds_.size()) throw std::logic_error("hip_row_verifier::finish: fewer rows replayed than expected");
+        const bool linear = linear_.is_set();
+        if (!linear && next_ != kinds_.size()) throw std::logic_error("hip_row_verifier::finish: fewer rows replayed than expected");
         lig_verify_info local;
         lig_verify_info* o = info ? info : &local;
         lig_vtrace* vt = vt_;
         vt_ = nullptr;                                        // finish frees the trace
-        if (lig_rows_verify_finish(vt, rands_.data(), 0, const_sum, o) != LIG_OK) throw std::runtime_error(std::string("lig_rows_verify_finish: ") + lig_last_error(ctx_));
+        if (lig_rows_verify_finish(vt, linear ? nullptr : rands_.data(), 0, const_sum, o) != LIG_OK) throw std::runtime_error(std::string("lig_rows_verify_finish: ") + lig_last_error(ctx_));
         return o->accept != 0;
     }
 
 private:
     void row(uint8_t kind, const uint64_t* rand) {
         if (next_ >= kinds_.size() || (kinds_[next_] & 0x7f) != kind) throw std::logic_error("hip_row_verifier: the guest diverges from the expected row kinds");
-        if (rand) std::memcpy(rands_.data() + next_ * (size_t)k_ * 4, rand, (size_t)k_ * 32);
+        if (rand && !linear_.is_set()) std::memcpy(rands_.data() + next_ * (size_t)k_ * 4, rand, (size_t)k_ * 32);
         next_++;
     }
     lig_ctx* ctx_;
@@ -443,6 +504,7 @@ private:
     size_t next_ = 0;
     std::vector<uint8_t> kinds_;
     std::vector<uint64_t> rands_;
+    hip_linear_system_copy linear_;
     lig_vtrace* vt_ = nullptr;
 };
 

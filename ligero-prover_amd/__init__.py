@@ -38,12 +38,14 @@ EXPORTS = [
     "lig_device_pci_bus_id", "lig_device_peer_access", "lig_host_alloc", "lig_host_free", "lig_write_async", "lig_fence_record", "lig_fence_wait", "lig_fence_destroy", "lig_rows_push_rands", "lig_rows_push_rands_sparse",
     "lig_abi_sizes", "lig_shard_rows_plan", "lig_shard_rows_begin", "lig_shard_rows_restart", "lig_shard_rows_commit", "lig_shard_rows_prove",
     "lig_upload_health", "lig_profile_read_launches",
+    "lig_linear_check", "lig_linear_form", "lig_rows_set_linear", "lig_rows_verify_set_linear",
 ]
 
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
 ROW_DRAW_PAD = 0x80
 ELEM_BIT = 0x81            # lig_rows_job.elem_bytes: the row's data slots are bits (LIG_ELEM_BIT)
 ARG_I64, ARG_STR, ARG_HEX = 0, 1, 2
+COEF_ONE, COEF_NEG_ONE = 0xFFFFFFFF, 0xFFFFFFFE      # lig_lin_term.coef values that need no table entry (LIG_COEF_ONE / LIG_COEF_NEG_ONE)
 
 
 class VerifyInfo(C.Structure):
@@ -94,6 +96,48 @@ def _attach_public_args(job, args):
     job.public_args = blob.ctypes.data if args else None
     job.public_arg_lens = lens.ctypes.data if args else None
     job.n_public_args = len(args)
+
+
+class LinearSystem(C.Structure):
+    """lig_linear_system: linear constraints sum_j a_cj * w[slot_cj] = b_c as a sparse term list of integers (include/lig_hip.h).
+    Build it with LinearSystem.make(...): the arrays are kept alive on the object."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("reserved", C.c_uint32), ("n_constraints", C.c_uint64), ("n_terms", C.c_uint64),
+                ("term_begin", C.c_void_p), ("terms", C.c_void_p), ("rhs_constraint", C.c_void_p), ("rhs_coef", C.c_void_p),
+                ("n_rhs", C.c_uint64), ("coefs", C.c_void_p), ("n_coefs", C.c_uint64), ("first_random", C.c_uint64)]
+
+    @classmethod
+    def make(cls, term_begin, slots, coef_idx, rhs_constraint=(), rhs_coef=(), coefs=(), first_random=0):
+        """term_begin: n_constraints + 1 offsets into the terms; slots / coef_idx: one entry per term (slot = row * l + column;
+        coefficient = index into `coefs`, COEF_ONE or COEF_NEG_ONE); rhs_constraint / rhs_coef: the constraints with b_c != 0,
+        ascending, and the coefficient index of b_c; coefs: the table, Python integers in [0, p) or an (n, 8) uint32 array"""
+        sys_ = cls()
+        tb = np.ascontiguousarray(term_begin, dtype=np.uint32)
+        slots, coef_idx = np.asarray(slots, dtype=np.uint32), np.asarray(coef_idx, dtype=np.uint32)
+        assert slots.shape == coef_idx.shape and slots.ndim == 1 and tb.ndim == 1 and len(tb) >= 1
+        terms = np.empty((len(slots), 2), dtype=np.uint32)
+        terms[:, 0], terms[:, 1] = slots, coef_idx
+        rc, rb = np.ascontiguousarray(rhs_constraint, dtype=np.uint32), np.ascontiguousarray(rhs_coef, dtype=np.uint32)
+        assert rc.shape == rb.shape and rc.ndim == 1
+        if isinstance(coefs, np.ndarray):
+            tab = np.ascontiguousarray(coefs, dtype=np.uint32).reshape(-1, 8)
+        else:
+            tab = np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in coefs), dtype=np.uint32).reshape(-1, 8).copy()
+        sys_._keep = (tb, terms, rc, rb, tab)
+        sys_.struct_bytes = C.sizeof(cls)
+        sys_.n_constraints, sys_.n_terms, sys_.n_rhs, sys_.n_coefs = len(tb) - 1, len(terms), len(rc), len(tab)
+        sys_.term_begin = tb.ctypes.data
+        sys_.terms = terms.ctypes.data if len(terms) else None
+        sys_.rhs_constraint = rc.ctypes.data if len(rc) else None
+        sys_.rhs_coef = rb.ctypes.data if len(rb) else None
+        sys_.coefs = tab.ctypes.data if len(tab) else None
+        sys_.first_random = first_random
+        return sys_
+
+
+def linear_check(system, kinds, l):
+    """lig_linear_check (host only) -> the return code: 0, or LIG_E_ARG (-1) for a system that breaks a rule of the format"""
+    kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+    return load_library().lig_linear_check(C.byref(system), kinds.ctypes.data if len(kinds) else None, len(kinds), l)
 
 
 class ProofInfo(C.Structure):
@@ -227,6 +271,10 @@ def load_library():
     L.lig_profile_enable.argtypes = [vp, C.c_int]
     L.lig_profile_read.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_double)]
     L.lig_profile_read_launches.argtypes = [vp, u32, C.POINTER(u64), C.POINTER(C.c_double)]
+    L.lig_linear_check.argtypes = [C.POINTER(LinearSystem), vp, u64, u32]
+    L.lig_linear_form.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, vp]
+    L.lig_rows_set_linear.argtypes = [vp, C.POINTER(LinearSystem)]
+    L.lig_rows_verify_set_linear.argtypes = [vp, C.POINTER(LinearSystem)]
     return L
 
 
@@ -763,15 +811,38 @@ class Context:
         return (vt if vt.value else None), seed.tobytes(), info
 
     def rows_verify_finish(self, vtrace, rands, const_sum, on_device=False):
+        """rands=None / const_sum=None: formed from the linear system set with rows_verify_set_linear"""
         info = VerifyInfo()
-        cs = np.frombuffer(bytes(const_sum), dtype=np.uint8).copy()
-        if on_device:
+        cs = np.frombuffer(bytes(const_sum), dtype=np.uint8).copy() if const_sum is not None else None
+        if rands is None:
+            rp = None
+        elif on_device:
             rp = rands
         else:
             rands = np.ascontiguousarray(rands, dtype=np.uint32)
             rp = C.c_void_p(rands.ctypes.data if rands.size else None)
         self.check(self.L.lig_rows_verify_finish(vtrace, rp, int(bool(on_device)), _hptr(cs), C.byref(info)))
         return info
+
+    # ---- sparse linear constraints: the linear-test randomness formed on the GPU (LinearSystem)
+    def linear_check(self, system, kinds):
+        return linear_check(system, kinds, self.l)
+
+    def rows_set_linear(self, trace, system):
+        """lig_rows_set_linear: rows_prove(trace, None, None) then forms randomness matrix and constant itself; None removes it"""
+        self.check(self.L.lig_rows_set_linear(trace, C.byref(system) if system is not None else None))
+
+    def rows_verify_set_linear(self, vtrace, system):
+        self.check(self.L.lig_rows_verify_set_linear(vtrace, C.byref(system) if system is not None else None))
+
+    def linear_form(self, system, kinds, key, out):
+        """lig_linear_form: out (device, len(kinds) x k x 32 bytes) <- the randomness matrix for the stream keyed by `key`;
+        -> the constant (32 bytes)"""
+        kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+        kb = np.frombuffer(bytes(key), dtype=np.uint8).copy()
+        cs = np.zeros(32, dtype=np.uint8)
+        self.check(self.L.lig_linear_form(self.h, C.byref(system), kinds.ctypes.data if len(kinds) else None, len(kinds), _hptr(kb), out, _hptr(cs)))
+        return cs.tobytes()
 
     def vtrace_destroy(self, vtrace):
         """give up a verification between begin and finish (finish frees the trace itself)"""

@@ -1,0 +1,327 @@
+// linear.hip -- sparse linear constraints: the linear-test randomness rows formed on the device (lig_linear_*, lig_rows_set_linear).
+//
+// The reference draws ONE element r_c per linear constraint c from the linear random engine and adds a * r_c to the randomness of
+// every witness the constraint touches, b_c * r_c to the public constant (witness_manager.hpp:344-388).  For constraints
+// sum_j a_cj * w[slot_cj] = b_c that is
+//     Rn[slot s] = sum over terms (c, s, a) of a * r_c            const_sum = - sum_c b_c * r_c
+// The structure (which constraint touches which slot with which coefficient) does not depend on the stage-1 seed, so the work is
+// split in two:
+//   prepare (once per lig_rows_set_linear, off the proving path): the term list, given constraint by constraint, is regrouped BY
+//     SLOT -- a per-slot count (32-bit atomics: they only decide where a term lands inside its slot's segment, and the sum over a
+//     segment is exact, so the result does not depend on them), an exclusive scan (rocPRIM), a scatter of (constraint, coefficient)
+//     pairs.  Rows no term touches and slots with very many terms are found here.
+//   form (per proof, on the side stream under the encodes): r = n_constraints elements of the AES-256-CTR field stream keyed by the
+//     stage-1 seed (aes.hip), then ONE pass in slot order in which every slot has exactly one owner:
+//       k_lin_form         one lane per slot of a touched row: gathers r_c (32 bytes, random), adds / subtracts it, or multiplies it
+//                          by a table coefficient first (the table is kept in Montgomery form: one product per such term, none for
+//                          +1 / -1); writes the canonical sum, zeros for slots without terms and for the pad slots [l, k)
+//       k_lin_heavy_part   a slot with more than HEAVY_MIN terms: HEAVY_PARTS workgroups each sum a fixed slice of its segment
+//       k_lin_heavy_fin    (LDS tree), one lane adds the HEAVY_PARTS partial sums in a fixed order -- a deterministic tree
+//       k_lin_const_*      block-wise modular reduction over the n_rhs products b_c * r_c, finished (and negated) by a last block
+//     rows no term touches are cleared with a memset.
+// Field arithmetic: canonical 8 x u32 (fr.hpp).  A term costs one 256-bit modular add (~50 VALU instructions) against a random
+// 32-byte gather from a vector that does not fit the last-level cache at 2^24 constraints: the pass is bound by the gather, not by
+// VALU, so the 29-bit-limb forms of fr29.hpp would buy nothing here.
+#include <cstring>
+
+#include <rocprim/device/device_scan.hpp>
+
+#include "prover_common.hpp"
+
+namespace lig {
+static constexpr uint32_t LIN_WG = 256;
+static constexpr uint32_t HEAVY_MIN = 2048;       // a slot with more terms than this is summed by HEAVY_PARTS workgroups
+static constexpr uint32_t HEAVY_PARTS = 32;
+static constexpr uint32_t CONST_BLOCKS = 256;     // partial sums of the constant (one per workgroup), reduced by a last block
+
+// ---------------------------------------------------------------- prepare
+// constraint of term t: the c with term_begin[c] <= t < term_begin[c + 1] (constraints may be empty)
+static __device__ __forceinline__ uint32_t lin_constraint_of(const uint32_t* __restrict__ term_begin, uint32_t n_constraints, uint32_t t) {
+    uint32_t lo = 0, hi = n_constraints;          // first index in (0, n_constraints] whose entry is > t, minus one
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (term_begin[mid + 1] > t) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+__global__ void __launch_bounds__(LIN_WG) k_lin_count(const lig_lin_term* __restrict__ terms, uint32_t n_terms, uint32_t* __restrict__ count) {
+    for (uint64_t t = blockIdx.x * LIN_WG + threadIdx.x; t < n_terms; t += gridDim.x * LIN_WG) atomicAdd(count + terms[t].slot, 1u);
+}
+__global__ void __launch_bounds__(LIN_WG) k_lin_scatter(const lig_lin_term* __restrict__ terms, uint32_t n_terms, const uint32_t* __restrict__ term_begin,
+                                                        uint32_t n_constraints, const uint32_t* __restrict__ begin, uint32_t* __restrict__ cursor,
+                                                        uint2* __restrict__ ent) {
+    for (uint64_t t = blockIdx.x * LIN_WG + threadIdx.x; t < n_terms; t += gridDim.x * LIN_WG) {
+        const lig_lin_term tm = terms[t];
+        const uint32_t pos = begin[tm.slot] + atomicAdd(cursor + tm.slot, 1u);
+        ent[pos] = make_uint2(lin_constraint_of(term_begin, n_constraints, (uint32_t)t), tm.coef);
+    }
+}
+// which rows carry a term at all; which slots are heavy (appended in any order: the host sorts the list)
+__global__ void __launch_bounds__(LIN_WG) k_lin_classify(const uint32_t* __restrict__ begin, uint32_t n_slots, uint32_t l, uint8_t* __restrict__ row_touched,
+                                                         uint32_t* __restrict__ heavy, uint32_t heavy_cap, uint32_t* __restrict__ n_heavy) {
+    for (uint64_t s = blockIdx.x * LIN_WG + threadIdx.x; s < n_slots; s += gridDim.x * LIN_WG) {
+        const uint32_t cnt = begin[s + 1] - begin[s];
+        if (cnt) row_touched[s / l] = 1;
+        if (cnt > HEAVY_MIN) { const uint32_t i = atomicAdd(n_heavy, 1u); if (i < heavy_cap) heavy[i] = (uint32_t)s; }
+    }
+}
+
+// ---------------------------------------------------------------- form
+// acc (canonical) += coef * r_c for one (constraint, coefficient) entry
+static __device__ __forceinline__ fr lin_accumulate(const fr& acc, const uint2 e, const fr* __restrict__ r, const fr* __restrict__ coef_mont) {
+    const fr v = fr_load(r + e.x);
+    if (e.y == LIG_COEF_ONE) return fr_add(acc, v);
+    if (e.y == LIG_COEF_NEG_ONE) return fr_sub(acc, v);
+    return fr_add(acc, fr_montmul(v, fr_load(coef_mont + e.y)));      // (a R) * r / R = a * r, canonical
+}
+// sum of the workgroup's LIN_WG values (fixed tree: the same bytes on every run); valid in thread 0
+static __device__ __forceinline__ fr lin_block_sum(fr v, fr* sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (uint32_t w = LIN_WG / 2; w; w >>= 1) {
+        if (threadIdx.x < w) sh[threadIdx.x] = fr_add(sh[threadIdx.x], sh[threadIdx.x + w]);
+        __syncthreads();
+    }
+    return sh[0];
+}
+// lane = slot `col` of touched row trows[blockIdx.y + ...]; heavy slots are left to k_lin_heavy_*
+__global__ void __launch_bounds__(LIN_WG) k_lin_form(const uint32_t* __restrict__ trows, uint32_t n_trows, uint32_t l, uint32_t k,
+                                                     const uint32_t* __restrict__ begin, const uint2* __restrict__ ent, const fr* __restrict__ r,
+                                                     const fr* __restrict__ coef_mont, fr* __restrict__ out) {
+    const uint32_t col = blockIdx.x * LIN_WG + threadIdx.x;
+    if (col >= k) return;
+    for (uint32_t ti = blockIdx.y; ti < n_trows; ti += gridDim.y) {
+        const uint32_t row = trows[ti];
+        fr acc = fr_zero();
+        if (col < l) {
+            const uint32_t s = row * l + col, b = begin[s], e = begin[s + 1];
+            if (e - b > HEAVY_MIN) continue;
+            for (uint32_t i = b; i < e; i++) acc = lin_accumulate(acc, ent[i], r, coef_mont);
+        }
+        fr_store(out + (size_t)row * k + col, acc);
+    }
+}
+// workgroup (h, p): slice p of the segment of heavy slot heavy[h]
+__global__ void __launch_bounds__(LIN_WG) k_lin_heavy_part(const uint32_t* __restrict__ heavy, const uint32_t* __restrict__ begin, const uint2* __restrict__ ent,
+                                                           const fr* __restrict__ r, const fr* __restrict__ coef_mont, fr* __restrict__ part) {
+    __shared__ fr sh[LIN_WG];
+    const uint32_t s = heavy[blockIdx.x], b = begin[s], cnt = begin[s + 1] - b;
+    const uint32_t per = (cnt + HEAVY_PARTS - 1) / HEAVY_PARTS;
+    const uint32_t lo = min(cnt, blockIdx.y * per), hi = min(cnt, lo + per);
+    fr acc = fr_zero();
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += LIN_WG) acc = lin_accumulate(acc, ent[b + i], r, coef_mont);
+    acc = lin_block_sum(acc, sh);
+    if (threadIdx.x == 0) fr_store(part + (size_t)blockIdx.x * HEAVY_PARTS + blockIdx.y, acc);
+}
+__global__ void __launch_bounds__(LIN_WG) k_lin_heavy_fin(const uint32_t* __restrict__ heavy, uint32_t n_heavy, uint32_t l, uint32_t k, const fr* __restrict__ part,
+                                                          fr* __restrict__ out) {
+    const uint32_t h = blockIdx.x * LIN_WG + threadIdx.x;
+    if (h >= n_heavy) return;
+    fr acc = fr_zero();
+    for (uint32_t p = 0; p < HEAVY_PARTS; p++) acc = fr_add(acc, fr_load(part + (size_t)h * HEAVY_PARTS + p));
+    const uint32_t s = heavy[h];
+    fr_store(out + (size_t)(s / l) * k + s % l, acc);
+}
+// partial sums of sum_i b_i * r_{c_i} over the constraints with a right-hand side
+__global__ void __launch_bounds__(LIN_WG) k_lin_const_part(const uint32_t* __restrict__ rhs_c, const uint32_t* __restrict__ rhs_coef, uint32_t n_rhs,
+                                                           const fr* __restrict__ r, const fr* __restrict__ coef_mont, fr* __restrict__ part) {
+    __shared__ fr sh[LIN_WG];
+    fr acc = fr_zero();
+    for (uint64_t i = blockIdx.x * LIN_WG + threadIdx.x; i < n_rhs; i += gridDim.x * LIN_WG) acc = lin_accumulate(acc, make_uint2(rhs_c[i], rhs_coef[i]), r, coef_mont);
+    acc = lin_block_sum(acc, sh);
+    if (threadIdx.x == 0) fr_store(part + blockIdx.x, acc);
+}
+// one workgroup: out = - sum of the n_part partial sums
+__global__ void __launch_bounds__(LIN_WG) k_lin_const_fin(const fr* __restrict__ part, uint32_t n_part, fr* __restrict__ out) {
+    __shared__ fr sh[LIN_WG];
+    fr acc = fr_zero();
+    for (uint32_t i = threadIdx.x; i < n_part; i += LIN_WG) acc = fr_add(acc, fr_load(part + i));
+    acc = lin_block_sum(acc, sh);
+    if (threadIdx.x == 0) fr_store(out, fr_neg(acc));
+}
+}  // namespace lig
+
+// a linear system on the device, regrouped by slot (lig_internal_linear_create)
+struct lig_linear {
+    lig_ctx* c = nullptr;
+    uint32_t l = 0, k = 0;
+    uint64_t rows = 0, n_constraints = 0, n_terms = 0, n_rhs = 0, n_coefs = 0, first_random = 0;
+    uint32_t n_slots = 0, n_heavy = 0, n_trows = 0;
+    uint32_t* begin = nullptr;          // n_slots + 1: the segment of slot s is ent[begin[s] .. begin[s + 1])
+    uint2* ent = nullptr;               // n_terms (constraint, coefficient index) pairs in slot order
+    fr* coef_mont = nullptr;            // the coefficient table, Montgomery form
+    uint32_t* rhs_c = nullptr; uint32_t* rhs_coef = nullptr;
+    uint32_t* heavy = nullptr;          // slots with more than HEAVY_MIN terms, ascending
+    uint32_t* trows = nullptr;          // rows with at least one term, ascending
+    fr* r = nullptr;                    // n_constraints stream elements (per proof)
+    fr* part = nullptr;                 // n_heavy x HEAVY_PARTS | CONST_BLOCKS | the constant
+    uint8_t* h_const = nullptr;         // pinned, 32 bytes: the constant of the last form
+    std::vector<std::pair<uint64_t, uint64_t>> zero_runs;      // (first row, rows) no term touches
+};
+
+static bool lin_coef_ok(uint32_t coef, uint64_t n_coefs) { return coef == LIG_COEF_ONE || coef == LIG_COEF_NEG_ONE || coef < n_coefs; }
+
+extern "C" int lig_linear_check(const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, uint32_t l) {
+    if (!sys || sys->struct_bytes < sizeof(lig_linear_system)) return LIG_E_ARG;
+    if (!l || (rows && !kinds) || rows * (uint64_t)l >= (1ull << 32) || rows >= (1ull << 32)) return LIG_E_ARG;
+    if (sys->n_terms >= (1ull << 32) || sys->n_constraints >= 0xFFFFFFFFull || sys->n_rhs > sys->n_constraints || sys->n_coefs >= LIG_COEF_NEG_ONE) return LIG_E_ARG;
+    if (sys->first_random + sys->n_constraints < sys->first_random) return LIG_E_ARG;
+    if (!sys->term_begin || (sys->n_terms && !sys->terms) || (sys->n_rhs && (!sys->rhs_constraint || !sys->rhs_coef)) || (sys->n_coefs && !sys->coefs)) return LIG_E_ARG;
+    if (sys->term_begin[0] != 0 || sys->term_begin[sys->n_constraints] != sys->n_terms) return LIG_E_ARG;
+    for (uint64_t c = 0; c < sys->n_constraints; c++) if (sys->term_begin[c + 1] < sys->term_begin[c]) return LIG_E_ARG;
+    for (uint64_t t = 0; t < sys->n_terms; t++) {
+        const uint64_t row = sys->terms[t].slot / l;
+        if (row >= rows || (kinds[row] & 0x7f) > LIG_ROW_QZ || !lin_coef_ok(sys->terms[t].coef, sys->n_coefs)) return LIG_E_ARG;
+    }
+    for (uint64_t i = 0; i < sys->n_rhs; i++) {
+        if (sys->rhs_constraint[i] >= sys->n_constraints || (i && sys->rhs_constraint[i] <= sys->rhs_constraint[i - 1])) return LIG_E_ARG;
+        if (!lin_coef_ok(sys->rhs_coef[i], sys->n_coefs)) return LIG_E_ARG;
+    }
+    for (uint64_t i = 0; i < sys->n_coefs; i++) {
+        H::Fr v;
+        std::memcpy(v.v, sys->coefs + 32 * i, 32);
+        if (H::geq(v, H::P)) return LIG_E_ARG;
+    }
+    return LIG_OK;
+}
+
+void lig_internal_linear_destroy(lig_linear* L) {
+    if (!L) return;
+    (void)hipSetDevice(L->c->device);
+    for (hipStream_t st : {L->c->stream, L->c->stream2}) if (st) (void)hipStreamSynchronize(st);
+    for (void* p : {(void*)L->begin, (void*)L->ent, (void*)L->coef_mont, (void*)L->rhs_c, (void*)L->rhs_coef, (void*)L->heavy, (void*)L->trows, (void*)L->r, (void*)L->part})
+        (void)hipFree(p);
+    (void)hipHostFree(L->h_const);
+    delete L;
+}
+
+static uint32_t lin_grid(uint64_t items) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + lig::LIN_WG - 1) / lig::LIN_WG, 1), 65535); }
+
+static int linear_prepare(lig_ctx* c, const lig_linear_system* sys, lig_linear* L) {
+    hipStream_t s = c->stream;
+    const uint32_t S = L->n_slots, NT = (uint32_t)L->n_terms, NC = (uint32_t)L->n_constraints;
+    auto dmalloc = [&](void** p, size_t bytes) -> int { HIP_TRY(c, hipMalloc(p, bytes ? bytes : 16)); return LIG_OK; };
+    TRY(dmalloc((void**)&L->begin, ((size_t)S + 1) * 4));
+    TRY(dmalloc((void**)&L->ent, (size_t)NT * sizeof(uint2)));
+    TRY(dmalloc((void**)&L->coef_mont, L->n_coefs * 32));
+    TRY(dmalloc((void**)&L->rhs_c, L->n_rhs * 4));
+    TRY(dmalloc((void**)&L->rhs_coef, L->n_rhs * 4));
+    TRY(dmalloc((void**)&L->r, L->n_constraints * 32));
+    HIP_TRY(c, hipHostMalloc((void**)&L->h_const, 32, hipHostMallocDefault));
+    std::memset(L->h_const, 0, 32);
+    const uint32_t heavy_cap = NT / (lig::HEAVY_MIN + 1) + 1;
+    TRY(dmalloc((void**)&L->heavy, (size_t)heavy_cap * 4));
+    // scratch of this call only
+    lig_lin_term* d_terms = nullptr; uint32_t *d_tb = nullptr, *d_cursor = nullptr, *d_count = nullptr, *d_nheavy = nullptr; uint8_t* d_touched = nullptr; void* d_scan = nullptr;
+    struct Scratch { std::vector<void**> v; lig_ctx* c; ~Scratch() { (void)hipStreamSynchronize(c->stream); for (void** p : v) (void)hipFree(*p); } }
+        scratch{{(void**)&d_terms, (void**)&d_tb, (void**)&d_cursor, (void**)&d_count, (void**)&d_nheavy, (void**)&d_touched, &d_scan}, c};
+    TRY(dmalloc((void**)&d_terms, (size_t)NT * sizeof(lig_lin_term)));
+    TRY(dmalloc((void**)&d_tb, ((size_t)NC + 1) * 4));
+    TRY(dmalloc((void**)&d_cursor, (size_t)S * 4));
+    TRY(dmalloc((void**)&d_count, ((size_t)S + 1) * 4));
+    TRY(dmalloc((void**)&d_nheavy, 4));
+    TRY(dmalloc((void**)&d_touched, L->rows));
+    // the coefficient table in Montgomery form: a term with a table coefficient is one Montgomery product
+    std::vector<H::Fr> cm(L->n_coefs);
+    for (uint64_t i = 0; i < L->n_coefs; i++) { H::Fr v; std::memcpy(v.v, sys->coefs + 32 * i, 32); cm[i] = H::to_mont(v); }
+    if (NT) HIP_TRY(c, hipMemcpyAsync(d_terms, sys->terms, (size_t)NT * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d_tb, sys->term_begin, ((size_t)NC + 1) * 4, hipMemcpyHostToDevice, s));
+    if (L->n_coefs) HIP_TRY(c, hipMemcpyAsync(L->coef_mont, cm.data(), L->n_coefs * 32, hipMemcpyHostToDevice, s));
+    if (L->n_rhs) {
+        HIP_TRY(c, hipMemcpyAsync(L->rhs_c, sys->rhs_constraint, L->n_rhs * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(L->rhs_coef, sys->rhs_coef, L->n_rhs * 4, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(c, hipMemsetAsync(d_count, 0, ((size_t)S + 1) * 4, s));
+    HIP_TRY(c, hipMemsetAsync(d_cursor, 0, (size_t)S * 4, s));
+    HIP_TRY(c, hipMemsetAsync(d_nheavy, 0, 4, s));
+    if (L->rows) HIP_TRY(c, hipMemsetAsync(d_touched, 0, L->rows, s));
+    if (NT) hipLaunchKernelGGL(lig::k_lin_count, dim3(lin_grid(NT)), dim3(lig::LIN_WG), 0, s, d_terms, NT, d_count);
+    size_t scan_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, d_count, L->begin, 0u, (size_t)S + 1, rocprim::plus<uint32_t>(), s));
+    TRY(dmalloc(&d_scan, scan_bytes));
+    HIP_TRY(c, rocprim::exclusive_scan(d_scan, scan_bytes, d_count, L->begin, 0u, (size_t)S + 1, rocprim::plus<uint32_t>(), s));
+    if (NT) hipLaunchKernelGGL(lig::k_lin_scatter, dim3(lin_grid(NT)), dim3(lig::LIN_WG), 0, s, d_terms, NT, d_tb, NC, L->begin, d_cursor, L->ent);
+    if (S) hipLaunchKernelGGL(lig::k_lin_classify, dim3(lin_grid(S)), dim3(lig::LIN_WG), 0, s, L->begin, S, L->l, d_touched, L->heavy, heavy_cap, d_nheavy);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint8_t> touched(L->rows);
+    uint32_t n_heavy = 0;
+    if (L->rows) HIP_TRY(c, hipMemcpyAsync(touched.data(), d_touched, L->rows, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&n_heavy, d_nheavy, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (n_heavy > heavy_cap) FAIL(c, LIG_E_STATE, "linear system: heavy-slot list overflow");      // (cannot happen: more than HEAVY_MIN terms each)
+    L->n_heavy = n_heavy;
+    if (n_heavy) {      // ascending: the same launch geometry whatever order the atomics appended them in
+        std::vector<uint32_t> hv(n_heavy);
+        HIP_TRY(c, hipMemcpy(hv.data(), L->heavy, (size_t)n_heavy * 4, hipMemcpyDeviceToHost));
+        std::sort(hv.begin(), hv.end());
+        HIP_TRY(c, hipMemcpy(L->heavy, hv.data(), (size_t)n_heavy * 4, hipMemcpyHostToDevice));
+    }
+    std::vector<uint32_t> trows;
+    for (uint64_t r = 0; r < L->rows;) {
+        if (touched[r]) { trows.push_back((uint32_t)r); r++; continue; }
+        uint64_t e = r + 1;
+        while (e < L->rows && !touched[e]) e++;
+        L->zero_runs.push_back({r, e - r});
+        r = e;
+    }
+    L->n_trows = (uint32_t)trows.size();
+    TRY(dmalloc((void**)&L->trows, trows.size() * 4));
+    if (!trows.empty()) HIP_TRY(c, hipMemcpy(L->trows, trows.data(), trows.size() * 4, hipMemcpyHostToDevice));
+    TRY(dmalloc((void**)&L->part, ((size_t)n_heavy * lig::HEAVY_PARTS + lig::CONST_BLOCKS + 1) * 32));
+    return LIG_OK;
+}
+
+// check, upload, regroup by slot; synchronous (every pointer of *sys may be released when it returns)
+int lig_internal_linear_create(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, lig_linear** out) {
+    *out = nullptr;
+    if (lig_linear_check(sys, kinds, rows, c->l) != LIG_OK) FAIL(c, LIG_E_ARG, "linear system: rejected by lig_linear_check");
+    lig_linear* L = new lig_linear();
+    L->c = c; L->l = c->l; L->k = c->k; L->rows = rows;
+    L->n_constraints = sys->n_constraints; L->n_terms = sys->n_terms; L->n_rhs = sys->n_rhs; L->n_coefs = sys->n_coefs; L->first_random = sys->first_random;
+    L->n_slots = (uint32_t)(rows * c->l);
+    const int rc = linear_prepare(c, sys, L);
+    if (rc != LIG_OK) { const std::string why = c->err; lig_internal_linear_destroy(L); c->err = why; return rc; }
+    *out = L;
+    return LIG_OK;
+}
+
+// enqueue on `st`: rands_dev (rows x k) <- the randomness matrix of the system for the stream whose round keys are in rk60_dev;
+// the constant lands in lig_internal_linear_const() once the work queued on `st` has been waited for
+int lig_internal_linear_form(lig_ctx* c, lig_linear* L, const uint32_t* rk60_dev, fr* rands_dev, hipStream_t st) {
+    const size_t row_bytes = (size_t)L->k * 32;
+    for (const auto& z : L->zero_runs) HIP_TRY(c, hipMemsetAsync(rands_dev + z.first * L->k, 0, z.second * row_bytes, st));
+    lig::launch_rng_fill(st, rk60_dev, L->first_random, L->r, L->n_constraints);
+    fr* hpart = L->part; fr* cpart = L->part + (size_t)L->n_heavy * lig::HEAVY_PARTS; fr* cst = cpart + lig::CONST_BLOCKS;
+    if (L->n_trows) {
+        const dim3 grid((L->k + lig::LIN_WG - 1) / lig::LIN_WG, std::min<uint32_t>(L->n_trows, 65535));
+        hipLaunchKernelGGL(lig::k_lin_form, grid, dim3(lig::LIN_WG), 0, st, L->trows, L->n_trows, L->l, L->k, L->begin, L->ent, L->r, L->coef_mont, rands_dev);
+    }
+    if (L->n_heavy) {
+        hipLaunchKernelGGL(lig::k_lin_heavy_part, dim3(L->n_heavy, lig::HEAVY_PARTS), dim3(lig::LIN_WG), 0, st, L->heavy, L->begin, L->ent, L->r, L->coef_mont, hpart);
+        hipLaunchKernelGGL(lig::k_lin_heavy_fin, dim3((L->n_heavy + lig::LIN_WG - 1) / lig::LIN_WG), dim3(lig::LIN_WG), 0, st, L->heavy, L->n_heavy, L->l, L->k, hpart, rands_dev);
+    }
+    const uint32_t cb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((L->n_rhs + lig::LIN_WG - 1) / lig::LIN_WG, 1), lig::CONST_BLOCKS);
+    hipLaunchKernelGGL(lig::k_lin_const_part, dim3(cb), dim3(lig::LIN_WG), 0, st, L->rhs_c, L->rhs_coef, (uint32_t)L->n_rhs, L->r, L->coef_mont, cpart);
+    hipLaunchKernelGGL(lig::k_lin_const_fin, dim3(1), dim3(lig::LIN_WG), 0, st, cpart, cb, cst);
+    HIP_TRY(c, hipGetLastError());
+    return lig_internal_download(c, L->h_const, cst, 32, st);
+}
+const uint8_t* lig_internal_linear_const(const lig_linear* L) { return L->h_const; }
+
+extern "C" int lig_linear_form(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, const uint8_t key32[32], void* rands_dev,
+                               uint8_t const_sum[32]) {
+    CHECK_CTX(c);
+    if (!key32 || !const_sum || (rows && !rands_dev)) return LIG_E_ARG;
+    lig_linear* L = nullptr;
+    TRY(lig_internal_linear_create(c, sys, kinds, rows, &L));
+    uint32_t rk[60];
+    lig::aes256_expand_host(key32, rk);
+    int rc = lig_internal_upload_small(c, c->rk_dev, rk, sizeof rk, c->stream);
+    if (rc == LIG_OK) rc = lig_internal_linear_form(c, L, c->rk_dev, (fr*)rands_dev, c->stream);
+    if (rc == LIG_OK && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "lig_linear_form: stream synchronize failed"; rc = LIG_E_HIP; }
+    if (rc == LIG_OK) std::memcpy(const_sum, L->h_const, 32);
+    const std::string why = c->err;
+    lig_internal_linear_destroy(L);
+    c->err = why;
+    return rc;
+}

@@ -44,7 +44,8 @@ struct lig_trace {
     uint32_t rand_seq = 0;              // ... of the last randomness-rows upload (its own flag words, its own counter: a restart
                                         // between commit and prove must not move what the next commit waits for)
     bool up_by_thread = false;
-    fr* rands_full = nullptr;           // lig_rows_push_rands: R x k, device resident
+    fr* rands_full = nullptr;           // lig_rows_push_rands / lig_rows_set_linear: R x k, device resident
+    lig_linear* linear = nullptr;       // lig_rows_set_linear: the sparse linear system, regrouped by slot (linear.hip); survives lig_rows_restart
     uint64_t rands_pushed = 0;          // rows handed to the uploader so far (word up_words - 1 counts the rows that have ARRIVED)
     size_t up_words = 0;                // words in up_flag: [stage-1 chunks | stage-2 chunks: randomness rows arrived | ... consumed]
     bool push_sync = false;             // lig_rows_push_rands without an uploader thread: the pushed rows were copied synchronously
@@ -429,7 +430,8 @@ static int prove_stage1(lig_trace* T, lig_proof_info* info, const std::function<
 
 // where the stage-2 randomness rows come from: generated (dense rows of the synthetic stream, from the linear stream
 // keyed by the stage-1 seed) or supplied by the caller (device pointer used in place / host rows uploaded chunk-wise)
-struct RandSource { const fr* dev = nullptr; const uint8_t* host = nullptr; bool pushed = false; };
+struct RandSource { const fr* dev = nullptr; const uint8_t* host = nullptr; bool pushed = false;
+                    lig_linear* linear = nullptr; };      // linear: `dev` (= T->rands_full) is formed from the sparse linear system on the side stream
 
 // ================= stage 2 + 3
 static int prove_stage23(lig_trace* T, const RandSource& rs, const uint8_t* const_sum_given, const uint8_t** proof, size_t* proof_len,
@@ -546,6 +548,9 @@ static int prove_stage23(lig_trace* T, const RandSource& rs, const uint8_t* cons
     }
     HIP_TRY(c, hipEventRecord(c->ev_fork, s));            // the side stream starts after the key / coefficient uploads and the memsets above
     HIP_TRY(c, hipStreamWaitEvent(s2, c->ev_fork, 0));
+    // sparse linear system: the whole randomness matrix is formed on the side stream (r_c from the linear stream, one pass in slot
+    // order: linear.hip) while the main stream accumulates the code test below; stage 2 then finds it where an uploaded matrix would be
+    if (rs.linear) TRY(lig_internal_linear_form(c, rs.linear, c->rk_dev, const_cast<fr*>(rs.dev), s2));
     if (n_chunks) TRY(form_rand_chunk(0));
     // (the side stream is already sampling the first randomness rows while the main stream does this)
     // The code-test accumulator does not depend on the randomness rows: it is formed FIRST (one pass over the message rows, one
@@ -636,7 +641,11 @@ static int prove_stage23(lig_trace* T, const RandSource& rs, const uint8_t* cons
         h2.finish(info->stage2_seed);
     }
     if (const_sum_given) std::memcpy(info->const_sum, const_sum_given, 32);     // the caller's public constant (linear_sums)
-    else {
+    else if (rs.linear) {
+        // the statement's own constant -sum_c b_c r_c, formed on the side stream (in host memory since the first chunk's event)
+        if (n_chunks) HIP_TRY(c, wait_event(T->ev_ready[0])); else HIP_TRY(c, wait_stream(s2));      // (every record of that event follows the form on the side stream)
+        std::memcpy(info->const_sum, lig_internal_linear_const(rs.linear), 32);
+    } else {
         // synthetic stream: every witness slot carries the constraint w_i = b_i with b public (derived from witness_key), so
         // the constant is minus the sum of all inner products <witness row, randomness row> = minus the sum of linH
         const H::Fr sum = H::neg(dots[0]);
@@ -749,6 +758,7 @@ void lig_trace_destroy(lig_trace* T) {
     uploader_drain(T);                                    // an upload still in flight
     rand_drain(T);
     if (T->c->stream_sha) (void)hipStreamSynchronize(T->c->stream_sha);      // (experiment knob LIG_SHA_CUMASK: the stage-1 hash stream)
+    lig_internal_linear_destroy(T->linear);
     T->c->sha.erase(T->sha_state);
     if (T->leak) {      // destinations of a transfer that was given up on and has never completed (upload_settled): they outlive the trace
         T->rands_full = nullptr; T->msgs_alt = nullptr; T->msgs = nullptr; T->randb = nullptr; T->packed_dev = nullptr;
@@ -1192,7 +1202,8 @@ int lig_rows_prove(lig_trace* T, const void* rands, int rands_on_device, const u
     lig_ctx* c = T->c;
     CHECK_CTX(c);
     if (!T->from_rows || !T->committed) FAIL(c, LIG_E_STATE, "lig_rows_prove: lig_rows_commit has not run on this trace");
-    if (T->R && !rands && !T->dense_rands && !T->rands_pushed) FAIL(c, LIG_E_ARG, "lig_rows_prove: null randomness rows");
+    if (T->linear && rands) FAIL(c, LIG_E_ARG, "lig_rows_prove: randomness rows given while a linear system is set (lig_rows_set_linear)");
+    if (T->R && !rands && !T->dense_rands && !T->rands_pushed && !T->linear) FAIL(c, LIG_E_ARG, "lig_rows_prove: null randomness rows");
     if (const_sum) {
         H::Fr v;
         std::memcpy(v.v, const_sum, 32);
@@ -1209,6 +1220,7 @@ int lig_rows_prove(lig_trace* T, const void* rands, int rands_on_device, const u
         T->rands_pushed = 0;
     }
     if (rands && rands_on_device) rs.dev = (const fr*)rands; else if (rands) rs.host = (const uint8_t*)rands;
+    else if (T->linear) { rs.dev = T->rands_full; rs.linear = T->linear; }
     else if (T->rands_pushed) {
         if (T->rands_pushed != T->R) FAIL(c, LIG_E_STATE, "lig_rows_prove: lig_rows_push_rands has not delivered every row");
         rs.dev = T->rands_full; rs.pushed = true;
@@ -1260,6 +1272,31 @@ int lig_rows_prove(lig_trace* T, const void* rands, int rands_on_device, const u
     return LIG_OK;
 }
 
+int lig_rows_set_linear(lig_trace* T, const lig_linear_system* sys) {
+    if (!T) return LIG_E_ARG;
+    lig_ctx* c = T->c;
+    CHECK_CTX(c);
+    if (!T->from_rows || !(T->loaded || T->committed)) FAIL(c, LIG_E_STATE, "lig_rows_set_linear: between lig_rows_begin and lig_rows_prove");
+    if (T->rands_pushed) FAIL(c, LIG_E_STATE, "lig_rows_set_linear: randomness rows have already been pushed");
+    if (!sys) {
+        lig_internal_linear_destroy(T->linear);
+        T->linear = nullptr;
+        return LIG_OK;
+    }
+    if (T->dense_rands) FAIL(c, LIG_E_ARG, "lig_rows_set_linear: the job has dense_rands_per_row");
+    std::vector<uint8_t> kinds(T->R);
+    for (size_t r = 0; r < T->R; r++) kinds[r] = T->rows[r].kind;
+    lig_linear* L = nullptr;
+    TRY(lig_internal_linear_create(c, sys, kinds.data(), T->R, &L));       // lig_linear_check first: nothing is launched for a system it rejects
+    if (!T->rands_full) {
+        const hipError_t e = hipMalloc((void**)&T->rands_full, (T->R ? T->R : 1) * (size_t)c->k * 32);
+        if (e != hipSuccess) { lig_internal_linear_destroy(L); FAIL(c, LIG_E_NOMEM, std::string("lig_rows_set_linear: randomness matrix: ") + hipGetErrorString(e)); }
+    }
+    lig_internal_linear_destroy(T->linear);
+    T->linear = L;
+    return LIG_OK;
+}
+
 int lig_rows_push_rands(lig_trace* T, uint64_t first_row, uint64_t n_rows, const void* host_rows) {
     return lig_rows_push_rands_sparse(T, first_row, n_rows, nullptr, host_rows);
 }
@@ -1268,6 +1305,7 @@ int lig_rows_push_rands_sparse(lig_trace* T, uint64_t first_row, uint64_t n_rows
     lig_ctx* c = T->c;
     CHECK_CTX(c);
     if (!T->from_rows || !T->committed) FAIL(c, LIG_E_STATE, "lig_rows_push_rands: lig_rows_commit has not run on this trace");
+    if (T->linear) FAIL(c, LIG_E_STATE, "lig_rows_push_rands: a linear system is set (lig_rows_set_linear): the library forms the randomness rows");
     if (first_row != T->rands_pushed || first_row + n_rows > T->R) FAIL(c, LIG_E_ARG, "lig_rows_push_rands: rows must arrive in order, without gaps, inside the trace");
     if (!n_rows) return LIG_OK;
     size_t n_present = n_rows;

@@ -358,6 +358,15 @@ struct lig_tune {
     static constexpr uint32_t DOT_GROUP = LIG_DOT_GROUP;   // rows per group of the fused coset-2 encode + dot (lig_internal_encode_dot): 64 groups x 1024 threads per chunk
 };
 
+// a sparse linear system on the device (linear.hip; lig_hip.h: lig_linear_system): create = lig_linear_check + upload + regroup by
+// slot, synchronous on the context stream; form = enqueue on `st` the rows x k randomness matrix for the stream whose round keys are
+// in rk60_dev -- the constant (32 bytes, pinned host memory) is valid once the work queued on `st` has been waited for
+struct lig_linear;
+int lig_internal_linear_create(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, lig_linear** out);
+void lig_internal_linear_destroy(lig_linear* L);
+int lig_internal_linear_form(lig_ctx* c, lig_linear* L, const uint32_t* rk60_dev, fr* rands_dev, hipStream_t st);
+const uint8_t* lig_internal_linear_const(const lig_linear* L);
+
 // the batch program of a job on the device: committed rows are written to rows_out in program order (prover.hip)
 int lig_run_batch_program(lig_ctx* c, const lig_synth_job& job, fr* rows_out);
 // witness values of the synthetic stream rows [first, rows.size()) (one draw of the witness_key stream per data slot of every

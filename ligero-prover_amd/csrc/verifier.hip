@@ -347,6 +347,9 @@ struct lig_vtrace {
     std::vector<RowDesc> rows;
     uint8_t ih[32] = {0};
     std::vector<uint8_t> proof;
+    uint8_t seed1[32] = {0};            // the stage-1 seed re-derived by lig_rows_verify_begin
+    lig_linear* linear = nullptr;       // lig_rows_verify_set_linear
+    ~lig_vtrace() { lig_internal_linear_destroy(linear); }
 };
 
 extern "C" {
@@ -387,14 +390,56 @@ int lig_rows_verify_begin(lig_ctx* c, const lig_rows_job* job, const uint8_t* pr
     V->proof.assign(proof, proof + proof_len);
     const int rc = verify_core(c, V->rows, V->ih, VSource{}, nullptr, V->proof.data(), V->proof.size(), out, stage1_seed, true);
     if (rc != LIG_OK || !out->parsed || !out->indices_match) { delete V; return rc; }      // malformed envelope: accept = 0, no trace
+    if (stage1_seed) std::memcpy(V->seed1, stage1_seed, 32);
+    else (void)verify_core(c, V->rows, V->ih, VSource{}, nullptr, V->proof.data(), V->proof.size(), out, V->seed1, true);
     *vt = V;
     return LIG_OK;
 }
 
-int lig_rows_verify_finish(lig_vtrace* V, const void* rands, int rands_on_device, const uint8_t const_sum[32], lig_verify_info* out) {
-    if (!V || !out || !const_sum) return LIG_E_ARG;
+int lig_rows_verify_set_linear(lig_vtrace* V, const lig_linear_system* sys) {
+    if (!V) return LIG_E_ARG;
     lig_ctx* c = V->c;
     CHECK_CTX(c);
+    lig_linear* L = nullptr;
+    if (sys) {
+        std::vector<uint8_t> kinds(V->rows.size());
+        for (size_t r = 0; r < kinds.size(); r++) kinds[r] = V->rows[r].kind;
+        TRY(lig_internal_linear_create(c, sys, kinds.data(), kinds.size(), &L));      // lig_linear_check first
+    }
+    lig_internal_linear_destroy(V->linear);
+    V->linear = L;
+    return LIG_OK;
+}
+
+// with a linear system: the randomness matrix and the constant are formed from the public structure and the re-derived stage-1 seed
+static int verify_finish_linear(lig_vtrace* V, const uint8_t* const_sum, lig_verify_info* out) {
+    lig_ctx* c = V->c;
+    const size_t R = V->rows.size();
+    fr* rands = nullptr;
+    HIP_TRY(c, hipMalloc((void**)&rands, (R ? R : 1) * (size_t)c->k * 32));
+    struct Free { fr* p; lig_ctx* c; ~Free() { (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->stream2); (void)hipFree(p); } } guard{rands, c};
+    uint32_t rk[60];
+    lig::aes256_expand_host(V->seed1, rk);
+    TRY(lig_internal_upload_small(c, c->rk_dev, rk, sizeof rk, c->stream));
+    TRY(lig_internal_linear_form(c, V->linear, c->rk_dev, rands, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint8_t cs[32];
+    std::memcpy(cs, const_sum ? const_sum : lig_internal_linear_const(V->linear), 32);
+    VSource src;
+    src.rand_dev = rands;
+    return verify_core(c, V->rows, V->ih, src, cs, V->proof.data(), V->proof.size(), out, nullptr, false);
+}
+
+int lig_rows_verify_finish(lig_vtrace* V, const void* rands, int rands_on_device, const uint8_t const_sum[32], lig_verify_info* out) {
+    if (!V || !out || (!const_sum && !V->linear)) return LIG_E_ARG;
+    lig_ctx* c = V->c;
+    CHECK_CTX(c);
+    if (V->linear) {
+        if (rands) FAIL(c, LIG_E_ARG, "lig_rows_verify_finish: randomness rows given while a linear system is set (lig_rows_verify_set_linear)");
+        const int rc = verify_finish_linear(V, const_sum, out);
+        delete V;
+        return rc;
+    }
     if (!V->rows.empty() && !rands) { delete V; FAIL(c, LIG_E_ARG, "lig_rows_verify_finish: null randomness rows"); }
     VSource src;
     if (rands_on_device) src.rand_dev = (const fr*)rands; else src.rand_host = (const uint8_t*)rands;
