@@ -499,6 +499,26 @@ int lig_shard_rows_restart(lig_shard *shard, const void *local_msgs, int msgs_on
 int lig_shard_rows_commit(lig_shard *shard, uint8_t root[32], uint8_t stage1_seed[32]);
 int lig_shard_rows_prove(lig_shard *shard, const void *local_rands, int rands_on_device, const uint8_t *const_sum,
                          const uint8_t **proof, size_t *proof_len, lig_proof_info *info);
+/* Sparse linear constraints on a rows shard: what lig_rows_set_linear is on one GPU.  `sys` describes the WHOLE trace (slot = global row *
+ * l + column, exactly what lig_rows_set_linear takes) and is copied before the call returns.  COLLECTIVE CONTRACT: every rank passes
+ * the same system, as every rank passes the kinds of all rows; ranks that set different systems are not detected (they produce an
+ * envelope that fails its own linear check, or differing envelopes).  A rank keeps only the terms whose row it was dealt, samples only the
+ * stream elements those terms and its slice [rank n_rhs / world, (rank + 1) n_rhs / world) of the right-hand sides need, and forms
+ * its local rows x k matrix on the device.  Any time after lig_shard_rows_begin and before lig_shard_rows_prove (before or after the
+ * commit); survives lig_shard_rows_restart; a second call replaces it; sys == NULL removes it; freed by lig_shard_destroy.
+ * With a system set, lig_shard_rows_prove(local_rands = NULL) uses the formed matrix; const_sum == NULL then means the system's
+ * constant -sum_c b_c r_c: the ranks' shares travel as one more element of the all-gather of partial accumulators (5k + 1 elements
+ * instead of 5k; a shard without a system sends what it always sent), are added in rank order and negated on every rank; it is
+ * returned in info->const_sum, identical on every rank, and info->valid_linear is a real check.  A non-NULL const_sum is used as given.
+ * LIG_E_ARG: a system lig_linear_check rejects (nothing is launched), a job with dense_rands_per_row, local_rands != NULL in
+ * lig_shard_rows_prove while a system is set.  LIG_E_STATE: a shard not made by lig_shard_rows_begin, a poisoned shard. */
+int lig_shard_rows_set_linear(lig_shard *shard, const lig_linear_system *sys);
+/* of the system set last: the terms this rank kept and the distinct stream elements it samples per proof (LIG_E_STATE: no system set) */
+int lig_shard_rows_linear_stats(const lig_shard *shard, uint64_t *local_terms, uint64_t *sampled_constraints);
+/* host only, no context: the same two numbers for `rank` of `world` from the deal of lig_shard_rows_plan -- to size a node before a
+ * GPU is touched.  LIG_E_ARG: world == 0, rank >= world, a system lig_linear_check rejects. */
+int lig_linear_shard_count(const lig_linear_system *sys, const uint8_t *kinds, uint64_t rows, uint32_t l, uint32_t rank, uint32_t world,
+                           uint64_t *local_terms, uint64_t *needed_constraints);
 
 /* sizeof of the public structs as this build of the library sees them, in the order {lig_batch_op, lig_synth_job, lig_proof_info,
  * lig_verify_info, lig_rows_job, lig_comm}: a binding in another language (ctypes, cgo, JNI) checks its own layouts against these at

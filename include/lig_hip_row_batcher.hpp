@@ -130,7 +130,8 @@ public:
     // randomness rows of those.  Call before commit(); `comm` from lig_rccl_comm_create (or lig_ipc_comm_create) must outlive
     // the batcher.  Every rank's prove() returns the same envelope as an unsharded batcher would.
     void shard_over(uint32_t rank, uint32_t world, const lig_comm* comm) {
-        if (pass_ != 1 || !comm || !world || rank >= world || linear_.is_set()) throw std::invalid_argument("hip_row_batcher::shard_over");
+        if (pass_ != 1 || !comm || !world || rank >= world) throw std::invalid_argument("hip_row_batcher::shard_over");
+        if (shard_) { lig_shard_destroy(shard_); shard_ = nullptr; linear_on_trace_ = false; }      // another deal: nothing of the old shard is reused
         sharded_ = true; rank_ = rank; world_ = world; comm_ = *comm;
     }
 
@@ -138,10 +139,10 @@ public:
     // forms the linear-test randomness rows and the public constant on the GPU.  Pass 2 -- the second run of the guest -- is no
     // longer needed: prove() may follow commit() directly (callbacks of a pass 2 that is replayed all the same are only counted),
     // and prove(nullptr) takes the system's own constant.  Any time before prove(); copied; kept across reset() for the next proof
-    // of the same program, where the structure stays resident on the device.  Not with shard_over().
+    // of the same program, where the structure stays resident on the device.  With shard_over() (before or after it): the system
+    // describes the WHOLE trace and every rank sets the same one (lig_shard_rows_set_linear); each rank forms the rows of its own chunks.
     void set_linear_system(const lig_linear_system& sys) {
         if (pass_ == 3) throw std::logic_error("hip_row_batcher::set_linear_system after prove (reset() first)");
-        if (sharded_) throw std::invalid_argument("hip_row_batcher::set_linear_system: not available on a sharded trace");
         if (pass_ == 2 && pushed_) throw std::logic_error("hip_row_batcher::set_linear_system: randomness rows have already been handed over");
         linear_.assign(sys);
         linear_on_trace_ = false;
@@ -161,6 +162,7 @@ public:
     uint64_t* next_slot() {
         if (pass_ == 1) { rows_.reserve(kinds_.size() + 1, kinds_.size()); return rows_.row(kinds_.size()); }
         if (pass_ != 2 || next_ >= kinds_.size()) throw std::logic_error("hip_row_batcher::next_slot: no row expected");
+        if (sharded_ && linear_.is_set()) return rands_.row(0);  // the library forms the randomness rows: what is exported here is never read
         if (!sharded_) return rands_.row(n_present_);            // randomness rows are kept packed: only rows that have one take a slot
         const size_t slot = local_of_[next_];
         return slot == (size_t)-1 ? nullptr : rands_.row(slot);
@@ -249,11 +251,11 @@ public:
     // (owned by the batcher, valid until it is destroyed or reset); `info` (optional) receives the prover's self-check.
     const uint8_t* prove(const uint8_t const_sum[32], size_t* proof_len, lig_proof_info* info = nullptr) {
         if (pass_ != 2) throw std::logic_error("hip_row_batcher::prove before commit");
-        const bool linear = linear_.is_set() && !sharded_;
+        const bool linear = linear_.is_set();
         if (!linear && next_ != kinds_.size()) throw std::logic_error("hip_row_batcher::prove: pass 2 replayed " + std::to_string(next_) + " of " + std::to_string(kinds_.size()) + " rows");
         const uint8_t* proof = nullptr;
         lig_proof_info local;
-        if (sharded_) check(lig_shard_rows_prove(shard_, rands_.data(), 0, const_sum, &proof, proof_len, info ? info : &local), "lig_shard_rows_prove");
+        if (sharded_) check(lig_shard_rows_prove(shard_, linear ? nullptr : rands_.data(), 0, const_sum, &proof, proof_len, info ? info : &local), "lig_shard_rows_prove");
         else {
             if (!linear) push_rands(kinds_.size());        // the tail; everything else went out while the guest was running
             check(lig_rows_prove(trace_, nullptr, 0, const_sum, &proof, proof_len, info ? info : &local), "lig_rows_prove");
@@ -292,8 +294,9 @@ private:
     // randomness row are in the staging (packed) and go over the link; the library zero-fills the others on the device
     // (lig_rows_push_rands_sparse) -- batch rows never have one, quadratic rows often do not.
     void apply_linear() {
-        if (!linear_.is_set() || linear_on_trace_ || !trace_) return;
-        check(lig_rows_set_linear(trace_, linear_.get()), "lig_rows_set_linear");
+        if (!linear_.is_set() || linear_on_trace_ || !(sharded_ ? (bool)shard_ : (bool)trace_)) return;
+        if (sharded_) check(lig_shard_rows_set_linear(shard_, linear_.get()), "lig_shard_rows_set_linear");
+        else check(lig_rows_set_linear(trace_, linear_.get()), "lig_rows_set_linear");
         linear_on_trace_ = true;
     }
     void push_rands(size_t upto) {
@@ -329,12 +332,18 @@ private:
             }
         job.msgs = n_local_ ? rows_.data() : nullptr;
         shipped_ = job.elem_bytes ? (size_t)(out - reinterpret_cast<uint8_t*>(rows_.row(0))) : n_local_ * words * 8;
-        if (shard_) { lig_shard_destroy(shard_); shard_ = nullptr; }
-        check(lig_shard_rows_begin(ctx_, &job, rank_, world_, &comm_, &shard_), "lig_shard_rows_begin");
+        if (shard_) {                                      // the next proof of the same program: the shard's buffers and its share of the system are reused
+            if (same_shape(job)) check(lig_shard_rows_restart(shard_, job.msgs, 0), "lig_shard_rows_restart");
+            else { lig_shard_destroy(shard_); shard_ = nullptr; linear_on_trace_ = false; }
+        }
+        if (!shard_) check(lig_shard_rows_begin(ctx_, &job, rank_, world_, &comm_, &shard_), "lig_shard_rows_begin");
+        shape_kinds_ = kinds_; shape_widths_ = job.elem_bytes ? widths : std::vector<uint8_t>(); shape_meta_ = meta_;
+        apply_linear();                                   // this rank's share of the system, under the commit
         check(lig_shard_rows_commit(shard_, root, stage1_seed), "lig_shard_rows_commit");
         for (auto& kd : kinds_) kd &= 0x7f;               // (pass 2 compares plain kinds)
-        begin_pass2(n_local_);
-        std::memset(rands_.row(0), 0, (n_local_ ? n_local_ : 1) * words * 8);       // batch rows and rows without a callback keep zero rows
+        const size_t rand_rows = linear_.is_set() ? 0 : n_local_;      // with a system no randomness row is staged (one scratch row for next_slot)
+        begin_pass2(rand_rows);
+        std::memset(rands_.row(0), 0, (rand_rows ? rand_rows : 1) * words * 8);     // batch rows and rows without a callback keep zero rows
     }
     // the width row r of the staging is shipped in: 32 for batch rows and rows whose data slots need more than 8 bytes; else 8,
     // or with `narrowest` the smallest of bits / 1 / 2 / 4 / 8 bytes that holds every data slot (the OR of the slots decides)

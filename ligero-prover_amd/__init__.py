@@ -39,6 +39,7 @@ EXPORTS = [
     "lig_abi_sizes", "lig_shard_rows_plan", "lig_shard_rows_begin", "lig_shard_rows_restart", "lig_shard_rows_commit", "lig_shard_rows_prove",
     "lig_upload_health", "lig_profile_read_launches",
     "lig_linear_check", "lig_linear_form", "lig_rows_set_linear", "lig_rows_verify_set_linear",
+    "lig_shard_rows_set_linear", "lig_shard_rows_linear_stats", "lig_linear_shard_count",
 ]
 
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
@@ -138,6 +139,18 @@ def linear_check(system, kinds, l):
     """lig_linear_check (host only) -> the return code: 0, or LIG_E_ARG (-1) for a system that breaks a rule of the format"""
     kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
     return load_library().lig_linear_check(C.byref(system), kinds.ctypes.data if len(kinds) else None, len(kinds), l)
+
+
+def linear_shard_count(system, kinds, l, rank, world):
+    """lig_linear_shard_count (host only) -> (local_terms, needed_constraints): the terms of `system` that `rank` of `world` keeps under
+    the deal of shard_rows_plan, and the distinct stream elements it samples per proof; LigError(-1) for rank >= world, world == 0 or a
+    system lig_linear_check rejects"""
+    kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+    lt, nc = C.c_uint64(), C.c_uint64()
+    rc = load_library().lig_linear_shard_count(C.byref(system), kinds.ctypes.data if len(kinds) else None, len(kinds), l, rank, world, C.byref(lt), C.byref(nc))
+    if rc != 0:
+        raise LigError("lig_linear_shard_count failed (%d)" % rc)
+    return int(lt.value), int(nc.value)
 
 
 class ProofInfo(C.Structure):
@@ -275,6 +288,9 @@ def load_library():
     L.lig_linear_form.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, vp]
     L.lig_rows_set_linear.argtypes = [vp, C.POINTER(LinearSystem)]
     L.lig_rows_verify_set_linear.argtypes = [vp, C.POINTER(LinearSystem)]
+    L.lig_shard_rows_set_linear.argtypes = [vp, C.POINTER(LinearSystem)]
+    L.lig_shard_rows_linear_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.lig_linear_shard_count.argtypes = [C.POINTER(LinearSystem), vp, u64, u32, u32, u32, C.POINTER(u64), C.POINTER(u64)]
     return L
 
 
@@ -657,7 +673,19 @@ class Context:
         self.check(self.L.lig_shard_rows_commit(shard, _hptr(root), _hptr(seed)))
         return root.tobytes(), seed.tobytes()
 
-    def shard_rows_prove(self, shard, local_rands, const_sum, on_device=False):
+    def shard_rows_set_linear(self, shard, system):
+        """lig_shard_rows_set_linear: `system` describes the WHOLE trace and is the same on every rank; shard_rows_prove(shard, None, None)
+        then forms this rank's randomness rows and the constant itself; None removes it"""
+        self.check(self.L.lig_shard_rows_set_linear(shard, C.byref(system) if system is not None else None))
+
+    def shard_rows_linear_stats(self, shard):
+        """-> (local_terms, sampled_constraints) of the system set last on this rank"""
+        lt, sc = C.c_uint64(), C.c_uint64()
+        self.check(self.L.lig_shard_rows_linear_stats(shard, C.byref(lt), C.byref(sc)))
+        return int(lt.value), int(sc.value)
+
+    def shard_rows_prove(self, shard, local_rands=None, const_sum=None, on_device=False):
+        """local_rands = None: the rows come from dense_rands_per_row or from the system of shard_rows_set_linear"""
         proof, ln, info = C.POINTER(C.c_uint8)(), C.c_size_t(), ProofInfo()
         cs = np.frombuffer(bytes(const_sum), dtype=np.uint8).copy() if const_sum is not None else None
         if local_rands is None:

@@ -148,6 +148,17 @@ __global__ void __launch_bounds__(256) k_rng_fill(const uint32_t* __restrict__ r
         fr_store(out + e, aes_field_elem<LOGR, LAYOUT>(rk, tl, first_elem + e));
 }
 
+// Indexed fill: out[e] = stream element first_elem + idx[e] -- a rank of a sharded trace samples only the constraints its rows need
+// (linear.hip); same table staging and launch shapes as k_rng_fill, one 4-byte index load per element on top.
+template <int LOGR, int LAYOUT = 0>
+__global__ void __launch_bounds__(256) k_rng_fill_indexed(const uint32_t* __restrict__ rk, uint64_t first_elem, const uint32_t* __restrict__ idx,
+                                                          fr* __restrict__ out, size_t count) {
+    __shared__ uint32_t te[1024 << LOGR];
+    const TeView tl = te_stage<LOGR, LAYOUT>(te);
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (size_t)gridDim.x * blockDim.x)
+        fr_store(out + e, aes_field_elem<LOGR, LAYOUT>(rk, tl, first_elem + idx[e]));
+}
+
 // Row-structured fill: out[r*row_stride + col_off + i*elem_stride] = stream element (first + r*stream_stride + i),
 // r < rows, i < per_row.  One launch forms the k-l pad columns of a whole row batch, a dense randomness row
 // batch, or the (0, r, 0, r, ...) pattern of a mask row (elem_stride = 2).
@@ -284,6 +295,13 @@ void launch_rng_fill(hipStream_t s, const uint32_t* rk60_dev, uint64_t first_ele
     if (count >= BIG_FILL && PERM_LAYOUT) hipLaunchKernelGGL((k_rng_fill<4, 1>), dim3(BIG_BLOCKS), dim3(256), 0, s, rk60_dev, first_elem, out, count);
     else if (count >= BIG_FILL) hipLaunchKernelGGL(k_rng_fill<REP>, dim3(BIG_BLOCKS), dim3(256), 0, s, rk60_dev, first_elem, out, count);
     else hipLaunchKernelGGL(k_rng_fill<0>, dim3(small_blocks(count, 4096)), dim3(256), 0, s, rk60_dev, first_elem, out, count);
+}
+
+void launch_rng_fill_indexed(hipStream_t s, const uint32_t* rk60_dev, uint64_t first_elem, const uint32_t* idx_dev, fr* out, size_t count) {
+    if (!count) return;
+    if (count >= BIG_FILL && PERM_LAYOUT) hipLaunchKernelGGL((k_rng_fill_indexed<4, 1>), dim3(BIG_BLOCKS), dim3(256), 0, s, rk60_dev, first_elem, idx_dev, out, count);
+    else if (count >= BIG_FILL) hipLaunchKernelGGL(k_rng_fill_indexed<REP>, dim3(BIG_BLOCKS), dim3(256), 0, s, rk60_dev, first_elem, idx_dev, out, count);
+    else hipLaunchKernelGGL(k_rng_fill_indexed<0>, dim3(small_blocks(count, 4096)), dim3(256), 0, s, rk60_dev, first_elem, idx_dev, out, count);
 }
 
 }  // namespace lig

@@ -161,6 +161,8 @@ void launch_merkle_build(hipStream_t s, const uint32_t* leaves, size_t n_leaves,
 
 // ---- aes.hip
 void launch_rng_fill(hipStream_t s, const uint32_t* rk60_dev, uint64_t first_elem, fr* out, size_t count);
+// out[i] = stream element first_elem + idx_dev[i], i < count (the stream is seekable per element)
+void launch_rng_fill_indexed(hipStream_t s, const uint32_t* rk60_dev, uint64_t first_elem, const uint32_t* idx_dev, fr* out, size_t count);
 void aes256_expand_host(const uint8_t key[32], uint32_t rk[60]);
 
 }  // namespace lig

@@ -21,7 +21,9 @@
 //     rows no term touches are cleared with a memset.
 // Field arithmetic: canonical 8 x u32 (fr.hpp).  A term costs one 256-bit modular add (~50 VALU instructions) against a random
 // 32-byte gather from a vector that does not fit the last-level cache at 2^24 constraints: the pass is bound by the gather, not by
-// VALU (DESIGN.md section 2 item 12), so the 29-bit-limb forms of fr29.hpp would buy nothing here.
+// VALU (DESIGN.md section 2 item 11), so the 29-bit-limb forms of fr29.hpp would buy nothing here.
+// One rank of a sharded trace (lig_shard_rows_set_linear) keeps the terms of its own rows and samples only the
+// constraints those need: the k_lin_shard_* kernels of the prepare phase below, k_rng_fill_indexed (aes.hip) in the form phase.
 #include <cstring>
 
 #include <rocprim/device/device_scan.hpp>
@@ -64,6 +66,51 @@ __global__ void __launch_bounds__(LIN_WG) k_lin_classify(const uint32_t* __restr
         if (cnt) row_touched[s / l] = 1;
         if (cnt > HEAVY_MIN) { const uint32_t i = atomicAdd(n_heavy, 1u); if (i < heavy_cap) heavy[i] = (uint32_t)s; }
     }
+}
+
+// ---------------------------------------------------------------- prepare, one rank of a sharded trace (lig_shard_rows_set_linear)
+// The system describes the WHOLE trace; a rank keeps the terms whose row it was dealt (local_of: global row -> local row, LIN_NOT_LOCAL
+// for the rows of other ranks), renumbered to local slots, and samples only the constraints it NEEDS: those with a kept term and those
+// of its slice of the right-hand sides.  flag[c] = 1 marks them (plain stores of the same value from any number of lanes), an exclusive
+// scan of the flags numbers them in ascending order, and the per-slot entries carry those compact numbers: r is need-list long.
+static constexpr uint32_t LIN_NOT_LOCAL = 0xFFFFFFFFu;
+static __device__ __forceinline__ uint32_t lin_local_slot(uint32_t slot, uint32_t l, const uint32_t* __restrict__ local_of) {
+    const uint32_t row = slot / l, lr = local_of[row];
+    return lr == LIN_NOT_LOCAL ? LIN_NOT_LOCAL : lr * l + (slot - row * l);
+}
+__global__ void __launch_bounds__(LIN_WG) k_lin_shard_count(const lig_lin_term* __restrict__ terms, uint32_t n_terms, const uint32_t* __restrict__ term_begin,
+                                                            uint32_t n_constraints, uint32_t l, const uint32_t* __restrict__ local_of,
+                                                            uint32_t* __restrict__ count, uint32_t* __restrict__ flag) {
+    for (uint64_t t = blockIdx.x * LIN_WG + threadIdx.x; t < n_terms; t += gridDim.x * LIN_WG) {
+        const uint32_t ls = lin_local_slot(terms[t].slot, l, local_of);
+        if (ls == LIN_NOT_LOCAL) continue;
+        atomicAdd(count + ls, 1u);
+        flag[lin_constraint_of(term_begin, n_constraints, (uint32_t)t)] = 1u;
+    }
+}
+// the rank's slice [lo, hi) of the right-hand sides
+__global__ void __launch_bounds__(LIN_WG) k_lin_shard_mark_rhs(const uint32_t* __restrict__ rhs_c, uint32_t n, uint32_t* __restrict__ flag) {
+    for (uint64_t i = blockIdx.x * LIN_WG + threadIdx.x; i < n; i += gridDim.x * LIN_WG) flag[rhs_c[i]] = 1u;
+}
+__global__ void __launch_bounds__(LIN_WG) k_lin_shard_scatter(const lig_lin_term* __restrict__ terms, uint32_t n_terms, const uint32_t* __restrict__ term_begin,
+                                                              uint32_t n_constraints, uint32_t l, const uint32_t* __restrict__ local_of,
+                                                              const uint32_t* __restrict__ compact, const uint32_t* __restrict__ begin,
+                                                              uint32_t* __restrict__ cursor, uint2* __restrict__ ent) {
+    for (uint64_t t = blockIdx.x * LIN_WG + threadIdx.x; t < n_terms; t += gridDim.x * LIN_WG) {
+        const lig_lin_term tm = terms[t];
+        const uint32_t ls = lin_local_slot(tm.slot, l, local_of);
+        if (ls == LIN_NOT_LOCAL) continue;
+        const uint32_t pos = begin[ls] + atomicAdd(cursor + ls, 1u);
+        ent[pos] = make_uint2(compact[lin_constraint_of(term_begin, n_constraints, (uint32_t)t)], tm.coef);
+    }
+}
+// need[compact[c]] = c for the marked constraints: ascending, every entry written exactly once
+__global__ void __launch_bounds__(LIN_WG) k_lin_shard_need(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ compact, uint32_t n_constraints,
+                                                           uint32_t* __restrict__ need) {
+    for (uint64_t c = blockIdx.x * LIN_WG + threadIdx.x; c < n_constraints; c += gridDim.x * LIN_WG) if (flag[c]) need[compact[c]] = (uint32_t)c;
+}
+__global__ void __launch_bounds__(LIN_WG) k_lin_shard_rhs(uint32_t* __restrict__ rhs_c, uint32_t n, const uint32_t* __restrict__ compact) {
+    for (uint64_t i = blockIdx.x * LIN_WG + threadIdx.x; i < n; i += gridDim.x * LIN_WG) rhs_c[i] = compact[rhs_c[i]];
 }
 
 // ---------------------------------------------------------------- form
@@ -131,13 +178,15 @@ __global__ void __launch_bounds__(LIN_WG) k_lin_const_part(const uint32_t* __res
     acc = lin_block_sum(acc, sh);
     if (threadIdx.x == 0) fr_store(part + blockIdx.x, acc);
 }
-// one workgroup: out = - sum of the n_part partial sums
+// one workgroup: out = - sum of the n_part partial sums; NEGATE = false (one rank of a sharded trace): the sum itself -- the ranks' sums
+// are added in rank order and negated after the all-gather (shard.hip)
+template <bool NEGATE>
 __global__ void __launch_bounds__(LIN_WG) k_lin_const_fin(const fr* __restrict__ part, uint32_t n_part, fr* __restrict__ out) {
     __shared__ fr sh[LIN_WG];
     fr acc = fr_zero();
     for (uint32_t i = threadIdx.x; i < n_part; i += LIN_WG) acc = fr_add(acc, fr_load(part + i));
     acc = lin_block_sum(acc, sh);
-    if (threadIdx.x == 0) fr_store(out, fr_neg(acc));
+    if (threadIdx.x == 0) fr_store(out, NEGATE ? fr_neg(acc) : acc);
 }
 }  // namespace lig
 
@@ -153,7 +202,12 @@ struct lig_linear {
     uint32_t* rhs_c = nullptr; uint32_t* rhs_coef = nullptr;
     uint32_t* heavy = nullptr;          // slots with more than HEAVY_MIN terms, ascending
     uint32_t* trows = nullptr;          // rows with at least one term, ascending
-    fr* r = nullptr;                    // n_constraints stream elements (per proof)
+    fr* r = nullptr;                    // n_constraints stream elements (per proof); one rank of a sharded trace: n_need
+    // one rank of a sharded trace (lig_internal_linear_create_shard): rows / n_slots / trows / zero_runs are LOCAL, n_terms = the terms kept,
+    // n_rhs = the rank's slice of the right-hand sides, ent[].x and rhs_c[] index r through the need list
+    bool sharded = false;
+    uint32_t* need = nullptr;           // n_need constraint numbers, ascending: r[i] = stream element first_random + need[i]
+    uint64_t n_need = 0;
     fr* part = nullptr;                 // n_heavy x HEAVY_PARTS | CONST_BLOCKS | the constant
     uint8_t* h_const = nullptr;         // pinned, 32 bytes: the constant of the last form
     std::vector<std::pair<uint64_t, uint64_t>> zero_runs;      // (first row, rows) no term touches
@@ -189,13 +243,45 @@ void lig_internal_linear_destroy(lig_linear* L) {
     if (!L) return;
     (void)hipSetDevice(L->c->device);
     for (hipStream_t st : {L->c->stream, L->c->stream2}) if (st) (void)hipStreamSynchronize(st);
-    for (void* p : {(void*)L->begin, (void*)L->ent, (void*)L->coef_mont, (void*)L->rhs_c, (void*)L->rhs_coef, (void*)L->heavy, (void*)L->trows, (void*)L->r, (void*)L->part})
+    for (void* p : {(void*)L->begin, (void*)L->ent, (void*)L->coef_mont, (void*)L->rhs_c, (void*)L->rhs_coef, (void*)L->heavy, (void*)L->trows, (void*)L->r, (void*)L->part, (void*)L->need})
         (void)hipFree(p);
     (void)hipHostFree(L->h_const);
     delete L;
 }
 
 static uint32_t lin_grid(uint64_t items) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + lig::LIN_WG - 1) / lig::LIN_WG, 1), 65535); }
+
+// the end of both prepares: heavy slots sorted, touched rows listed, runs of untouched rows, the partial-sum scratch
+static int linear_prepare_lists(lig_ctx* c, lig_linear* L, const uint8_t* d_touched, const uint32_t* d_nheavy, uint32_t heavy_cap) {
+    hipStream_t s = c->stream;
+    auto dmalloc = [&](void** p, size_t bytes) -> int { HIP_TRY(c, hipMalloc(p, bytes ? bytes : 16)); return LIG_OK; };
+    std::vector<uint8_t> touched(L->rows);
+    uint32_t n_heavy = 0;
+    if (L->rows) HIP_TRY(c, hipMemcpyAsync(touched.data(), d_touched, L->rows, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&n_heavy, d_nheavy, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (n_heavy > heavy_cap) FAIL(c, LIG_E_STATE, "linear system: heavy-slot list overflow");      // (cannot happen: more than HEAVY_MIN terms each)
+    L->n_heavy = n_heavy;
+    if (n_heavy) {      // ascending: the same launch geometry whatever order the atomics appended them in
+        std::vector<uint32_t> hv(n_heavy);
+        HIP_TRY(c, hipMemcpy(hv.data(), L->heavy, (size_t)n_heavy * 4, hipMemcpyDeviceToHost));
+        std::sort(hv.begin(), hv.end());
+        HIP_TRY(c, hipMemcpy(L->heavy, hv.data(), (size_t)n_heavy * 4, hipMemcpyHostToDevice));
+    }
+    std::vector<uint32_t> trows;
+    for (uint64_t r = 0; r < L->rows;) {
+        if (touched[r]) { trows.push_back((uint32_t)r); r++; continue; }
+        uint64_t e = r + 1;
+        while (e < L->rows && !touched[e]) e++;
+        L->zero_runs.push_back({r, e - r});
+        r = e;
+    }
+    L->n_trows = (uint32_t)trows.size();
+    TRY(dmalloc((void**)&L->trows, trows.size() * 4));
+    if (!trows.empty()) HIP_TRY(c, hipMemcpy(L->trows, trows.data(), trows.size() * 4, hipMemcpyHostToDevice));
+    TRY(dmalloc((void**)&L->part, ((size_t)n_heavy * lig::HEAVY_PARTS + lig::CONST_BLOCKS + 1) * 32));
+    return LIG_OK;
+}
 
 static int linear_prepare(lig_ctx* c, const lig_linear_system* sys, lig_linear* L) {
     hipStream_t s = c->stream;
@@ -243,32 +329,81 @@ static int linear_prepare(lig_ctx* c, const lig_linear_system* sys, lig_linear* 
     if (NT) hipLaunchKernelGGL(lig::k_lin_scatter, dim3(lin_grid(NT)), dim3(lig::LIN_WG), 0, s, d_terms, NT, d_tb, NC, L->begin, d_cursor, L->ent);
     if (S) hipLaunchKernelGGL(lig::k_lin_classify, dim3(lin_grid(S)), dim3(lig::LIN_WG), 0, s, L->begin, S, L->l, d_touched, L->heavy, heavy_cap, d_nheavy);
     HIP_TRY(c, hipGetLastError());
-    std::vector<uint8_t> touched(L->rows);
-    uint32_t n_heavy = 0;
-    if (L->rows) HIP_TRY(c, hipMemcpyAsync(touched.data(), d_touched, L->rows, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&n_heavy, d_nheavy, 4, hipMemcpyDeviceToHost, s));
+    return linear_prepare_lists(c, L, d_touched, d_nheavy, heavy_cap);
+}
+
+// one rank of a sharded trace: local_of = global row -> local row (LIN_NOT_LOCAL: another rank's), rows_local = the rank's rows;
+// the rank's slice of the right-hand sides = entries [rhs_lo, rhs_hi)
+static int linear_prepare_shard(lig_ctx* c, const lig_linear_system* sys, lig_linear* L, const uint32_t* local_of, uint64_t rows_global, uint64_t rhs_lo,
+                                uint64_t rhs_hi) {
+    hipStream_t s = c->stream;
+    const uint32_t S = L->n_slots, NT = (uint32_t)sys->n_terms, NC = (uint32_t)L->n_constraints, NR = (uint32_t)(rhs_hi - rhs_lo);
+    auto dmalloc = [&](void** p, size_t bytes) -> int { HIP_TRY(c, hipMalloc(p, bytes ? bytes : 16)); return LIG_OK; };
+    L->n_rhs = NR;
+    TRY(dmalloc((void**)&L->begin, ((size_t)S + 1) * 4));
+    TRY(dmalloc((void**)&L->coef_mont, L->n_coefs * 32));
+    TRY(dmalloc((void**)&L->rhs_c, (size_t)NR * 4));
+    TRY(dmalloc((void**)&L->rhs_coef, (size_t)NR * 4));
+    HIP_TRY(c, hipHostMalloc((void**)&L->h_const, 32, hipHostMallocDefault));
+    std::memset(L->h_const, 0, 32);
+    const uint32_t heavy_cap = NT / (lig::HEAVY_MIN + 1) + 1;
+    TRY(dmalloc((void**)&L->heavy, (size_t)heavy_cap * 4));
+    std::vector<H::Fr> cm(L->n_coefs);         // (declared before the guard below: it outlives the guard's synchronise, an async copy reads it)
+    // scratch of this call only
+    lig_lin_term* d_terms = nullptr; uint32_t *d_tb = nullptr, *d_cursor = nullptr, *d_count = nullptr, *d_nheavy = nullptr, *d_local = nullptr, *d_flag = nullptr, *d_compact = nullptr;
+    uint8_t* d_touched = nullptr; void* d_scan = nullptr;
+    struct Scratch { std::vector<void**> v; lig_ctx* c; ~Scratch() { (void)hipStreamSynchronize(c->stream); for (void** p : v) (void)hipFree(*p); } }
+        scratch{{(void**)&d_terms, (void**)&d_tb, (void**)&d_cursor, (void**)&d_count, (void**)&d_nheavy, (void**)&d_local, (void**)&d_flag, (void**)&d_compact,
+                 (void**)&d_touched, &d_scan}, c};
+    TRY(dmalloc((void**)&d_terms, (size_t)NT * sizeof(lig_lin_term)));
+    TRY(dmalloc((void**)&d_tb, ((size_t)NC + 1) * 4));
+    TRY(dmalloc((void**)&d_cursor, (size_t)S * 4));
+    TRY(dmalloc((void**)&d_count, ((size_t)S + 1) * 4));
+    TRY(dmalloc((void**)&d_nheavy, 4));
+    TRY(dmalloc((void**)&d_local, rows_global * 4));
+    TRY(dmalloc((void**)&d_flag, ((size_t)NC + 1) * 4));
+    TRY(dmalloc((void**)&d_compact, ((size_t)NC + 1) * 4));
+    TRY(dmalloc((void**)&d_touched, L->rows));
+    for (uint64_t i = 0; i < L->n_coefs; i++) { H::Fr v; std::memcpy(v.v, sys->coefs + 32 * i, 32); cm[i] = H::to_mont(v); }
+    if (NT) HIP_TRY(c, hipMemcpyAsync(d_terms, sys->terms, (size_t)NT * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d_tb, sys->term_begin, ((size_t)NC + 1) * 4, hipMemcpyHostToDevice, s));
+    if (rows_global) HIP_TRY(c, hipMemcpyAsync(d_local, local_of, rows_global * 4, hipMemcpyHostToDevice, s));
+    if (L->n_coefs) HIP_TRY(c, hipMemcpyAsync(L->coef_mont, cm.data(), L->n_coefs * 32, hipMemcpyHostToDevice, s));
+    if (NR) {
+        HIP_TRY(c, hipMemcpyAsync(L->rhs_c, sys->rhs_constraint + rhs_lo, (size_t)NR * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(L->rhs_coef, sys->rhs_coef + rhs_lo, (size_t)NR * 4, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(c, hipMemsetAsync(d_count, 0, ((size_t)S + 1) * 4, s));
+    HIP_TRY(c, hipMemsetAsync(d_cursor, 0, (size_t)S * 4, s));
+    HIP_TRY(c, hipMemsetAsync(d_flag, 0, ((size_t)NC + 1) * 4, s));
+    HIP_TRY(c, hipMemsetAsync(d_nheavy, 0, 4, s));
+    if (L->rows) HIP_TRY(c, hipMemsetAsync(d_touched, 0, L->rows, s));
+    if (NT) hipLaunchKernelGGL(lig::k_lin_shard_count, dim3(lin_grid(NT)), dim3(lig::LIN_WG), 0, s, d_terms, NT, d_tb, NC, L->l, d_local, d_count, d_flag);
+    if (NR) hipLaunchKernelGGL(lig::k_lin_shard_mark_rhs, dim3(lin_grid(NR)), dim3(lig::LIN_WG), 0, s, L->rhs_c, NR, d_flag);
+    size_t scan_slots = 0, scan_flags = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_slots, d_count, L->begin, 0u, (size_t)S + 1, rocprim::plus<uint32_t>(), s));
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_flags, d_flag, d_compact, 0u, (size_t)NC + 1, rocprim::plus<uint32_t>(), s));
+    const size_t scan_bytes = std::max(scan_slots, scan_flags);
+    TRY(dmalloc(&d_scan, scan_bytes));
+    scan_slots = scan_flags = scan_bytes;
+    HIP_TRY(c, rocprim::exclusive_scan(d_scan, scan_slots, d_count, L->begin, 0u, (size_t)S + 1, rocprim::plus<uint32_t>(), s));
+    HIP_TRY(c, rocprim::exclusive_scan(d_scan, scan_flags, d_flag, d_compact, 0u, (size_t)NC + 1, rocprim::plus<uint32_t>(), s));
+    // how many terms were kept, how many constraints are needed: the sizes of ent / need / r
+    uint32_t kept = 0, n_need = 0;
+    HIP_TRY(c, hipMemcpyAsync(&kept, L->begin + S, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&n_need, d_compact + NC, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (n_heavy > heavy_cap) FAIL(c, LIG_E_STATE, "linear system: heavy-slot list overflow");      // (cannot happen: more than HEAVY_MIN terms each)
-    L->n_heavy = n_heavy;
-    if (n_heavy) {      // ascending: the same launch geometry whatever order the atomics appended them in
-        std::vector<uint32_t> hv(n_heavy);
-        HIP_TRY(c, hipMemcpy(hv.data(), L->heavy, (size_t)n_heavy * 4, hipMemcpyDeviceToHost));
-        std::sort(hv.begin(), hv.end());
-        HIP_TRY(c, hipMemcpy(L->heavy, hv.data(), (size_t)n_heavy * 4, hipMemcpyHostToDevice));
-    }
-    std::vector<uint32_t> trows;
-    for (uint64_t r = 0; r < L->rows;) {
-        if (touched[r]) { trows.push_back((uint32_t)r); r++; continue; }
-        uint64_t e = r + 1;
-        while (e < L->rows && !touched[e]) e++;
-        L->zero_runs.push_back({r, e - r});
-        r = e;
-    }
-    L->n_trows = (uint32_t)trows.size();
-    TRY(dmalloc((void**)&L->trows, trows.size() * 4));
-    if (!trows.empty()) HIP_TRY(c, hipMemcpy(L->trows, trows.data(), trows.size() * 4, hipMemcpyHostToDevice));
-    TRY(dmalloc((void**)&L->part, ((size_t)n_heavy * lig::HEAVY_PARTS + lig::CONST_BLOCKS + 1) * 32));
-    return LIG_OK;
+    if (kept > NT || n_need > NC) FAIL(c, LIG_E_STATE, "linear system: sharded prepare counted more than the system holds");
+    L->n_terms = kept; L->n_need = n_need;
+    TRY(dmalloc((void**)&L->ent, (size_t)kept * sizeof(uint2)));
+    TRY(dmalloc((void**)&L->need, (size_t)n_need * 4));
+    TRY(dmalloc((void**)&L->r, (size_t)n_need * 32));
+    if (NT) hipLaunchKernelGGL(lig::k_lin_shard_scatter, dim3(lin_grid(NT)), dim3(lig::LIN_WG), 0, s, d_terms, NT, d_tb, NC, L->l, d_local, d_compact, L->begin, d_cursor, L->ent);
+    if (NC) hipLaunchKernelGGL(lig::k_lin_shard_need, dim3(lin_grid(NC)), dim3(lig::LIN_WG), 0, s, d_flag, d_compact, NC, L->need);
+    if (NR) hipLaunchKernelGGL(lig::k_lin_shard_rhs, dim3(lin_grid(NR)), dim3(lig::LIN_WG), 0, s, L->rhs_c, NR, d_compact);
+    if (S) hipLaunchKernelGGL(lig::k_lin_classify, dim3(lin_grid(S)), dim3(lig::LIN_WG), 0, s, L->begin, S, L->l, d_touched, L->heavy, heavy_cap, d_nheavy);
+    HIP_TRY(c, hipGetLastError());
+    return linear_prepare_lists(c, L, d_touched, d_nheavy, heavy_cap);
 }
 
 // check, upload, regroup by slot; synchronous (every pointer of *sys may be released when it returns)
@@ -285,12 +420,61 @@ int lig_internal_linear_create(lig_ctx* c, const lig_linear_system* sys, const u
     return LIG_OK;
 }
 
+// this rank's share of a deal: which rows are local, its slice of the right-hand sides.  grow = the global row of every local row.
+static void linear_shard_share(const lig_linear_system* sys, const std::vector<size_t>& grow, uint64_t rows, uint32_t rank, uint32_t world,
+                               std::vector<uint32_t>& local_of, uint64_t& rhs_lo, uint64_t& rhs_hi) {
+    local_of.assign(rows, lig::LIN_NOT_LOCAL);
+    for (size_t lr = 0; lr < grow.size(); lr++) local_of[grow[lr]] = (uint32_t)lr;
+    rhs_lo = (uint64_t)((unsigned __int128)rank * sys->n_rhs / world);
+    rhs_hi = (uint64_t)((unsigned __int128)(rank + 1) * sys->n_rhs / world);
+}
+// the two numbers of lig_shard_rows_linear_stats on the host (lig_linear_shard_count); sys has passed lig_linear_check
+void lig_internal_linear_shard_count(const lig_linear_system* sys, uint32_t l, const std::vector<size_t>& grow, uint64_t rows, uint32_t rank, uint32_t world,
+                                     uint64_t* local_terms, uint64_t* needed) {
+    std::vector<uint32_t> local_of;
+    uint64_t lo, hi;
+    linear_shard_share(sys, grow, rows, rank, world, local_of, lo, hi);
+    uint64_t kept = 0, need = 0, i = lo;
+    for (uint64_t cn = 0; cn < sys->n_constraints; cn++) {
+        uint64_t mine = 0;
+        for (uint32_t t = sys->term_begin[cn]; t < sys->term_begin[cn + 1]; t++) mine += local_of[sys->terms[t].slot / l] != lig::LIN_NOT_LOCAL;
+        while (i < hi && sys->rhs_constraint[i] < cn) i++;
+        kept += mine;
+        need += mine || (i < hi && sys->rhs_constraint[i] == cn);
+    }
+    *local_terms = kept; *needed = need;
+}
+// one rank of a sharded trace (lig_shard_rows_set_linear): kinds / rows describe the WHOLE trace (lig_linear_check runs on it), grow is the
+// global row of every row dealt to this rank; the structure that comes out addresses the rank's local rows x k matrix
+int lig_internal_linear_create_shard(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, const std::vector<size_t>& grow, uint32_t rank,
+                                     uint32_t world, lig_linear** out) {
+    *out = nullptr;
+    if (lig_linear_check(sys, kinds, rows, c->l) != LIG_OK) FAIL(c, LIG_E_ARG, "linear system: rejected by lig_linear_check");
+    std::vector<uint32_t> local_of;
+    uint64_t lo, hi;
+    linear_shard_share(sys, grow, rows, rank, world, local_of, lo, hi);
+    lig_linear* L = new lig_linear();
+    L->c = c; L->l = c->l; L->k = c->k; L->rows = grow.size(); L->sharded = true;
+    L->n_constraints = sys->n_constraints; L->n_coefs = sys->n_coefs; L->first_random = sys->first_random;
+    L->n_slots = (uint32_t)(grow.size() * c->l);
+    const int rc = linear_prepare_shard(c, sys, L, local_of.data(), rows, lo, hi);
+    if (rc != LIG_OK) { const std::string why = c->err; lig_internal_linear_destroy(L); c->err = why; return rc; }
+    *out = L;
+    return LIG_OK;
+}
+void lig_internal_linear_stats(const lig_linear* L, uint64_t* local_terms, uint64_t* sampled) { *local_terms = L->n_terms; *sampled = L->sharded ? L->n_need : L->n_constraints; }
+// one rank of a sharded trace: the rank's sum of b_c r_c (NOT negated), one element of device memory, final once the form queued on its stream is
+const fr* lig_internal_linear_partial_dev(const lig_linear* L) { return L->part + (size_t)L->n_heavy * lig::HEAVY_PARTS + lig::CONST_BLOCKS; }
+uint8_t* lig_internal_linear_const_buf(lig_linear* L) { return L->h_const; }
+
 // enqueue on `st`: rands_dev (rows x k) <- the randomness matrix of the system for the stream whose round keys are in rk60_dev;
-// the constant lands in lig_internal_linear_const() once the work queued on `st` has been waited for
+// the constant lands in lig_internal_linear_const() once the work queued on `st` has been waited for.  One rank of a sharded trace: the
+// LOCAL rows x k matrix from the need-list long r (indexed sampler), and the rank's un-negated sum in lig_internal_linear_partial_dev()
 int lig_internal_linear_form(lig_ctx* c, lig_linear* L, const uint32_t* rk60_dev, fr* rands_dev, hipStream_t st) {
     const size_t row_bytes = (size_t)L->k * 32;
     for (const auto& z : L->zero_runs) HIP_TRY(c, hipMemsetAsync(rands_dev + z.first * L->k, 0, z.second * row_bytes, st));
-    lig::launch_rng_fill(st, rk60_dev, L->first_random, L->r, L->n_constraints);
+    if (L->sharded) lig::launch_rng_fill_indexed(st, rk60_dev, L->first_random, L->need, L->r, L->n_need);
+    else lig::launch_rng_fill(st, rk60_dev, L->first_random, L->r, L->n_constraints);
     fr* hpart = L->part; fr* cpart = L->part + (size_t)L->n_heavy * lig::HEAVY_PARTS; fr* cst = cpart + lig::CONST_BLOCKS;
     if (L->n_trows) {
         const dim3 grid((L->k + lig::LIN_WG - 1) / lig::LIN_WG, std::min<uint32_t>(L->n_trows, 65535));
@@ -302,7 +486,12 @@ int lig_internal_linear_form(lig_ctx* c, lig_linear* L, const uint32_t* rk60_dev
     }
     const uint32_t cb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((L->n_rhs + lig::LIN_WG - 1) / lig::LIN_WG, 1), lig::CONST_BLOCKS);
     hipLaunchKernelGGL(lig::k_lin_const_part, dim3(cb), dim3(lig::LIN_WG), 0, st, L->rhs_c, L->rhs_coef, (uint32_t)L->n_rhs, L->r, L->coef_mont, cpart);
-    hipLaunchKernelGGL(lig::k_lin_const_fin, dim3(1), dim3(lig::LIN_WG), 0, st, cpart, cb, cst);
+    if (L->sharded) {
+        hipLaunchKernelGGL(lig::k_lin_const_fin<false>, dim3(1), dim3(lig::LIN_WG), 0, st, cpart, cb, cst);
+        HIP_TRY(c, hipGetLastError());
+        return LIG_OK;
+    }
+    hipLaunchKernelGGL(lig::k_lin_const_fin<true>, dim3(1), dim3(lig::LIN_WG), 0, st, cpart, cb, cst);
     HIP_TRY(c, hipGetLastError());
     return lig_internal_download(c, L->h_const, cst, 32, st);
 }

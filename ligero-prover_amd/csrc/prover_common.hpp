@@ -366,6 +366,16 @@ int lig_internal_linear_create(lig_ctx* c, const lig_linear_system* sys, const u
 void lig_internal_linear_destroy(lig_linear* L);
 int lig_internal_linear_form(lig_ctx* c, lig_linear* L, const uint32_t* rk60_dev, fr* rands_dev, hipStream_t st);
 const uint8_t* lig_internal_linear_const(const lig_linear* L);
+// one rank of a sharded trace (lig_shard_rows_set_linear): the system describes the whole trace, `grow` = the global row of every local row.
+// The rank keeps the terms of its rows, samples the constraints it needs (stats), forms its local rows x k matrix and its un-negated
+// share of sum_c b_c r_c (partial_dev, one device element); const_buf = 32 pinned bytes the shard downloads the summed shares into.
+int lig_internal_linear_create_shard(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, const std::vector<size_t>& grow, uint32_t rank,
+                                     uint32_t world, lig_linear** out);
+void lig_internal_linear_shard_count(const lig_linear_system* sys, uint32_t l, const std::vector<size_t>& grow, uint64_t rows, uint32_t rank, uint32_t world,
+                                     uint64_t* local_terms, uint64_t* needed);
+void lig_internal_linear_stats(const lig_linear* L, uint64_t* local_terms, uint64_t* sampled);
+const fr* lig_internal_linear_partial_dev(const lig_linear* L);
+uint8_t* lig_internal_linear_const_buf(lig_linear* L);
 
 // the batch program of a job on the device: committed rows are written to rows_out in program order (prover.hip)
 int lig_run_batch_program(lig_ctx* c, const lig_synth_job& job, fr* rows_out);

@@ -68,6 +68,10 @@ struct lig_shard {
     bool narrow = false;
     std::vector<uint64_t> src_off;
     uint64_t* src_off_dev = nullptr; uint8_t* widths_dev = nullptr; uint8_t* packed_dev = nullptr;
+    // sparse linear system (lig_shard_rows_set_linear): this rank's share of it, regrouped by local slot (linear.hip), and the local rows x k
+    // randomness matrix it is formed into per proof; both survive lig_shard_rows_restart
+    lig_linear* linear = nullptr;
+    fr* rands_lin = nullptr;
     bool used_comm = false;                    // a collective has been issued with buffers of this shard as send buffers
     bool exchange_even_alone = false;          // LIG_SHARD_FORCE_EXCHANGE: run pack + all-to-all with world == 1 too (tests)
     size_t chunk_rows(size_t g) const { return g < G ? gb[g + 1] - gb[g] : 0; }
@@ -256,8 +260,8 @@ static int shard_alloc(lig_ctx* c, uint32_t rank, uint32_t world, lig_shard* S) 
     TRY(dm((void**)&S->rhalf, chunk * 2 * (size_t)k * 32));
     TRY(dm((void**)&S->acc, 4 * (size_t)n * 32));
     TRY(dm((void**)&S->parts, (2 * ((chunk + lig_tune::GROUP / 4 - 1) / (lig_tune::GROUP / 4)) + (chunk + lig_tune::DOT_GROUP - 1) / lig_tune::DOT_GROUP) * (size_t)k * 32));
-    TRY(dm((void**)&S->accp, 5 * (size_t)k * 32));
-    TRY(dm((void**)&S->accg, (size_t)world * 5 * k * 32));
+    TRY(dm((void**)&S->accp, (5 * (size_t)k + 1) * 32));               // (+ 1: a rank's share of the linear system's constant, when one is set)
+    TRY(dm((void**)&S->accg, (size_t)world * (5 * (size_t)k + 1) * 32));
     TRY(dm((void**)&S->dots, 32));
     TRY(dm((void**)&S->smp, (RM + 3) * (size_t)t * 32));
     TRY(dm((void**)&S->smpg, (size_t)world * RM * t * 32));
@@ -322,6 +326,8 @@ void lig_shard_destroy(lig_shard* S) {
         return;
     }
     if (S->up_flag) (void)hipHostFree((void*)S->up_flag);
+    lig_internal_linear_destroy(S->linear);
+    (void)hipFree(S->rands_lin);
     // the send buffers below are about to be freed.  forget() may be a host collective (comm_ipc): a shard that fails before its
     // first collective (a local error in *_begin / *_prepare) has exported nothing and must not wait for peers that are not there
     if (S->comm.forget && S->used_comm) S->comm.forget(S->comm.user);
@@ -383,7 +389,8 @@ static int shard_bounded_wait(lig_shard* S, const std::function<hipError_t()>& q
 }
 
 // where the stage-2 randomness rows of the LOCAL rows come from: generated (dense rows of the synthetic stream) or the caller's
-struct ShardRands { const fr* dev = nullptr; const uint8_t* host = nullptr; };
+struct ShardRands { const fr* dev = nullptr; const uint8_t* host = nullptr;
+                    lig_linear* linear = nullptr; };      // linear: `dev` (= S->rands_lin) is formed from the rank's share of the sparse linear system on the side stream
 #define SHARD_COMMON \
     lig_ctx* c = S->c; \
     const uint32_t l = c->l, k = c->k, n = c->n, t = 192, pad = k - l, W = S->world; \
@@ -618,6 +625,12 @@ static int shard_stage23(lig_shard* S, const ShardRands& rs, const uint8_t* cons
         HIP_TRY(c, hipEventRecord(S->ev_enc[cidx & 1], s_hash));
         return LIG_OK;
     };
+    // sparse linear system: the rank's local randomness matrix is formed on the side stream (the constraints its rows need are sampled
+    // through the need list, one pass in slot order: linear.hip); the row loop below then finds it where device rows of the caller would be
+    if (rs.linear) {
+        TRY(lig_internal_linear_form(c, rs.linear, c->rk_dev, const_cast<fr*>(rs.dev), s_hash));
+        HIP_TRY(c, hipEventRecord(c->ev_fork, s_hash));       // (its wait above is queued: the event is free) -- the main stream waits for it before it reads the rank's share
+    }
     if (S->rounds) TRY(form_rand_chunk(0));
     for (size_t cidx = 0; cidx < S->rounds; cidx++) {
         const size_t lb = S->lrow0[cidx], nb = S->lrow0[cidx + 1] - lb;
@@ -644,19 +657,26 @@ static int shard_stage23(lig_shard* S, const ShardRands& rs, const uint8_t* cons
     const lig::CwView view{S->msgs, S->cw, k};
     lig::launch_quad_rows29_view(s, view, 2 * k, S->tri_dev, S->coef_dev + Rl, S->coef_dev + Rl + NTl, NTl, quad, S->parts, 2 * (size_t)pg * k);
     // partial sums [code (k message values) | lin (2k) | quad (2k)] -> every rank -> added mod p (one rank: they are the sums)
+    // With a linear system the rank's share of sum_c b_c r_c travels as one more element: the W shares are added in rank order like the
+    // accumulators.  Without a system the all-gather carries exactly 5k elements.
+    const size_t acc_elems = 5 * (size_t)k + (rs.linear ? 1 : 0);
+    if (rs.linear) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_fork, 0));      // the form on the side stream has written the share
     if (W > 1 || S->exchange_even_alone) {
         HIP_TRY(c, hipMemcpyAsync(S->accp, tmp, (size_t)k * 32, hipMemcpyDeviceToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(S->accp + k, lin, 2 * (size_t)k * 32, hipMemcpyDeviceToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(S->accp + 3 * (size_t)k, quad, 2 * (size_t)k * 32, hipMemcpyDeviceToDevice, s));
-        TRY(all_gather(S->accp, S->accg, 5 * (size_t)k * 32, s, "all_gather(partial accumulators)"));
-        HIP_TRY(c, hipMemsetAsync(S->accp, 0, 5 * (size_t)k * 32, s));
-        lig::launch_rlc_combine(s, S->accp, S->accg, W, 5 * k);
+        if (rs.linear) HIP_TRY(c, hipMemcpyAsync(S->accp + 5 * (size_t)k, lig_internal_linear_partial_dev(rs.linear), 32, hipMemcpyDeviceToDevice, s));
+        TRY(all_gather(S->accp, S->accg, acc_elems * 32, s, "all_gather(partial accumulators)"));
+        HIP_TRY(c, hipMemsetAsync(S->accp, 0, acc_elems * 32, s));
+        lig::launch_rlc_combine(s, S->accp, S->accg, W, (uint32_t)acc_elems);
+        if (rs.linear) HIP_TRY(c, hipMemcpyAsync(lig_internal_linear_const_buf(rs.linear), S->accp + 5 * (size_t)k, 32, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemsetAsync(S->acc, 0, 4 * (size_t)n * 32, s));
         HIP_TRY(c, hipMemcpyAsync(tmp, S->accp, (size_t)k * 32, hipMemcpyDeviceToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(lin, S->accp + k, 2 * (size_t)k * 32, hipMemcpyDeviceToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(quad, S->accp + 3 * (size_t)k, 2 * (size_t)k * 32, hipMemcpyDeviceToDevice, s));
     } else {
         HIP_TRY(c, hipMemsetAsync(lin + 2 * (size_t)k, 0, (size_t)(n - 2 * k) * 32, s));      // linH / linC scratch behind the 2k values
+        if (rs.linear) HIP_TRY(c, hipMemcpyAsync(lig_internal_linear_const_buf(rs.linear), lig_internal_linear_partial_dev(rs.linear), 32, hipMemcpyDeviceToHost, s));   // one rank: its share is the sum
     }
     H::Fr* dots = reinterpret_cast<H::Fr*>(S->h_small);
     lig::launch_sum_elems(s, lin, k, 2, S->dots, nullptr);   // linear-test constant = -(sum of the message-domain half: the even points)
@@ -698,7 +718,12 @@ static int shard_stage23(lig_shard* S, const ShardRands& rs, const uint8_t* cons
     }
     (void)enc_bytes;
     if (const_sum_given) std::memcpy(info->const_sum, const_sum_given, 32);     // the caller's public constant (linear_sums)
-    else {
+    else if (rs.linear) {                                     // the statement's own constant: minus the ranks' shares of sum_c b_c r_c (copied before ev_acc[0])
+        H::Fr sum;
+        std::memcpy(sum.v, lig_internal_linear_const_buf(rs.linear), 32);
+        sum = H::neg(sum);
+        std::memcpy(info->const_sum, sum.v, 32);
+    } else {
         const H::Fr sum = H::neg(dots[0]);                    // (copied before ev_acc[0])
         std::memcpy(info->const_sum, sum.v, 32);
     }
@@ -980,7 +1005,8 @@ int lig_shard_rows_prove(lig_shard* S, const void* local_rands, int rands_on_dev
     CHECK_CTX(c);
     if (S->poisoned) FAIL(c, LIG_E_STATE, "lig_shard_rows_prove: the shard is poisoned (work queued behind a failed collective never drained): destroy it");
     if (!S->from_rows || !S->committed) FAIL(c, LIG_E_STATE, "lig_shard_rows_prove: lig_shard_rows_commit has not run on this shard");
-    if (S->Rl && !local_rands && !S->dense_rands) FAIL(c, LIG_E_ARG, "lig_shard_rows_prove: null randomness rows");
+    if (S->linear && local_rands) FAIL(c, LIG_E_ARG, "lig_shard_rows_prove: randomness rows given while a linear system is set (lig_shard_rows_set_linear)");
+    if (S->Rl && !local_rands && !S->dense_rands && !S->linear) FAIL(c, LIG_E_ARG, "lig_shard_rows_prove: null randomness rows");
     if (const_sum) {
         H::Fr v;
         std::memcpy(v.v, const_sum, 32);
@@ -990,6 +1016,7 @@ int lig_shard_rows_prove(lig_shard* S, const void* local_rands, int rands_on_dev
     const auto t_begin = clk::now();
     ShardRands rs;
     if (local_rands && rands_on_device) rs.dev = (const fr*)local_rands; else if (local_rands) rs.host = (const uint8_t*)local_rands;
+    else if (S->linear) { rs.dev = S->rands_lin; rs.linear = S->linear; }
     {
         const int rc = shard_stage23(S, rs, const_sum, proof, proof_len, info);
         if (rc != LIG_OK) {               // randomness-row copies the uploader thread still holds read the caller's memory: drop them, wait
@@ -1007,6 +1034,54 @@ int lig_shard_rows_prove(lig_shard* S, const void* local_rands, int rands_on_dev
     }
     info->ms_total = info->ms_stage1 + ms_since(t_begin);
     S->committed = false;
+    return LIG_OK;
+}
+
+// The sparse linear system of the WHOLE trace on a rows shard: every rank passes the same system (a collective contract, like the kinds) and
+// keeps its share -- the terms of the rows it was dealt, the constraints those need, its slice of the right-hand sides (linear.hip).
+int lig_shard_rows_set_linear(lig_shard* S, const lig_linear_system* sys) {
+    if (!S) return LIG_E_ARG;
+    lig_ctx* c = S->c;
+    CHECK_CTX(c);
+    if (S->poisoned) FAIL(c, LIG_E_STATE, "lig_shard_rows_set_linear: the shard is poisoned (work queued behind a failed collective never drained): destroy it");
+    if (!S->from_rows) FAIL(c, LIG_E_STATE, "lig_shard_rows_set_linear: not a rows shard (lig_shard_rows_begin)");
+    if (!sys) {
+        lig_internal_linear_destroy(S->linear);
+        S->linear = nullptr;
+        return LIG_OK;
+    }
+    if (S->dense_rands) FAIL(c, LIG_E_ARG, "lig_shard_rows_set_linear: the job has dense_rands_per_row");
+    std::vector<uint8_t> kinds(S->R);
+    for (size_t r = 0; r < S->R; r++) kinds[r] = S->rows[r].kind;
+    lig_linear* L = nullptr;
+    TRY(lig_internal_linear_create_shard(c, sys, kinds.data(), S->R, S->grow, S->rank, S->world, &L));      // lig_linear_check first: nothing is launched for a system it rejects
+    if (!S->rands_lin) {
+        const hipError_t e = hipMalloc((void**)&S->rands_lin, (S->Rl ? S->Rl : 1) * (size_t)c->k * 32);
+        if (e != hipSuccess) { (void)hipGetLastError(); lig_internal_linear_destroy(L); FAIL(c, LIG_E_NOMEM, std::string("lig_shard_rows_set_linear: randomness matrix: ") + hipGetErrorString(e)); }
+    }
+    lig_internal_linear_destroy(S->linear);
+    S->linear = L;
+    return LIG_OK;
+}
+int lig_shard_rows_linear_stats(const lig_shard* S, uint64_t* local_terms, uint64_t* sampled_constraints) {
+    if (!S || !local_terms || !sampled_constraints) return LIG_E_ARG;
+    if (!S->linear) return LIG_E_STATE;
+    lig_internal_linear_stats(S->linear, local_terms, sampled_constraints);
+    return LIG_OK;
+}
+// host only: the same two numbers from the deal alone
+int lig_linear_shard_count(const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, uint32_t l, uint32_t rank, uint32_t world, uint64_t* local_terms,
+                           uint64_t* needed_constraints) {
+    if (!world || rank >= world || !local_terms || !needed_constraints) return LIG_E_ARG;
+    if (lig_linear_check(sys, kinds, rows, l) != LIG_OK) return LIG_E_ARG;
+    std::vector<RowDesc> rd(rows);
+    for (uint64_t r = 0; r < rows; r++) rd[r] = RowDesc{(uint8_t)(kinds[r] & 0x7f), 0};
+    size_t rounds = 0;
+    std::vector<size_t> gb, grow;
+    shard_chunks(rd, world, rounds, gb);
+    for (size_t cidx = 0; cidx < rounds; cidx++)
+        for (size_t r = gb[cidx * world + rank]; r < gb[cidx * world + rank + 1]; r++) grow.push_back(r);
+    lig_internal_linear_shard_count(sys, l, grow, rows, rank, world, local_terms, needed_constraints);
     return LIG_OK;
 }
 
