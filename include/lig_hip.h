@@ -271,8 +271,11 @@ enum {
     LIG_ROW_EQY = 7, LIG_ROW_BQX = 8, LIG_ROW_BQY = 9, LIG_ROW_BQZ = 10,
     LIG_ROW_DRAW_PAD = 0x80      /* or-ed in: slots [l, k) of this row are drawn from the encoding stream by the library */
 };
-/* lig_rows_job.elem_bytes values with the 0x80 prefix ("packed bits"): only this one is defined */
-enum { LIG_ELEM_BIT = 0x81 };    /* slot i < l = bit i % 8 of byte i / 8, LSB first (numpy.packbits(bitorder="little")) */
+/* lig_rows_job.elem_bytes values with the 0x80 prefix: the two that are not a number of bytes */
+enum {
+    LIG_ELEM_BIT = 0x81,         /* slot i < l = bit i % 8 of byte i / 8, LSB first (numpy.packbits(bitorder="little")) */
+    LIG_ELEM_PRODUCT = 0x82      /* the QZ row of a triple, not shipped: slot i < l = x[i] * y[i] mod p, formed on the device */
+};
 typedef struct {
     uint64_t rows;                   /* committed rows, the 3 mask rows excluded */
     const uint8_t *kinds;            /* one byte per row (host memory) */
@@ -295,7 +298,15 @@ typedef struct {
      * include/util/mpz_vector.hpp:108-127).  `msgs` then holds the rows back to back in commit order, a narrow row taking
      * l * w bytes (ceil(l / 8) for bits) rounded up to a multiple of 4 -- every row starts 4-byte aligned; the padding bytes
      * are ignored -- and a full row k * 32; the library expands them on the device.  A narrow row must be LINEAR / QX / QY / QZ
-     * and flagged LIG_ROW_DRAW_PAD (its k - l pad slots are drawn by the library).  Any other value is LIG_E_ARG.
+     * and flagged LIG_ROW_DRAW_PAD (its k - l pad slots are drawn by the library).
+     * LIG_ELEM_PRODUCT = a DERIVED row: it contributes no bytes to `msgs`; its data slots i < l are x[i] * y[i] mod p
+     * (canonical), x and y being the two rows in front of it, formed on the device from their packed sources, and its pads
+     * are drawn by the library.  Only on a row of kind QZ flagged LIG_ROW_DRAW_PAD (directly behind its QX and QY, which may have
+     * any of the widths above, flagged or carrying their pads, but are never derived themselves; full-width operands must be
+     * canonical, as every full-width row); BQZ rows are device variables and are not accepted.  The prover's own valid_quad is
+     * VACUOUS for such a triple, as valid_linear is with const_sum == NULL: a caller whose z was wrong now proves a different
+     * z, and a linear constraint on it fails instead.  Any other value, or a value where it is not allowed, is LIG_E_ARG
+     * (decided on the host before anything is launched).
      * lig_rows_restart takes the same packed layout, as do lig_shard_rows_begin / _restart (there: one byte per row of the
      * whole trace, `msgs` = this rank's rows only, packed back to back in commit order). */
     const uint8_t *elem_bytes;

@@ -51,6 +51,11 @@ struct hip_proof_meta {
     // (LIG_ELEM_BIT / elem_bytes) -- on one GPU and on every rank of a sharded trace (shard_over).  Off: 8 bytes per slot on one
     // GPU, full rows when sharded.
     bool narrowest = false;
+    // With narrow_rows: the z row of every triple recorded by quadratic_callback is NOT shipped (LIG_ELEM_PRODUCT): the library forms
+    // x * y mod p on the device from the x and y rows it received, on one GPU and on every rank of a sharded trace, and draws the
+    // row's pads.  The z the guest handed over is ignored: the prover's valid_quad says nothing about such a triple -- a guest whose z
+    // was wrong proves the product instead, and a linear constraint on that z fails (valid_linear with set_linear_system).
+    bool derive_products = false;
     // Rows the guest is expected to commit (0: unknown).  The staging is page-locked memory that grows geometrically when the
     // guest outruns it; a driver that proves the same program again (or knows its size) saves the re-allocations.
     size_t expected_rows = 0;
@@ -221,10 +226,7 @@ public:
         if (meta_.narrow_rows) {
             // packed IN PLACE: a narrow row shrinks to l x (its width) bytes, rows only ever move towards the front of the staging
             const size_t R = kinds_.size();
-            widths.assign(R ? R : 1, 32);
-            bool any = false;
-            for (size_t r = 0; r < R; r++) any = (widths[r] = ship_width(r)) != 32 || any;
-            if (any) {
+            if (plan_widths(widths, true)) {
                 uint8_t* out = reinterpret_cast<uint8_t*>(rows_.row(0));
                 for (size_t r = 0; r < R; r++) {
                     if (widths[r] != 32) kinds_[r] |= LIG_ROW_DRAW_PAD;
@@ -312,12 +314,10 @@ private:
         local_of_.assign(R, (size_t)-1);
         n_local_ = 0;
         // narrowest: the widths of ALL rows (every rank sees the same rows), this rank's rows packed in place behind the compaction
+        // (derive_products without narrowest: the derived z rows leave the matrix, every other row stays full)
         std::vector<uint8_t> widths;
-        if (meta_.narrow_rows && meta_.narrowest) {
-            widths.assign(R ? R : 1, 32);
-            bool any = false;
-            for (size_t r = 0; r < R; r++) any = (widths[r] = ship_width(r)) != 32 || any;
-            if (any) {
+        if (meta_.narrow_rows && (meta_.narrowest || meta_.derive_products)) {
+            if (plan_widths(widths, meta_.narrowest)) {
                 for (size_t r = 0; r < R; r++) if (widths[r] != 32) kinds_[r] |= LIG_ROW_DRAW_PAD;
                 job.elem_bytes = widths.data();
             }
@@ -345,6 +345,18 @@ private:
         begin_pass2(rand_rows);
         std::memset(rands_.row(0), 0, (rand_rows ? rand_rows : 1) * words * 8);     // batch rows and rows without a callback keep zero rows
     }
+    // widths of all rows: a derived z row (derive_products) LIG_ELEM_PRODUCT, every other row ship_width() or, with narrow_others off,
+    // 32; false = every row is full width (the plain format)
+    bool plan_widths(std::vector<uint8_t>& widths, bool narrow_others) const {
+        const size_t R = kinds_.size();
+        widths.assign(R ? R : 1, 32);
+        bool any = false;
+        for (size_t r = 0; r < R; r++) {
+            widths[r] = meta_.derive_products && kinds_[r] == LIG_ROW_QZ ? (uint8_t)LIG_ELEM_PRODUCT : narrow_others ? ship_width(r) : 32;
+            any = any || widths[r] != 32;
+        }
+        return any;
+    }
     // the width row r of the staging is shipped in: 32 for batch rows and rows whose data slots need more than 8 bytes; else 8,
     // or with `narrowest` the smallest of bits / 1 / 2 / 4 / 8 bytes that holds every data slot (the OR of the slots decides)
     uint8_t ship_width(size_t r) const {
@@ -357,8 +369,10 @@ private:
         return lo <= 1 ? (uint8_t)LIG_ELEM_BIT : lo <= 0xff ? 1 : lo <= 0xffff ? 2 : lo <= 0xffffffffu ? 4 : 8;
     }
     // row `rw` (k x 4 u64) in the packed layout of width w written at `out` <= rw (the same staging: the write never overtakes
-    // the read); returns the next row's start -- narrow rows take l x w bytes (bits: ceil(l / 8)) zero-padded to a multiple of 4
+    // the read); returns the next row's start -- narrow rows take l x w bytes (bits: ceil(l / 8)) zero-padded to a multiple of 4,
+    // derived rows nothing
     uint8_t* pack_row(const uint64_t* rw, uint8_t w, uint8_t* out) const {
+        if (w == LIG_ELEM_PRODUCT) return out;            // a derived row: nothing is shipped
         if (w == 32) {
             if ((const void*)out != (const void*)rw) std::memmove(out, rw, (size_t)k_ * 32);
             return out + (size_t)k_ * 32;

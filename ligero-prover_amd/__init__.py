@@ -45,6 +45,7 @@ EXPORTS = [
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
 ROW_DRAW_PAD = 0x80
 ELEM_BIT = 0x81            # lig_rows_job.elem_bytes: the row's data slots are bits (LIG_ELEM_BIT)
+ELEM_PRODUCT = 0x82        # ... the QZ row of a triple is not shipped: the library forms x * y mod p on the device (LIG_ELEM_PRODUCT)
 ARG_I64, ARG_STR, ARG_HEX = 0, 1, 2
 COEF_ONE, COEF_NEG_ONE = 0xFFFFFFFF, 0xFFFFFFFE      # lig_lin_term.coef values that need no table entry (LIG_COEF_ONE / LIG_COEF_NEG_ONE)
 
@@ -357,12 +358,15 @@ def shard_plan(job, l, world):
 
 
 def pack_rows(rows, widths, l):
-    """rows (R, k, 8) uint32 + per-row width (1 / 2 / 4 / 8 / 32 / ELEM_BIT) -> the packed byte array of the narrow row format
-    (lig_rows_job.elem_bytes): a narrow row contributes its l data slots as little-endian integers of that width (ELEM_BIT: bit
-    i % 8 of byte i / 8, LSB first), zero-padded to a multiple of 4 bytes; a row of width 0 / 32 all of its k slots"""
+    """rows (R, k, 8) uint32 + per-row width (1 / 2 / 4 / 8 / 32 / ELEM_BIT / ELEM_PRODUCT) -> the packed byte array of the narrow
+    row format (lig_rows_job.elem_bytes): a narrow row contributes its l data slots as little-endian integers of that width
+    (ELEM_BIT: bit i % 8 of byte i / 8, LSB first), zero-padded to a multiple of 4 bytes; a row of width 0 / 32 all of its k
+    slots; an ELEM_PRODUCT row (a derived QZ row: rows[r] is not looked at) nothing"""
     parts = []
     for r, w in enumerate(widths):
         w = int(w)
+        if w == ELEM_PRODUCT:
+            continue
         if w in (0, 32):
             parts.append(np.ascontiguousarray(rows[r], dtype=np.uint32).tobytes())
             continue
@@ -381,14 +385,18 @@ def pack_rows(rows, widths, l):
     return np.frombuffer(b"".join(parts), dtype=np.uint8).copy()
 
 
-def narrowest_widths(rows, kinds, l):
+def narrowest_widths(rows, kinds, l, derive_products=False):
     """-> uint8 widths for pack_rows / elem_bytes: the smallest width each LINEAR / QX / QY / QZ row of rows (R, k, 8) fits into
-    (ELEM_BIT if every data slot is 0 or 1, else 1, 2, 4, 8 bytes, else 32); every other row kind is 32"""
+    (ELEM_BIT if every data slot is 0 or 1, else 1, 2, 4, 8 bytes, else 32); every other row kind is 32.
+    derive_products: every QZ row is ELEM_PRODUCT instead (not shipped; the row must then be flagged ROW_DRAW_PAD)"""
     rows = np.asarray(rows)
     kinds = np.asarray(kinds, dtype=np.uint8) & 0x7F
     out = np.full(len(kinds), 32, dtype=np.uint8)
     for r in range(len(kinds)):
         if kinds[r] > 3:
+            continue
+        if derive_products and kinds[r] == 3:
+            out[r] = ELEM_PRODUCT
             continue
         d = rows[r, :l]
         if d[:, 2:].any():

@@ -61,6 +61,7 @@ struct lig_trace {
     std::vector<uint64_t> src_off;
     std::vector<uint8_t> widths;
     uint64_t* src_off_dev = nullptr; uint8_t* widths_dev = nullptr; uint8_t* packed_dev = nullptr;
+    ProductRows prod;                   // derived rows (LIG_ELEM_PRODUCT): formed next to the expansion from the packed x and y rows
     lig_proof_info info1;               // stage-1 results kept between lig_rows_commit and lig_rows_prove
     size_t R = 0, RB = 0, n_init = 0;   // all rows, leading rows committed by the batch program, of those: init rows
     fr* msgs = nullptr;                 // R x k witness matrix (pads are re-drawn by every prove)
@@ -345,7 +346,8 @@ static int prove_stage1(lig_trace* T, lig_proof_info* info, const std::function<
         if (streamed) {
             if (T->up_by_thread) HIP_TRY(c, hipStreamWaitValue32(s_enc, T->up_flag_dev + ci, T->up_seq, hipStreamWaitValueGte, 0xffffffffu));
             else HIP_TRY(c, hipStreamWaitEvent(s_enc, T->ev_up[ci], 0));                   // this chunk's rows have arrived
-            if (T->narrow) lig::launch_expand_rows(s_enc, T->packed_dev, T->src_off_dev, T->widths_dev, b, nb, l, k, T->msgs);
+            // (a derived row whose x / y rows belong to the previous chunk reads them from the staging area: that chunk's arrival was waited for earlier on this stream)
+            if (T->narrow) lig::launch_expand_rows(s_enc, T->packed_dev, T->src_off_dev, T->widths_dev, b, nb, l, k, T->msgs, T->prod.first(b), T->prod.count(b, b + nb));
             for (; pr_i < T->pad_runs.size() && T->pad_runs[pr_i].first < b + nb; pr_i++) {      // runs never straddle chunks (split in begin)
                 const PadRun& pr = T->pad_runs[pr_i];
                 lig::launch_rng_fill_rows(s_enc, c->rk_dev, pr.pos, T->msgs + pr.first * (size_t)k, pr.count, pad, k, l, 1, pad);
@@ -773,7 +775,7 @@ void lig_trace_destroy(lig_trace* T) {
     for (int a3 = 0; a3 < 3; a3++) if (T->ev_acc[a3]) (void)hipEventDestroy(T->ev_acc[a3]);
     for (hipEvent_t e : T->ev_up) (void)hipEventDestroy(e);
     if (T->up_flag) (void)hipHostFree((void*)T->up_flag);
-    (void)hipFree(T->src_off_dev); (void)hipFree(T->widths_dev); (void)hipFree(T->packed_dev);
+    (void)hipFree(T->src_off_dev); (void)hipFree(T->widths_dev); (void)hipFree(T->packed_dev); (void)hipFree(T->prod.dev);
     (void)hipHostFree(T->h_proof); (void)hipHostFree(T->h_enc); (void)hipHostFree(T->h_nodes); (void)hipHostFree(T->h_small);
     delete T;
 }
@@ -1026,7 +1028,7 @@ static int rows_load(lig_ctx* c, lig_trace* T, const void* msgs, bool on_device)
         T->alt_pending = true;
     }
     if (on_device) {
-        if (T->narrow) lig::launch_expand_rows(c->stream, (const uint8_t*)msgs, T->src_off_dev, T->widths_dev, 0, R, c->l, k, dst);
+        if (T->narrow) lig::launch_expand_rows(c->stream, (const uint8_t*)msgs, T->src_off_dev, T->widths_dev, 0, R, c->l, k, dst, T->prod.dev, T->prod.rows.size());
         else HIP_TRY(c, hipMemcpyAsync(dst, msgs, R * (size_t)k * 32, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(c, hipGetLastError());
         return LIG_OK;
@@ -1103,9 +1105,9 @@ static int rows_begin_impl(lig_ctx* c, const lig_rows_job* job, lig_trace* T) {
         T->widths.assign(R ? R : 1, 32);
         for (size_t r = 0; r < R; r++) {
             const uint8_t w = job->elem_bytes[r] ? job->elem_bytes[r] : 32;
-            if (!lig::narrow_row_bytes(w, l, k)) FAIL(c, LIG_E_ARG, "rows job: elem_bytes must be 0, 1, 2, 4, 8, 32 or LIG_ELEM_BIT");
-            if (w != 32 && (T->rows[r].kind > 3 || !draw[r])) FAIL(c, LIG_E_ARG, "rows job: a narrow row must be LINEAR / QX / QY / QZ with LIG_ROW_DRAW_PAD");
-            T->narrow = T->narrow || w != 32;
+            if (const char* why = lig::narrow_row_refusal(job->elem_bytes, r, T->rows[r].kind, draw[r] != 0, l, k)) FAIL(c, LIG_E_ARG, std::string("rows job: ") + why);
+            T->narrow = T->narrow || w != 32;          // (a derived row alone takes the packed path as well)
+            if (w == LIG_ELEM_PRODUCT) T->prod.rows.push_back((uint32_t)r);
             T->widths[r] = w;
             T->src_off[r + 1] = T->src_off[r] + lig::narrow_row_bytes(w, l, k);
         }
@@ -1116,6 +1118,10 @@ static int rows_begin_impl(lig_ctx* c, const lig_rows_job* job, lig_trace* T) {
         HIP_TRY(c, hipMalloc((void**)&T->widths_dev, R));
         HIP_TRY(c, hipMemcpy(T->src_off_dev, T->src_off.data(), (R + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemcpy(T->widths_dev, T->widths.data(), R, hipMemcpyHostToDevice));
+        if (!T->prod.rows.empty()) {
+            HIP_TRY(c, hipMalloc((void**)&T->prod.dev, T->prod.rows.size() * sizeof(uint32_t)));
+            HIP_TRY(c, hipMemcpy(T->prod.dev, T->prod.rows.data(), T->prod.rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
         if (!job->msgs_on_device) HIP_TRY(c, hipMalloc((void**)&T->packed_dev, T->src_off[R] ? T->src_off[R] : 16));
     }
     // pad runs: consecutive flagged rows whose stream positions are consecutive, never straddling a stage-1 chunk

@@ -40,18 +40,33 @@ void launch_lin_interleave(hipStream_t s, fr* out, const fr* accH, const fr* acc
 void launch_rlc_combine(hipStream_t s, fr* acc, const fr* part, uint32_t groups, uint32_t count);
 void launch_copy_from_host(hipStream_t s, uint8_t* dst_dev, const uint8_t* src_mapped, size_t bytes);
 // narrow caller rows (lig_rows_job.elem_bytes, expand.hip): rows [first_row, first_row + rows) of the packed matrix -- row r at
-// packed + off_dev[r], width widths_dev[r] -- into out + r * k, full width; slots l..k-1 of a narrow row are zeroed
+// packed + off_dev[r], width widths_dev[r] -- into out + r * k, full width; slots l..k-1 of a narrow row are zeroed.
+// prod_rows_dev[0 .. n_prod): the derived rows (LIG_ELEM_PRODUCT) among them, ascending row indices -- formed from the packed
+// sources of the two rows in front of each (which may lie before first_row: they only have to be in `packed`)
 void launch_expand_rows(hipStream_t s, const uint8_t* packed, const uint64_t* off_dev, const uint8_t* widths_dev, size_t first_row,
-                        size_t rows, uint32_t l, uint32_t k, fr* out);
-// packed bytes of one row of width w (0 = not a width of the format): 32 -> all k slots; bits, 1, 2, 4, 8 -> the l data slots,
-// rounded up to a multiple of 4 so that every row starts 4-byte aligned
+                        size_t rows, uint32_t l, uint32_t k, fr* out, const uint32_t* prod_rows_dev = nullptr, size_t n_prod = 0);
+// packed bytes of one row of width w (NOT_A_WIDTH = no width of the format): 32 -> all k slots; bits, 1, 2, 4, 8 -> the l data
+// slots, rounded up to a multiple of 4 so that every row starts 4-byte aligned; LIG_ELEM_PRODUCT -> 0, the row is derived
+static constexpr uint64_t NOT_A_WIDTH = ~(uint64_t)0;
 inline uint64_t narrow_row_bytes(uint32_t w, uint32_t l, uint32_t k) {
     switch (w) {
         case 32: return (uint64_t)k * 32;
         case LIG_ELEM_BIT: return ((uint64_t)l + 31) / 32 * 4;
         case 1: case 2: case 4: case 8: return ((uint64_t)l * w + 3) & ~(uint64_t)3;
-        default: return 0;
+        case LIG_ELEM_PRODUCT: return 0;
+        default: return NOT_A_WIDTH;
     }
+}
+// elem_bytes[r] of a rows job checked against the row's kind (kind: without the flag; draws: LIG_ROW_DRAW_PAD given).  nullptr = accepted.
+inline const char* narrow_row_refusal(const uint8_t* elem_bytes, size_t r, uint8_t kind, bool draws, uint32_t l, uint32_t k) {
+    const uint8_t w = elem_bytes[r] ? elem_bytes[r] : 32;
+    if (narrow_row_bytes(w, l, k) == NOT_A_WIDTH) return "elem_bytes must be 0, 1, 2, 4, 8, 32, LIG_ELEM_BIT or LIG_ELEM_PRODUCT";
+    if (w == LIG_ELEM_PRODUCT) {
+        // (a QZ row has its QX and QY in front of it -- the kinds were checked first -- and neither of them can be derived)
+        return kind == 3 && draws ? nullptr : "LIG_ELEM_PRODUCT is only accepted on a QZ row with LIG_ROW_DRAW_PAD";
+    }
+    if (w != 32 && (kind > 3 || !draws)) return "a narrow row must be LINEAR / QX / QY / QZ with LIG_ROW_DRAW_PAD";
+    return nullptr;
 }
 }  // namespace lig
 
@@ -76,6 +91,13 @@ std::string lig_internal_uploader_state(int device);                  // diagnos
 struct RowDesc { uint8_t kind; uint32_t data; };
 // `count` consecutive rows from `first` whose k-l pads are element pos, pos + (k-l), ... of the encoding stream
 struct PadRun { size_t first, count; uint64_t pos; };
+// the derived rows of a packed matrix, ascending, and their copy on the device: what launch_expand_rows takes for rows [b, e)
+struct ProductRows {
+    std::vector<uint32_t> rows;
+    uint32_t* dev = nullptr;
+    const uint32_t* first(size_t b) const { return dev + (std::lower_bound(rows.begin(), rows.end(), (uint32_t)b) - rows.begin()); }
+    size_t count(size_t b, size_t e) const { return std::lower_bound(rows.begin(), rows.end(), (uint32_t)e) - std::lower_bound(rows.begin(), rows.end(), (uint32_t)b); }
+};
 
 namespace {
 

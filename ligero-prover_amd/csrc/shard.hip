@@ -68,6 +68,7 @@ struct lig_shard {
     bool narrow = false;
     std::vector<uint64_t> src_off;
     uint64_t* src_off_dev = nullptr; uint8_t* widths_dev = nullptr; uint8_t* packed_dev = nullptr;
+    ProductRows prod;                          // derived LOCAL rows (LIG_ELEM_PRODUCT)
     // sparse linear system (lig_shard_rows_set_linear): this rank's share of it, regrouped by local slot (linear.hip), and the local rows x k
     // randomness matrix it is formed into per proof; both survive lig_shard_rows_restart
     lig_linear* linear = nullptr;
@@ -335,7 +336,7 @@ void lig_shard_destroy(lig_shard* S) {
     for (void* p : {(void*)S->msgs, (void*)S->cw, (void*)S->maskcw, (void*)S->send, (void*)S->recv, (void*)S->randb, (void*)S->rhalf, (void*)S->acc,
                     (void*)S->parts, (void*)S->accp, (void*)S->accg, (void*)S->dots, (void*)S->smp, (void*)S->smpg, (void*)S->sha_state,
                     (void*)S->leaves_slice, (void*)S->leaves, (void*)S->nodes, (void*)S->tri_dev, (void*)S->coef_dev, (void*)S->src_off_dev,
-                    (void*)S->widths_dev, (void*)S->packed_dev})
+                    (void*)S->widths_dev, (void*)S->packed_dev, (void*)S->prod.dev})
         (void)hipFree(p);
     for (int i = 0; i < 2; i++)
         for (hipEvent_t e : {S->ev_enc[i], S->ev_comm[i], S->ev_hash[i]}) if (e) (void)hipEventDestroy(e);
@@ -864,7 +865,7 @@ static int shard_rows_load(lig_shard* S, const void* local_msgs, bool on_device)
             if (S->src_off[S->Rl]) HIP_TRY(c, hipMemcpyAsync(S->packed_dev, local_msgs, S->src_off[S->Rl], hipMemcpyHostToDevice, c->stream));
             src = S->packed_dev;
         }
-        lig::launch_expand_rows(c->stream, src, S->src_off_dev, S->widths_dev, 0, S->Rl, c->l, c->k, S->msgs);
+        lig::launch_expand_rows(c->stream, src, S->src_off_dev, S->widths_dev, 0, S->Rl, c->l, c->k, S->msgs, S->prod.dev, S->prod.rows.size());
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's memory is no longer referenced
         return LIG_OK;
@@ -899,8 +900,7 @@ static int shard_narrow_setup(lig_shard* S, const lig_rows_job* job, uint32_t l,
     std::vector<uint8_t> widths(S->R);
     for (size_t r = 0; r < S->R; r++) {
         const uint8_t w = job->elem_bytes[r] ? job->elem_bytes[r] : 32;
-        if (!lig::narrow_row_bytes(w, l, k)) FAIL(c, LIG_E_ARG, "sharded rows job: elem_bytes must be 0, 1, 2, 4, 8, 32 or LIG_ELEM_BIT");
-        if (w != 32 && (S->rows[r].kind > 3 || !S->draw[r])) FAIL(c, LIG_E_ARG, "sharded rows job: a narrow row must be LINEAR / QX / QY / QZ with LIG_ROW_DRAW_PAD");
+        if (const char* why = lig::narrow_row_refusal(job->elem_bytes, r, S->rows[r].kind, S->draw[r] != 0, l, k)) FAIL(c, LIG_E_ARG, std::string("sharded rows job: ") + why);
         widths[r] = w;
         S->narrow = S->narrow || w != 32;
     }
@@ -911,6 +911,11 @@ static int shard_narrow_setup(lig_shard* S, const lig_rows_job* job, uint32_t l,
     for (size_t lr = 0; lr < Rl; lr++) {
         local_w[lr] = widths[S->grow[lr]];
         S->src_off[lr + 1] = S->src_off[lr] + lig::narrow_row_bytes(local_w[lr], l, k);
+        if (local_w[lr] == LIG_ELEM_PRODUCT) S->prod.rows.push_back((uint32_t)lr);       // x, y are local rows lr - 2, lr - 1: the deal never splits a triple
+    }
+    if (!S->prod.rows.empty()) {
+        HIP_TRY(c, hipMalloc((void**)&S->prod.dev, S->prod.rows.size() * sizeof(uint32_t)));
+        HIP_TRY(c, hipMemcpy(S->prod.dev, S->prod.rows.data(), S->prod.rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     HIP_TRY(c, hipMalloc((void**)&S->src_off_dev, (Rl + 1) * sizeof(uint64_t)));
     HIP_TRY(c, hipMalloc((void**)&S->widths_dev, local_w.size()));
