@@ -411,6 +411,47 @@ int lig_rows_verify_set_linear(lig_vtrace *trace, const lig_linear_system *sys);
 int lig_linear_form(lig_ctx *ctx, const lig_linear_system *sys, const uint8_t *kinds, uint64_t rows, const uint8_t key32[32],
                     void *rands_dev, uint8_t const_sum[32]);
 
+/* ---- prepared linear systems: one resident structure for many proofs, many verifications, several contexts.
+ * lig_rows_set_linear / lig_rows_verify_set_linear / lig_linear_form above prepare a structure that ONE trace owns.  The entries
+ * below split that in two: the PROGRAM (the regrouped structure: immutable, reference counted, shared) and the ATTACHMENT of one
+ * trace to it (what a proof writes: the sampled r_c, partial sums, the constant, an overriding coefficient table).  A verifier
+ * service prepares once and attaches per envelope; two contexts proving the same guest hold one copy; a new statement of the same
+ * program (other right-hand sides) is lig_rows_set_linear_values, not a new prepare.
+ * The sharded entry (lig_shard_rows_set_linear) is not covered: a rank's structure depends on its deal, and nothing shares it. */
+typedef struct lig_linear_program lig_linear_program;
+/* check (lig_linear_check), upload, regroup by slot -- what lig_rows_set_linear does -- into an immutable, reference-counted object
+ * bound to ctx's DEVICE and (l, k), not to ctx: it may be attached to traces of any context of this process on that device, from any
+ * thread, and outlives ctx.  Synchronous: every pointer of *sys may be released when it returns; nothing writes the program's device
+ * memory afterwards.  The caller owns one reference.  LIG_E_ARG for a system lig_linear_check rejects (nothing is launched). */
+int  lig_linear_prepare(lig_ctx *ctx, const lig_linear_system *sys, const uint8_t *kinds, uint64_t rows, lig_linear_program **out);
+/* drops the caller's reference; NULL is a no-op.  Every attachment holds a reference of its own, so this may come before
+ * lig_trace_destroy / lig_rows_verify_finish / lig_vtrace_destroy; device memory goes with the last reference (atomic count). */
+void lig_linear_program_release(lig_linear_program *p);
+/* host only: the device memory the program holds, and what EVERY attachment to it allocates on top (r and the partial sums; an
+ * attachment with values of its own adds n_coefs x 32) -- the sizes of the library's own allocations */
+int  lig_linear_program_bytes(const lig_linear_program *p, uint64_t *program_bytes, uint64_t *attachment_bytes);
+/* lig_rows_set_linear with a prepared program: same window (after lig_rows_begin, before lig_rows_prove), same effect on
+ * lig_rows_prove (rands == NULL forms the matrix; const_sum == NULL is the system's constant), survives lig_rows_restart, replaces
+ * a system set with lig_rows_set_linear and is replaced by one; p == NULL detaches.  Checked on the host before anything is
+ * launched: the trace has the program's device, l, k, row count and row kinds (LIG_ROW_DRAW_PAD masked off), else LIG_E_ARG;
+ * LIG_E_ARG for a job with dense_rands_per_row; LIG_E_STATE after lig_rows_push_rands*.  While attached, lig_rows_prove(rands !=
+ * NULL) is LIG_E_ARG and lig_rows_push_rands* is LIG_E_STATE. */
+int  lig_rows_attach_linear(lig_trace *trace, const lig_linear_program *p);
+/* the verifier's side (lig_rows_verify_set_linear with a prepared program); the attachment goes with lig_rows_verify_finish or
+ * lig_vtrace_destroy */
+int  lig_rows_verify_attach_linear(lig_vtrace *trace, const lig_linear_program *p);
+/* per-proof VALUES of the coefficient table of the attached structure: coefs[] with the program's n_coefs, canonical -- the public
+ * right-hand sides b_c of a new statement are the entries named by rhs_coef.  They belong to the attachment, not the program (two
+ * traces on one program may carry different values), and stay over lig_rows_restart until set again; coefs == NULL: back to the
+ * program's own table.  Copied before the call returns; the table is converted on the device, on the stream the forms run on.
+ * LIG_E_ARG: another n_coefs, an entry >= p (decided on the host, nothing launched); LIG_E_STATE: nothing attached. */
+int  lig_rows_set_linear_values(lig_trace *trace, const uint8_t *coefs, uint64_t n_coefs);
+int  lig_rows_verify_set_linear_values(lig_vtrace *trace, const uint8_t *coefs, uint64_t n_coefs);
+/* lig_linear_form without the prepare (blocking); coefs == NULL uses the program's table.  LIG_E_ARG when ctx is on another device
+ * or has another (l, k). */
+int  lig_linear_program_form(lig_ctx *ctx, const lig_linear_program *p, const uint8_t key32[32], const uint8_t *coefs, uint64_t n_coefs,
+                             void *rands_dev, uint8_t const_sum[32]);
+
 /* ==== proof file framing (src/webgpu_prover.cpp:437-457 writes gzip(level 6) of the serialized envelope with
  * Boost.iostreams; src/webgpu_verifier.cpp:249-253 reads it back).  Host-only helpers on zlib: the output is a standard
  * gzip member that any gzip reader (the reference's gzip_decompressor included) accepts; compressed BYTES depend on the

@@ -109,6 +109,7 @@ public:
         set_ = true;
     }
     bool is_set() const { return set_; }
+    void clear() { sys_ = lig_linear_system{}; set_ = false; }
     const lig_linear_system* get() const { return &sys_; }
 private:
     bool set_ = false;
@@ -136,6 +137,7 @@ public:
     // the batcher.  Every rank's prove() returns the same envelope as an unsharded batcher would.
     void shard_over(uint32_t rank, uint32_t world, const lig_comm* comm) {
         if (pass_ != 1 || !comm || !world || rank >= world) throw std::invalid_argument("hip_row_batcher::shard_over");
+        if (program_ || values_set_) throw std::logic_error("hip_row_batcher::shard_over: a prepared linear program / values of its table are not for a sharded batcher");
         if (shard_) { lig_shard_destroy(shard_); shard_ = nullptr; linear_on_trace_ = false; }      // another deal: nothing of the old shard is reused
         sharded_ = true; rank_ = rank; world_ = world; comm_ = *comm;
     }
@@ -150,8 +152,38 @@ public:
         if (pass_ == 3) throw std::logic_error("hip_row_batcher::set_linear_system after prove (reset() first)");
         if (pass_ == 2 && pushed_) throw std::logic_error("hip_row_batcher::set_linear_system: randomness rows have already been handed over");
         linear_.assign(sys);
-        linear_on_trace_ = false;
+        program_ = nullptr; values_set_ = false;          // (a system and a program replace each other; values belong to what they were set on)
+        linear_on_trace_ = values_on_trace_ = false;
         if (pass_ == 2) apply_linear();
+    }
+    // The same with a structure prepared once (lig_linear_prepare): one lig_linear_program may feed any
+    // number of batchers and verifiers, of any context on its device, at the same time; nothing is uploaded or regrouped here.  Not
+    // copied and not owned: the caller keeps its reference for as long as this batcher may still begin a trace with it (the trace
+    // itself holds a reference of its own once the program is attached).  Kept across reset(); nullptr removes it.  Not with
+    // shard_over(): a rank's structure depends on its deal (set_linear_system there).
+    void set_linear_program(const lig_linear_program* p) {
+        if (pass_ == 3) throw std::logic_error("hip_row_batcher::set_linear_program after prove (reset() first)");
+        if (pass_ == 2 && pushed_) throw std::logic_error("hip_row_batcher::set_linear_program: randomness rows have already been handed over");
+        if (p && sharded_) throw std::logic_error("hip_row_batcher::set_linear_program: not on a sharded batcher (set_linear_system)");
+        linear_.clear();
+        program_ = p; values_set_ = false;
+        linear_on_trace_ = values_on_trace_ = false;
+        if (pass_ == 2) {
+            if (p) apply_linear();
+            else check(lig_rows_attach_linear(trace_, nullptr), "lig_rows_attach_linear");
+        }
+    }
+    // The values of the coefficient table for the proofs that follow (lig_rows_set_linear_values): n_coefs x 32 bytes, canonical,
+    // n_coefs as in the system / program -- the public right-hand sides of a new statement of the same program are the entries that
+    // rhs_coef names.  Copied; kept across reset() until set again; nullptr: the table the system / program came with.
+    void set_linear_values(const uint8_t* coefs, uint64_t n_coefs) {
+        if (pass_ == 3) throw std::logic_error("hip_row_batcher::set_linear_values after prove (reset() first)");
+        if (!has_linear()) throw std::logic_error("hip_row_batcher::set_linear_values without a linear system or program");
+        if (sharded_) throw std::logic_error("hip_row_batcher::set_linear_values: not on a sharded batcher");
+        values_set_ = coefs != nullptr;
+        values_.assign(coefs, coefs + (coefs ? n_coefs * 32 : 0));
+        values_on_trace_ = false;
+        if (pass_ == 2 && linear_on_trace_) apply_values();      // (pass 1: with the attach / after the restart of the next commit())
     }
 
     // ---- the callbacks of nonbatch_context_base (nonbatch_context.hpp:78-86).  `rand` rows are null in pass 1.
@@ -167,7 +199,7 @@ public:
     uint64_t* next_slot() {
         if (pass_ == 1) { rows_.reserve(kinds_.size() + 1, kinds_.size()); return rows_.row(kinds_.size()); }
         if (pass_ != 2 || next_ >= kinds_.size()) throw std::logic_error("hip_row_batcher::next_slot: no row expected");
-        if (sharded_ && linear_.is_set()) return rands_.row(0);  // the library forms the randomness rows: what is exported here is never read
+        if (sharded_ && has_linear()) return rands_.row(0);  // the library forms the randomness rows: what is exported here is never read
         if (!sharded_) return rands_.row(n_present_);            // randomness rows are kept packed: only rows that have one take a slot
         const size_t slot = local_of_[next_];
         return slot == (size_t)-1 ? nullptr : rands_.row(slot);
@@ -238,7 +270,7 @@ public:
         }
         if (trace_) {                                      // the next proof of the same program: every device buffer is reused
             if (same_shape(job)) check(lig_rows_restart(trace_, job.msgs, 0), "lig_rows_restart");
-            else { lig_trace_destroy(trace_); trace_ = nullptr; linear_on_trace_ = false; }
+            else { lig_trace_destroy(trace_); trace_ = nullptr; linear_on_trace_ = values_on_trace_ = false; }
         }
         if (!trace_) check(lig_rows_begin(ctx_, &job, &trace_), "lig_rows_begin");
         shape_kinds_ = kinds_; shape_widths_ = widths; shape_meta_ = meta_;
@@ -253,7 +285,7 @@ public:
     // (owned by the batcher, valid until it is destroyed or reset); `info` (optional) receives the prover's self-check.
     const uint8_t* prove(const uint8_t const_sum[32], size_t* proof_len, lig_proof_info* info = nullptr) {
         if (pass_ != 2) throw std::logic_error("hip_row_batcher::prove before commit");
-        const bool linear = linear_.is_set();
+        const bool linear = has_linear();
         if (!linear && next_ != kinds_.size()) throw std::logic_error("hip_row_batcher::prove: pass 2 replayed " + std::to_string(next_) + " of " + std::to_string(kinds_.size()) + " rows");
         const uint8_t* proof = nullptr;
         lig_proof_info local;
@@ -295,14 +327,25 @@ private:
     // randomness rows [pushed_, upto) are complete: hand them to the library while the guest goes on.  Only the rows that HAVE a
     // randomness row are in the staging (packed) and go over the link; the library zero-fills the others on the device
     // (lig_rows_push_rands_sparse) -- batch rows never have one, quadratic rows often do not.
+    bool has_linear() const { return linear_.is_set() || program_ != nullptr; }
     void apply_linear() {
-        if (!linear_.is_set() || linear_on_trace_ || !(sharded_ ? (bool)shard_ : (bool)trace_)) return;
-        if (sharded_) check(lig_shard_rows_set_linear(shard_, linear_.get()), "lig_shard_rows_set_linear");
-        else check(lig_rows_set_linear(trace_, linear_.get()), "lig_rows_set_linear");
-        linear_on_trace_ = true;
+        if (!has_linear() || !(sharded_ ? (bool)shard_ : (bool)trace_)) return;
+        if (!linear_on_trace_) {
+            if (sharded_ && program_) throw std::logic_error("hip_row_batcher: a prepared linear program on a sharded batcher (set_linear_system)");
+            if (sharded_) check(lig_shard_rows_set_linear(shard_, linear_.get()), "lig_shard_rows_set_linear");
+            else if (program_) check(lig_rows_attach_linear(trace_, program_), "lig_rows_attach_linear");
+            else check(lig_rows_set_linear(trace_, linear_.get()), "lig_rows_set_linear");
+            linear_on_trace_ = true;
+            values_on_trace_ = !values_set_;              // a fresh attachment reads the table it came with
+        }
+        if (!sharded_ && !values_on_trace_) apply_values();
+    }
+    void apply_values() {                                 // (the trace keeps them across lig_rows_restart)
+        check(lig_rows_set_linear_values(trace_, values_set_ ? values_.data() : nullptr, values_.size() / 32), "lig_rows_set_linear_values");
+        values_on_trace_ = true;
     }
     void push_rands(size_t upto) {
-        if (sharded_ || upto <= pushed_ || linear_.is_set()) return;
+        if (sharded_ || upto <= pushed_ || has_linear()) return;
         check(lig_rows_push_rands_sparse(trace_, pushed_, upto - pushed_, present_.data() + pushed_, rands_.row(pushed_present_)), "lig_rows_push_rands_sparse");
         pushed_ = upto; pushed_present_ = n_present_;
     }
@@ -341,7 +384,7 @@ private:
         apply_linear();                                   // this rank's share of the system, under the commit
         check(lig_shard_rows_commit(shard_, root, stage1_seed), "lig_shard_rows_commit");
         for (auto& kd : kinds_) kd &= 0x7f;               // (pass 2 compares plain kinds)
-        const size_t rand_rows = linear_.is_set() ? 0 : n_local_;      // with a system no randomness row is staged (one scratch row for next_slot)
+        const size_t rand_rows = has_linear() ? 0 : n_local_;      // with a system no randomness row is staged (one scratch row for next_slot)
         begin_pass2(rand_rows);
         std::memset(rands_.row(0), 0, (rand_rows ? rand_rows : 1) * words * 8);     // batch rows and rows without a callback keep zero rows
     }
@@ -410,7 +453,7 @@ private:
         } else if (pass_ == 2) {
             // the guest is deterministic: pass 2 must replay the callbacks of pass 1 in the same order
             if (next_ >= kinds_.size() || kinds_[next_] != kind) throw std::logic_error("hip_row_batcher: pass 2 diverges from pass 1");
-            if (linear_.is_set()) {                                                  // the library forms the randomness rows: the replay is only counted
+            if (has_linear()) {                                                  // the library forms the randomness rows: the replay is only counted
             } else if (sharded_) {                                                   // dense local matrix: only the rows of this rank's chunks are kept
                 const size_t slot = local_of_[next_];
                 if (slot != (size_t)-1 && !in_slot && rand) std::memcpy(rands_.row(slot), rand, words * 8);
@@ -445,7 +488,11 @@ private:
     hip_row_staging rows_, rands_;
     lig_trace* trace_ = nullptr;
     hip_linear_system_copy linear_;
-    bool linear_on_trace_ = false;                        // trace_ holds linear_ (it stays resident across lig_rows_restart)
+    const lig_linear_program* program_ = nullptr;         // set_linear_program: the caller's object (linear_ is then unset)
+    std::vector<uint8_t> values_;                         // set_linear_values
+    bool values_set_ = false;
+    bool linear_on_trace_ = false;                        // trace_ holds linear_ / program_ (it stays resident across lig_rows_restart)
+    bool values_on_trace_ = false;                        // ... and the values of values_ (or, !values_set_, its own table)
     bool sharded_ = false;
     uint32_t rank_ = 0, world_ = 1;
     lig_comm comm_{};
@@ -473,7 +520,23 @@ public:
     // run of the guest, nothing but the envelope and the public structure.  Before or after begin(); copied.
     void set_linear_system(const lig_linear_system& sys) {
         linear_.assign(sys);
+        program_ = nullptr; values_set_ = false;
         if (vt_ && lig_rows_verify_set_linear(vt_, linear_.get()) != LIG_OK) throw std::runtime_error(std::string("lig_rows_verify_set_linear: ") + lig_last_error(ctx_));
+    }
+    // the same with a structure prepared once (lig_linear_prepare): a verifier service prepares per program, not per envelope.  Not
+    // copied and not owned: the caller keeps its reference while this verifier may still begin() with it.  nullptr removes it.
+    void set_linear_program(const lig_linear_program* p) {
+        linear_.clear();
+        program_ = p; values_set_ = false;
+        if (vt_ && lig_rows_verify_attach_linear(vt_, p) != LIG_OK) throw std::runtime_error(std::string("lig_rows_verify_attach_linear: ") + lig_last_error(ctx_));
+    }
+    // the values of the coefficient table of the statement to verify (lig_rows_verify_set_linear_values): the public right-hand
+    // sides are part of the statement.  Copied; kept for the envelopes that follow until set again; nullptr: the structure's own table.
+    void set_linear_values(const uint8_t* coefs, uint64_t n_coefs) {
+        if (!has_linear()) throw std::logic_error("hip_row_verifier::set_linear_values without a linear system or program");
+        values_set_ = coefs != nullptr;
+        values_.assign(coefs, coefs + (coefs ? n_coefs * 32 : 0));
+        if (vt_) apply_values();
     }
     // parse the envelope, re-derive both seeds and the sample indices; false: malformed envelope / wrong indices (reject)
     bool begin(const uint8_t* proof, size_t len, uint8_t stage1_seed[32], lig_verify_info* info = nullptr) {
@@ -492,7 +555,10 @@ public:
         if (rc != LIG_OK) throw std::runtime_error(std::string("lig_rows_verify_begin: ") + lig_last_error(ctx_));
         if (vt_ && linear_.is_set() && lig_rows_verify_set_linear(vt_, linear_.get()) != LIG_OK)
             throw std::runtime_error(std::string("lig_rows_verify_set_linear: ") + lig_last_error(ctx_));
-        if (!linear_.is_set()) rands_.assign(kinds_.size() * (size_t)k_ * 4, 0);
+        if (vt_ && program_ && lig_rows_verify_attach_linear(vt_, program_) != LIG_OK)
+            throw std::runtime_error(std::string("lig_rows_verify_attach_linear: ") + lig_last_error(ctx_));
+        if (vt_ && has_linear() && values_set_) apply_values();
+        if (!has_linear()) rands_.assign(kinds_.size() * (size_t)k_ * 4, 0);
         next_ = 0;
         return vt_ != nullptr;
     }
@@ -505,7 +571,7 @@ public:
     // the seven predicates of webgpu_verifier.cpp:412-442; returns accept
     bool finish(const uint8_t const_sum[32], lig_verify_info* info = nullptr) {
         if (!vt_) throw std::logic_error("hip_row_verifier::finish without a successful begin");
-        const bool linear = linear_.is_set();
+        const bool linear = has_linear();
         if (!linear && next_ != kinds_.size()) throw std::logic_error("hip_row_verifier::finish: fewer rows replayed than expected");
         lig_verify_info local;
         lig_verify_info* o = info ? info : &local;
@@ -516,9 +582,14 @@ public:
     }
 
 private:
+    bool has_linear() const { return linear_.is_set() || program_ != nullptr; }
+    void apply_values() {
+        if (lig_rows_verify_set_linear_values(vt_, values_set_ ? values_.data() : nullptr, values_.size() / 32) != LIG_OK)
+            throw std::runtime_error(std::string("lig_rows_verify_set_linear_values: ") + lig_last_error(ctx_));
+    }
     void row(uint8_t kind, const uint64_t* rand) {
         if (next_ >= kinds_.size() || (kinds_[next_] & 0x7f) != kind) throw std::logic_error("hip_row_verifier: the guest diverges from the expected row kinds");
-        if (rand && !linear_.is_set()) std::memcpy(rands_.data() + next_ * (size_t)k_ * 4, rand, (size_t)k_ * 32);
+        if (rand && !has_linear()) std::memcpy(rands_.data() + next_ * (size_t)k_ * 4, rand, (size_t)k_ * 32);
         next_++;
     }
     lig_ctx* ctx_;
@@ -528,6 +599,9 @@ private:
     std::vector<uint8_t> kinds_;
     std::vector<uint64_t> rands_;
     hip_linear_system_copy linear_;
+    const lig_linear_program* program_ = nullptr;
+    std::vector<uint8_t> values_;
+    bool values_set_ = false;
     lig_vtrace* vt_ = nullptr;
 };
 

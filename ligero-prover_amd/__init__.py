@@ -40,6 +40,8 @@ EXPORTS = [
     "lig_upload_health", "lig_profile_read_launches",
     "lig_linear_check", "lig_linear_form", "lig_rows_set_linear", "lig_rows_verify_set_linear",
     "lig_shard_rows_set_linear", "lig_shard_rows_linear_stats", "lig_linear_shard_count",
+    "lig_linear_prepare", "lig_linear_program_release", "lig_linear_program_bytes", "lig_rows_attach_linear", "lig_rows_verify_attach_linear",
+    "lig_rows_set_linear_values", "lig_rows_verify_set_linear_values", "lig_linear_program_form",
 ]
 
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
@@ -152,6 +154,51 @@ def linear_shard_count(system, kinds, l, rank, world):
     if rc != 0:
         raise LigError("lig_linear_shard_count failed (%d)" % rc)
     return int(lt.value), int(nc.value)
+
+
+def coef_table(coefs):
+    """a coefficient table as the (n, 8) uint32 array the library reads: Python integers in [0, 2^256) or an array of limbs"""
+    if isinstance(coefs, np.ndarray):
+        return np.ascontiguousarray(coefs, dtype=np.uint32).reshape(-1, 8)
+    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in coefs), dtype=np.uint32).reshape(-1, 8).copy()
+
+
+class LinearProgram:
+    """lig_linear_program: a prepared linear system (Context.linear_prepare) -- immutable, reference counted by the library, bound to a
+    device and (l, k).  This object is the CALLER's reference: release() (or leaving a `with` block) drops it exactly once; traces it
+    was attached to keep the structure alive for as long as they need it."""
+
+    def __init__(self, lib, handle):
+        self._lib, self.h = lib, handle
+
+    def release(self):
+        h, self.h = self.h, None
+        if h:
+            self._lib.lig_linear_program_release(h)
+
+    def bytes(self):
+        """-> (device bytes the program holds, device bytes every attachment adds)"""
+        pb, ab = C.c_uint64(), C.c_uint64()
+        if self._lib.lig_linear_program_bytes(self._handle(), C.byref(pb), C.byref(ab)) != 0:
+            raise LigError("lig_linear_program_bytes failed")
+        return int(pb.value), int(ab.value)
+
+    def _handle(self):
+        if not self.h:
+            raise LigError("the linear program has been released")
+        return self.h
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
 
 
 class ProofInfo(C.Structure):
@@ -292,6 +339,15 @@ def load_library():
     L.lig_shard_rows_set_linear.argtypes = [vp, C.POINTER(LinearSystem)]
     L.lig_shard_rows_linear_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.lig_linear_shard_count.argtypes = [C.POINTER(LinearSystem), vp, u64, u32, u32, u32, C.POINTER(u64), C.POINTER(u64)]
+    L.lig_linear_prepare.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, C.POINTER(vp)]
+    L.lig_linear_program_release.argtypes = [vp]
+    L.lig_linear_program_release.restype = None
+    L.lig_linear_program_bytes.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.lig_rows_attach_linear.argtypes = [vp, vp]
+    L.lig_rows_verify_attach_linear.argtypes = [vp, vp]
+    L.lig_rows_set_linear_values.argtypes = [vp, vp, u64]
+    L.lig_rows_verify_set_linear_values.argtypes = [vp, vp, u64]
+    L.lig_linear_program_form.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     return L
 
 
@@ -878,6 +934,43 @@ class Context:
         kb = np.frombuffer(bytes(key), dtype=np.uint8).copy()
         cs = np.zeros(32, dtype=np.uint8)
         self.check(self.L.lig_linear_form(self.h, C.byref(system), kinds.ctypes.data if len(kinds) else None, len(kinds), _hptr(kb), out, _hptr(cs)))
+        return cs.tobytes()
+
+    # ---- prepared linear systems: one LinearProgram for many proofs, verifications and contexts
+    def linear_prepare(self, system, kinds, rows=None):
+        """lig_linear_prepare -> LinearProgram (the caller's reference: release() it, or use it in a `with` block)"""
+        kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+        rows = len(kinds) if rows is None else int(rows)
+        if rows > len(kinds):
+            raise ValueError("linear_prepare: %d rows but %d kinds" % (rows, len(kinds)))
+        h = C.c_void_p()
+        self.check(self.L.lig_linear_prepare(self.h, C.byref(system), kinds.ctypes.data if len(kinds) else None, rows, C.byref(h)))
+        return LinearProgram(self.L, h)
+
+    def rows_attach_linear(self, trace, program):
+        """lig_rows_attach_linear: rows_set_linear with a prepared LinearProgram; None detaches"""
+        self.check(self.L.lig_rows_attach_linear(trace, program._handle() if program is not None else None))
+
+    def rows_verify_attach_linear(self, vtrace, program):
+        self.check(self.L.lig_rows_verify_attach_linear(vtrace, program._handle() if program is not None else None))
+
+    def rows_set_linear_values(self, trace, coefs):
+        """lig_rows_set_linear_values: this trace's values of the coefficient table (integers or (n, 8) uint32); None: the program's own"""
+        tab = coef_table(coefs) if coefs is not None else None
+        self.check(self.L.lig_rows_set_linear_values(trace, _hptr(tab) if tab is not None and len(tab) else None, len(tab) if tab is not None else 0))
+
+    def rows_verify_set_linear_values(self, vtrace, coefs):
+        tab = coef_table(coefs) if coefs is not None else None
+        self.check(self.L.lig_rows_verify_set_linear_values(vtrace, _hptr(tab) if tab is not None and len(tab) else None, len(tab) if tab is not None else 0))
+
+    def linear_program_form(self, program, key, out, coefs=None):
+        """lig_linear_program_form: linear_form without the prepare; coefs: a table of values for this call (None: the program's)
+        -> the constant (32 bytes)"""
+        kb = np.frombuffer(bytes(key), dtype=np.uint8).copy()
+        cs = np.zeros(32, dtype=np.uint8)
+        tab = coef_table(coefs) if coefs is not None else None
+        self.check(self.L.lig_linear_program_form(self.h, program._handle(), _hptr(kb), _hptr(tab) if tab is not None and len(tab) else None,
+                                                  len(tab) if tab is not None else 0, out, _hptr(cs)))
         return cs.tobytes()
 
     def vtrace_destroy(self, vtrace):

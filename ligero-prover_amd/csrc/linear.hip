@@ -22,6 +22,10 @@
 // Field arithmetic: canonical 8 x u32 (fr.hpp).  A term costs one 256-bit modular add (~50 VALU instructions) against a random
 // 32-byte gather from a vector that does not fit the last-level cache at 2^24 constraints: the pass is bound by the gather, not by
 // VALU, so the 29-bit-limb forms of fr29.hpp would buy nothing here.
+// Ownership: what the prepare makes is a lig_linear_program -- immutable once lig_linear_prepare returns,
+// reference counted, bound to a device and (l, k), read by any number of traces of any context at once.  What one user of it writes
+// per proof is a lig_linear, the ATTACHMENT: r, the heavy / constant partial sums, the pinned constant, and the Montgomery copy of a
+// coefficient table that overrides the program's own (lig_rows_set_linear_values: k_lin_coefs_mont converts it on the device).
 // One rank of a sharded trace (lig_shard_rows_set_linear) keeps the terms of its own rows and samples only the
 // constraints those need: the k_lin_shard_* kernels of the prepare phase below, k_rng_fill_indexed (aes.hip) in the form phase.
 #include <cstring>
@@ -188,11 +192,21 @@ __global__ void __launch_bounds__(LIN_WG) k_lin_const_fin(const fr* __restrict__
     acc = lin_block_sum(acc, sh);
     if (threadIdx.x == 0) fr_store(out, NEGATE ? fr_neg(acc) : acc);
 }
+// per-proof coefficient table (lig_rows_set_linear_values): canonical -> Montgomery form in place, one lane per entry, a * R^2 / R = a R;
+// 16-byte loads and stores (fr_load / fr_store), no LDS, no atomics; the host has checked every entry < p
+static constexpr uint32_t COEFS_MAX_BLOCKS = 1024;
+__global__ void __launch_bounds__(LIN_WG) k_lin_coefs_mont(fr* __restrict__ tab, uint64_t n) {
+    const fr r2 = fr_const(FR_R2);
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG) fr_store(tab + i, fr_montmul(fr_load(tab + i), r2));
+}
 }  // namespace lig
 
-// a linear system on the device, regrouped by slot (lig_internal_linear_create)
-struct lig_linear {
-    lig_ctx* c = nullptr;
+// a linear system on the device, regrouped by slot (lig_linear_prepare): nothing writes its device memory once the prepare has returned
+struct lig_linear_program {
+    mutable std::atomic<uint32_t> refs{1};
+    int device = 0;
+    std::vector<uint8_t> kinds;         // the row kinds it was checked against, LIG_ROW_DRAW_PAD masked off (empty: one rank of a sharded trace)
+    size_t dev_bytes = 0;               // device memory it holds
     uint32_t l = 0, k = 0;
     uint64_t rows = 0, n_constraints = 0, n_terms = 0, n_rhs = 0, n_coefs = 0, first_random = 0;
     uint32_t n_slots = 0, n_heavy = 0, n_trows = 0;
@@ -202,15 +216,24 @@ struct lig_linear {
     uint32_t* rhs_c = nullptr; uint32_t* rhs_coef = nullptr;
     uint32_t* heavy = nullptr;          // slots with more than HEAVY_MIN terms, ascending
     uint32_t* trows = nullptr;          // rows with at least one term, ascending
-    fr* r = nullptr;                    // n_constraints stream elements (per proof); one rank of a sharded trace: n_need
     // one rank of a sharded trace (lig_internal_linear_create_shard): rows / n_slots / trows / zero_runs are LOCAL, n_terms = the terms kept,
     // n_rhs = the rank's slice of the right-hand sides, ent[].x and rhs_c[] index r through the need list
     bool sharded = false;
     uint32_t* need = nullptr;           // n_need constraint numbers, ascending: r[i] = stream element first_random + need[i]
     uint64_t n_need = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> zero_runs;      // (first row, rows) no term touches
+};
+// one user of a program (a trace, a verifier trace, one lig_linear_program_form call): holds a reference and everything a form writes
+struct lig_linear {
+    lig_ctx* c = nullptr;
+    const lig_linear_program* P = nullptr;
+    fr* r = nullptr;                    // n_constraints stream elements (per proof); one rank of a sharded trace: n_need
     fr* part = nullptr;                 // n_heavy x HEAVY_PARTS | CONST_BLOCKS | the constant
     uint8_t* h_const = nullptr;         // pinned, 32 bytes: the constant of the last form
-    std::vector<std::pair<uint64_t, uint64_t>> zero_runs;      // (first row, rows) no term touches
+    const fr* coef = nullptr;           // the table the form kernels read: P->coef_mont, or vals
+    fr* vals = nullptr;                 // lig_rows_set_linear_values: n_coefs elements, Montgomery form once k_lin_coefs_mont has run
+    uint8_t* h_vals = nullptr;          // pinned staging of the canonical table: the caller's memory is free when set_values returns
+    hipEvent_t ev_vals = nullptr;       // the copy out of h_vals has finished
 };
 
 static bool lin_coef_ok(uint32_t coef, uint64_t n_coefs) { return coef == LIG_COEF_ONE || coef == LIG_COEF_NEG_ONE || coef < n_coefs; }
@@ -239,22 +262,37 @@ extern "C" int lig_linear_check(const lig_linear_system* sys, const uint8_t* kin
     return LIG_OK;
 }
 
+static void linear_program_retain(const lig_linear_program* P) { P->refs.fetch_add(1, std::memory_order_relaxed); }
+// the last reference frees the device memory; every attachment has drained its own streams before it drops its reference
+// (lig_internal_linear_destroy), so nothing reads the program any more
+static void linear_program_release(const lig_linear_program* P) {
+    if (!P || P->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(P->device);
+    for (void* p : {(void*)P->begin, (void*)P->ent, (void*)P->coef_mont, (void*)P->rhs_c, (void*)P->rhs_coef, (void*)P->heavy, (void*)P->trows, (void*)P->need})
+        (void)hipFree(p);
+    if (prev >= 0 && prev != P->device) (void)hipSetDevice(prev);
+    delete P;
+}
 void lig_internal_linear_destroy(lig_linear* L) {
     if (!L) return;
     (void)hipSetDevice(L->c->device);
     for (hipStream_t st : {L->c->stream, L->c->stream2}) if (st) (void)hipStreamSynchronize(st);
-    for (void* p : {(void*)L->begin, (void*)L->ent, (void*)L->coef_mont, (void*)L->rhs_c, (void*)L->rhs_coef, (void*)L->heavy, (void*)L->trows, (void*)L->r, (void*)L->part, (void*)L->need})
-        (void)hipFree(p);
+    for (void* p : {(void*)L->r, (void*)L->part, (void*)L->vals}) (void)hipFree(p);
     (void)hipHostFree(L->h_const);
+    (void)hipHostFree(L->h_vals);
+    if (L->ev_vals) (void)hipEventDestroy(L->ev_vals);
+    linear_program_release(L->P);
     delete L;
 }
 
 static uint32_t lin_grid(uint64_t items) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + lig::LIN_WG - 1) / lig::LIN_WG, 1), 65535); }
 
-// the end of both prepares: heavy slots sorted, touched rows listed, runs of untouched rows, the partial-sum scratch
-static int linear_prepare_lists(lig_ctx* c, lig_linear* L, const uint8_t* d_touched, const uint32_t* d_nheavy, uint32_t heavy_cap) {
+// the end of both prepares: heavy slots sorted, touched rows listed, runs of untouched rows
+static int linear_prepare_lists(lig_ctx* c, lig_linear_program* L, const uint8_t* d_touched, const uint32_t* d_nheavy, uint32_t heavy_cap) {
     hipStream_t s = c->stream;
-    auto dmalloc = [&](void** p, size_t bytes) -> int { HIP_TRY(c, hipMalloc(p, bytes ? bytes : 16)); return LIG_OK; };
+    auto dmalloc = [&](void** p, size_t bytes) -> int { HIP_TRY(c, hipMalloc(p, bytes ? bytes : 16)); L->dev_bytes += bytes ? bytes : 16; return LIG_OK; };
     std::vector<uint8_t> touched(L->rows);
     uint32_t n_heavy = 0;
     if (L->rows) HIP_TRY(c, hipMemcpyAsync(touched.data(), d_touched, L->rows, hipMemcpyDeviceToHost, s));
@@ -279,24 +317,21 @@ static int linear_prepare_lists(lig_ctx* c, lig_linear* L, const uint8_t* d_touc
     L->n_trows = (uint32_t)trows.size();
     TRY(dmalloc((void**)&L->trows, trows.size() * 4));
     if (!trows.empty()) HIP_TRY(c, hipMemcpy(L->trows, trows.data(), trows.size() * 4, hipMemcpyHostToDevice));
-    TRY(dmalloc((void**)&L->part, ((size_t)n_heavy * lig::HEAVY_PARTS + lig::CONST_BLOCKS + 1) * 32));
     return LIG_OK;
 }
 
-static int linear_prepare(lig_ctx* c, const lig_linear_system* sys, lig_linear* L) {
+static int linear_prepare(lig_ctx* c, const lig_linear_system* sys, lig_linear_program* L) {
     hipStream_t s = c->stream;
     const uint32_t S = L->n_slots, NT = (uint32_t)L->n_terms, NC = (uint32_t)L->n_constraints;
     auto dmalloc = [&](void** p, size_t bytes) -> int { HIP_TRY(c, hipMalloc(p, bytes ? bytes : 16)); return LIG_OK; };
-    TRY(dmalloc((void**)&L->begin, ((size_t)S + 1) * 4));
-    TRY(dmalloc((void**)&L->ent, (size_t)NT * sizeof(uint2)));
-    TRY(dmalloc((void**)&L->coef_mont, L->n_coefs * 32));
-    TRY(dmalloc((void**)&L->rhs_c, L->n_rhs * 4));
-    TRY(dmalloc((void**)&L->rhs_coef, L->n_rhs * 4));
-    TRY(dmalloc((void**)&L->r, L->n_constraints * 32));
-    HIP_TRY(c, hipHostMalloc((void**)&L->h_const, 32, hipHostMallocDefault));
-    std::memset(L->h_const, 0, 32);
+    auto keep = [&](void** p, size_t bytes) -> int { TRY(dmalloc(p, bytes)); L->dev_bytes += bytes ? bytes : 16; return LIG_OK; };      // memory of the program
+    TRY(keep((void**)&L->begin, ((size_t)S + 1) * 4));
+    TRY(keep((void**)&L->ent, (size_t)NT * sizeof(uint2)));
+    TRY(keep((void**)&L->coef_mont, L->n_coefs * 32));
+    TRY(keep((void**)&L->rhs_c, L->n_rhs * 4));
+    TRY(keep((void**)&L->rhs_coef, L->n_rhs * 4));
     const uint32_t heavy_cap = NT / (lig::HEAVY_MIN + 1) + 1;
-    TRY(dmalloc((void**)&L->heavy, (size_t)heavy_cap * 4));
+    TRY(keep((void**)&L->heavy, (size_t)heavy_cap * 4));
     // scratch of this call only
     lig_lin_term* d_terms = nullptr; uint32_t *d_tb = nullptr, *d_cursor = nullptr, *d_count = nullptr, *d_nheavy = nullptr; uint8_t* d_touched = nullptr; void* d_scan = nullptr;
     struct Scratch { std::vector<void**> v; lig_ctx* c; ~Scratch() { (void)hipStreamSynchronize(c->stream); for (void** p : v) (void)hipFree(*p); } }
@@ -334,20 +369,19 @@ static int linear_prepare(lig_ctx* c, const lig_linear_system* sys, lig_linear* 
 
 // one rank of a sharded trace: local_of = global row -> local row (LIN_NOT_LOCAL: another rank's), rows_local = the rank's rows;
 // the rank's slice of the right-hand sides = entries [rhs_lo, rhs_hi)
-static int linear_prepare_shard(lig_ctx* c, const lig_linear_system* sys, lig_linear* L, const uint32_t* local_of, uint64_t rows_global, uint64_t rhs_lo,
+static int linear_prepare_shard(lig_ctx* c, const lig_linear_system* sys, lig_linear_program* L, const uint32_t* local_of, uint64_t rows_global, uint64_t rhs_lo,
                                 uint64_t rhs_hi) {
     hipStream_t s = c->stream;
     const uint32_t S = L->n_slots, NT = (uint32_t)sys->n_terms, NC = (uint32_t)L->n_constraints, NR = (uint32_t)(rhs_hi - rhs_lo);
     auto dmalloc = [&](void** p, size_t bytes) -> int { HIP_TRY(c, hipMalloc(p, bytes ? bytes : 16)); return LIG_OK; };
+    auto keep = [&](void** p, size_t bytes) -> int { TRY(dmalloc(p, bytes)); L->dev_bytes += bytes ? bytes : 16; return LIG_OK; };      // memory of the program
     L->n_rhs = NR;
-    TRY(dmalloc((void**)&L->begin, ((size_t)S + 1) * 4));
-    TRY(dmalloc((void**)&L->coef_mont, L->n_coefs * 32));
-    TRY(dmalloc((void**)&L->rhs_c, (size_t)NR * 4));
-    TRY(dmalloc((void**)&L->rhs_coef, (size_t)NR * 4));
-    HIP_TRY(c, hipHostMalloc((void**)&L->h_const, 32, hipHostMallocDefault));
-    std::memset(L->h_const, 0, 32);
+    TRY(keep((void**)&L->begin, ((size_t)S + 1) * 4));
+    TRY(keep((void**)&L->coef_mont, L->n_coefs * 32));
+    TRY(keep((void**)&L->rhs_c, (size_t)NR * 4));
+    TRY(keep((void**)&L->rhs_coef, (size_t)NR * 4));
     const uint32_t heavy_cap = NT / (lig::HEAVY_MIN + 1) + 1;
-    TRY(dmalloc((void**)&L->heavy, (size_t)heavy_cap * 4));
+    TRY(keep((void**)&L->heavy, (size_t)heavy_cap * 4));
     std::vector<H::Fr> cm(L->n_coefs);         // (declared before the guard below: it outlives the guard's synchronise, an async copy reads it)
     // scratch of this call only
     lig_lin_term* d_terms = nullptr; uint32_t *d_tb = nullptr, *d_cursor = nullptr, *d_count = nullptr, *d_nheavy = nullptr, *d_local = nullptr, *d_flag = nullptr, *d_compact = nullptr;
@@ -395,9 +429,8 @@ static int linear_prepare_shard(lig_ctx* c, const lig_linear_system* sys, lig_li
     HIP_TRY(c, hipStreamSynchronize(s));
     if (kept > NT || n_need > NC) FAIL(c, LIG_E_STATE, "linear system: sharded prepare counted more than the system holds");
     L->n_terms = kept; L->n_need = n_need;
-    TRY(dmalloc((void**)&L->ent, (size_t)kept * sizeof(uint2)));
-    TRY(dmalloc((void**)&L->need, (size_t)n_need * 4));
-    TRY(dmalloc((void**)&L->r, (size_t)n_need * 32));
+    TRY(keep((void**)&L->ent, (size_t)kept * sizeof(uint2)));
+    TRY(keep((void**)&L->need, (size_t)n_need * 4));
     if (NT) hipLaunchKernelGGL(lig::k_lin_shard_scatter, dim3(lin_grid(NT)), dim3(lig::LIN_WG), 0, s, d_terms, NT, d_tb, NC, L->l, d_local, d_compact, L->begin, d_cursor, L->ent);
     if (NC) hipLaunchKernelGGL(lig::k_lin_shard_need, dim3(lin_grid(NC)), dim3(lig::LIN_WG), 0, s, d_flag, d_compact, NC, L->need);
     if (NR) hipLaunchKernelGGL(lig::k_lin_shard_rhs, dim3(lin_grid(NR)), dim3(lig::LIN_WG), 0, s, L->rhs_c, NR, d_compact);
@@ -406,17 +439,82 @@ static int linear_prepare_shard(lig_ctx* c, const lig_linear_system* sys, lig_li
     return linear_prepare_lists(c, L, d_touched, d_nheavy, heavy_cap);
 }
 
-// check, upload, regroup by slot; synchronous (every pointer of *sys may be released when it returns)
-int lig_internal_linear_create(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, lig_linear** out) {
+// check, upload, regroup by slot; synchronous (every pointer of *sys may be released when it returns).  The caller owns one reference.
+int lig_internal_linear_prepare(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, lig_linear_program** out) {
     *out = nullptr;
     if (lig_linear_check(sys, kinds, rows, c->l) != LIG_OK) FAIL(c, LIG_E_ARG, "linear system: rejected by lig_linear_check");
-    lig_linear* L = new lig_linear();
-    L->c = c; L->l = c->l; L->k = c->k; L->rows = rows;
+    lig_linear_program* L = new lig_linear_program();
+    L->device = c->device; L->l = c->l; L->k = c->k; L->rows = rows;
+    L->kinds.resize(rows);
+    for (uint64_t r = 0; r < rows; r++) L->kinds[r] = kinds[r] & 0x7f;
     L->n_constraints = sys->n_constraints; L->n_terms = sys->n_terms; L->n_rhs = sys->n_rhs; L->n_coefs = sys->n_coefs; L->first_random = sys->first_random;
     L->n_slots = (uint32_t)(rows * c->l);
     const int rc = linear_prepare(c, sys, L);
-    if (rc != LIG_OK) { const std::string why = c->err; lig_internal_linear_destroy(L); c->err = why; return rc; }
+    if (rc != LIG_OK) { linear_program_release(L); return rc; }
     *out = L;
+    return LIG_OK;
+}
+// device memory of one attachment: the sampled elements, the partial sums (+ n_coefs x 32 once values are set)
+static size_t linear_r_bytes(const lig_linear_program* P) { return std::max<size_t>((size_t)(P->sharded ? P->n_need : P->n_constraints) * 32, 16); }
+static size_t linear_part_bytes(const lig_linear_program* P) { return ((size_t)P->n_heavy * lig::HEAVY_PARTS + lig::CONST_BLOCKS + 1) * 32; }
+// the per-proof buffers of one user of P on context c; holds a reference to P until lig_internal_linear_destroy
+int lig_internal_linear_attach(lig_ctx* c, const lig_linear_program* P, lig_linear** out) {
+    *out = nullptr;
+    lig_linear* L = new lig_linear();
+    L->c = c; L->P = P; L->coef = P->coef_mont;
+    linear_program_retain(P);
+    const size_t r_bytes = linear_r_bytes(P), part_bytes = linear_part_bytes(P);
+    hipError_t e = hipMalloc((void**)&L->r, r_bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&L->part, part_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&L->h_const, 32, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        lig_internal_linear_destroy(L);
+        FAIL(c, LIG_E_NOMEM, std::string("linear system: per-proof buffers: ") + hipGetErrorString(e));
+    }
+    std::memset(L->h_const, 0, 32);
+    *out = L;
+    return LIG_OK;
+}
+// what lig_rows_set_linear has always done: a program of its own, attached, the only reference held by the attachment
+int lig_internal_linear_create(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, lig_linear** out) {
+    *out = nullptr;
+    lig_linear_program* P = nullptr;
+    TRY(lig_internal_linear_prepare(c, sys, kinds, rows, &P));
+    const int rc = lig_internal_linear_attach(c, P, out);
+    linear_program_release(P);
+    return rc;
+}
+// does a trace of context c with these rows fit P?  (host only)
+bool lig_internal_linear_fits(const lig_ctx* c, const lig_linear_program* P, const uint8_t* kinds, uint64_t rows) {
+    if (P->sharded || c->device != P->device || c->l != P->l || c->k != P->k || rows != P->rows) return false;
+    for (uint64_t r = 0; r < rows; r++) if ((kinds[r] & 0x7f) != P->kinds[r]) return false;
+    return true;
+}
+// per-proof values of the coefficient table: host check, pinned copy, upload and k_lin_coefs_mont on `st` -- the stream the
+// attachment's forms run on, so a form queued later reads the converted table.  coefs == NULL: the program's own table again.
+int lig_internal_linear_set_values(lig_ctx* c, lig_linear* L, const uint8_t* coefs, uint64_t n_coefs, hipStream_t st) {
+    const lig_linear_program* P = L->P;
+    if (!coefs) { L->coef = P->coef_mont; return LIG_OK; }
+    if (n_coefs != P->n_coefs) FAIL(c, LIG_E_ARG, "linear values: n_coefs differs from the program's");
+    for (uint64_t i = 0; i < n_coefs; i++) {
+        H::Fr v;
+        std::memcpy(v.v, coefs + 32 * i, 32);
+        if (H::geq(v, H::P)) FAIL(c, LIG_E_ARG, "linear values: an entry is not reduced mod p");
+    }
+    if (!n_coefs) { L->coef = P->coef_mont; return LIG_OK; }
+    const size_t bytes = (size_t)n_coefs * 32;
+    if (!L->vals) HIP_TRY(c, hipMalloc((void**)&L->vals, bytes));
+    if (!L->h_vals) HIP_TRY(c, hipHostMalloc((void**)&L->h_vals, bytes, hipHostMallocDefault));
+    if (!L->ev_vals) HIP_TRY(c, hipEventCreateWithFlags(&L->ev_vals, hipEventDisableTiming));
+    else HIP_TRY(c, hipEventSynchronize(L->ev_vals));          // the copy of the previous table out of the staging buffer
+    std::memcpy(L->h_vals, coefs, bytes);
+    HIP_TRY(c, hipMemcpyAsync(L->vals, L->h_vals, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(L->ev_vals, st));
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_coefs + lig::LIN_WG - 1) / lig::LIN_WG, lig::COEFS_MAX_BLOCKS);
+    hipLaunchKernelGGL(lig::k_lin_coefs_mont, dim3(blocks), dim3(lig::LIN_WG), 0, st, L->vals, n_coefs);
+    HIP_TRY(c, hipGetLastError());
+    L->coef = L->vals;
     return LIG_OK;
 }
 
@@ -453,39 +551,40 @@ int lig_internal_linear_create_shard(lig_ctx* c, const lig_linear_system* sys, c
     std::vector<uint32_t> local_of;
     uint64_t lo, hi;
     linear_shard_share(sys, grow, rows, rank, world, local_of, lo, hi);
-    lig_linear* L = new lig_linear();
-    L->c = c; L->l = c->l; L->k = c->k; L->rows = grow.size(); L->sharded = true;
+    lig_linear_program* L = new lig_linear_program();      // the rank's own: it depends on the deal, nothing shares it
+    L->device = c->device; L->l = c->l; L->k = c->k; L->rows = grow.size(); L->sharded = true;
     L->n_constraints = sys->n_constraints; L->n_coefs = sys->n_coefs; L->first_random = sys->first_random;
     L->n_slots = (uint32_t)(grow.size() * c->l);
-    const int rc = linear_prepare_shard(c, sys, L, local_of.data(), rows, lo, hi);
-    if (rc != LIG_OK) { const std::string why = c->err; lig_internal_linear_destroy(L); c->err = why; return rc; }
-    *out = L;
-    return LIG_OK;
+    int rc = linear_prepare_shard(c, sys, L, local_of.data(), rows, lo, hi);
+    if (rc == LIG_OK) rc = lig_internal_linear_attach(c, L, out);
+    linear_program_release(L);
+    return rc;
 }
-void lig_internal_linear_stats(const lig_linear* L, uint64_t* local_terms, uint64_t* sampled) { *local_terms = L->n_terms; *sampled = L->sharded ? L->n_need : L->n_constraints; }
+void lig_internal_linear_stats(const lig_linear* L, uint64_t* local_terms, uint64_t* sampled) { *local_terms = L->P->n_terms; *sampled = L->P->sharded ? L->P->n_need : L->P->n_constraints; }
 // one rank of a sharded trace: the rank's sum of b_c r_c (NOT negated), one element of device memory, final once the form queued on its stream is
-const fr* lig_internal_linear_partial_dev(const lig_linear* L) { return L->part + (size_t)L->n_heavy * lig::HEAVY_PARTS + lig::CONST_BLOCKS; }
+const fr* lig_internal_linear_partial_dev(const lig_linear* L) { return L->part + (size_t)L->P->n_heavy * lig::HEAVY_PARTS + lig::CONST_BLOCKS; }
 uint8_t* lig_internal_linear_const_buf(lig_linear* L) { return L->h_const; }
 
 // enqueue on `st`: rands_dev (rows x k) <- the randomness matrix of the system for the stream whose round keys are in rk60_dev;
 // the constant lands in lig_internal_linear_const() once the work queued on `st` has been waited for.  One rank of a sharded trace: the
 // LOCAL rows x k matrix from the need-list long r (indexed sampler), and the rank's un-negated sum in lig_internal_linear_partial_dev()
-int lig_internal_linear_form(lig_ctx* c, lig_linear* L, const uint32_t* rk60_dev, fr* rands_dev, hipStream_t st) {
+int lig_internal_linear_form(lig_ctx* c, lig_linear* A, const uint32_t* rk60_dev, fr* rands_dev, hipStream_t st) {
+    const lig_linear_program* L = A->P;
     const size_t row_bytes = (size_t)L->k * 32;
     for (const auto& z : L->zero_runs) HIP_TRY(c, hipMemsetAsync(rands_dev + z.first * L->k, 0, z.second * row_bytes, st));
-    if (L->sharded) lig::launch_rng_fill_indexed(st, rk60_dev, L->first_random, L->need, L->r, L->n_need);
-    else lig::launch_rng_fill(st, rk60_dev, L->first_random, L->r, L->n_constraints);
-    fr* hpart = L->part; fr* cpart = L->part + (size_t)L->n_heavy * lig::HEAVY_PARTS; fr* cst = cpart + lig::CONST_BLOCKS;
+    if (L->sharded) lig::launch_rng_fill_indexed(st, rk60_dev, L->first_random, L->need, A->r, L->n_need);
+    else lig::launch_rng_fill(st, rk60_dev, L->first_random, A->r, L->n_constraints);
+    fr* hpart = A->part; fr* cpart = A->part + (size_t)L->n_heavy * lig::HEAVY_PARTS; fr* cst = cpart + lig::CONST_BLOCKS;
     if (L->n_trows) {
         const dim3 grid((L->k + lig::LIN_WG - 1) / lig::LIN_WG, std::min<uint32_t>(L->n_trows, 65535));
-        hipLaunchKernelGGL(lig::k_lin_form, grid, dim3(lig::LIN_WG), 0, st, L->trows, L->n_trows, L->l, L->k, L->begin, L->ent, L->r, L->coef_mont, rands_dev);
+        hipLaunchKernelGGL(lig::k_lin_form, grid, dim3(lig::LIN_WG), 0, st, L->trows, L->n_trows, L->l, L->k, L->begin, L->ent, A->r, A->coef, rands_dev);
     }
     if (L->n_heavy) {
-        hipLaunchKernelGGL(lig::k_lin_heavy_part, dim3(L->n_heavy, lig::HEAVY_PARTS), dim3(lig::LIN_WG), 0, st, L->heavy, L->begin, L->ent, L->r, L->coef_mont, hpart);
+        hipLaunchKernelGGL(lig::k_lin_heavy_part, dim3(L->n_heavy, lig::HEAVY_PARTS), dim3(lig::LIN_WG), 0, st, L->heavy, L->begin, L->ent, A->r, A->coef, hpart);
         hipLaunchKernelGGL(lig::k_lin_heavy_fin, dim3((L->n_heavy + lig::LIN_WG - 1) / lig::LIN_WG), dim3(lig::LIN_WG), 0, st, L->heavy, L->n_heavy, L->l, L->k, hpart, rands_dev);
     }
     const uint32_t cb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((L->n_rhs + lig::LIN_WG - 1) / lig::LIN_WG, 1), lig::CONST_BLOCKS);
-    hipLaunchKernelGGL(lig::k_lin_const_part, dim3(cb), dim3(lig::LIN_WG), 0, st, L->rhs_c, L->rhs_coef, (uint32_t)L->n_rhs, L->r, L->coef_mont, cpart);
+    hipLaunchKernelGGL(lig::k_lin_const_part, dim3(cb), dim3(lig::LIN_WG), 0, st, L->rhs_c, L->rhs_coef, (uint32_t)L->n_rhs, A->r, A->coef, cpart);
     if (L->sharded) {
         hipLaunchKernelGGL(lig::k_lin_const_fin<false>, dim3(1), dim3(lig::LIN_WG), 0, st, cpart, cb, cst);
         HIP_TRY(c, hipGetLastError());
@@ -493,24 +592,53 @@ int lig_internal_linear_form(lig_ctx* c, lig_linear* L, const uint32_t* rk60_dev
     }
     hipLaunchKernelGGL(lig::k_lin_const_fin<true>, dim3(1), dim3(lig::LIN_WG), 0, st, cpart, cb, cst);
     HIP_TRY(c, hipGetLastError());
-    return lig_internal_download(c, L->h_const, cst, 32, st);
+    return lig_internal_download(c, A->h_const, cst, 32, st);
 }
 const uint8_t* lig_internal_linear_const(const lig_linear* L) { return L->h_const; }
 
+// key -> round keys -> form on the context stream, waited for; `A` is destroyed whatever happens
+static int linear_form_once(lig_ctx* c, lig_linear* A, const uint8_t key32[32], void* rands_dev, uint8_t const_sum[32], const char* who) {
+    uint32_t rk[60];
+    lig::aes256_expand_host(key32, rk);
+    int rc = lig_internal_upload_small(c, c->rk_dev, rk, sizeof rk, c->stream);
+    if (rc == LIG_OK) rc = lig_internal_linear_form(c, A, c->rk_dev, (fr*)rands_dev, c->stream);
+    if (rc == LIG_OK && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = std::string(who) + ": stream synchronize failed"; rc = LIG_E_HIP; }
+    if (rc == LIG_OK) std::memcpy(const_sum, A->h_const, 32);
+    const std::string why = c->err;
+    lig_internal_linear_destroy(A);
+    c->err = why;
+    return rc;
+}
 extern "C" int lig_linear_form(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, const uint8_t key32[32], void* rands_dev,
                                uint8_t const_sum[32]) {
     CHECK_CTX(c);
     if (!key32 || !const_sum || (rows && !rands_dev)) return LIG_E_ARG;
     lig_linear* L = nullptr;
     TRY(lig_internal_linear_create(c, sys, kinds, rows, &L));
-    uint32_t rk[60];
-    lig::aes256_expand_host(key32, rk);
-    int rc = lig_internal_upload_small(c, c->rk_dev, rk, sizeof rk, c->stream);
-    if (rc == LIG_OK) rc = lig_internal_linear_form(c, L, c->rk_dev, (fr*)rands_dev, c->stream);
-    if (rc == LIG_OK && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "lig_linear_form: stream synchronize failed"; rc = LIG_E_HIP; }
-    if (rc == LIG_OK) std::memcpy(const_sum, L->h_const, 32);
-    const std::string why = c->err;
-    lig_internal_linear_destroy(L);
-    c->err = why;
-    return rc;
+    return linear_form_once(c, L, key32, rands_dev, const_sum, "lig_linear_form");
+}
+
+extern "C" int lig_linear_prepare(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, lig_linear_program** out) {
+    CHECK_CTX(c);
+    if (!out) return LIG_E_ARG;
+    return lig_internal_linear_prepare(c, sys, kinds, rows, out);
+}
+extern "C" void lig_linear_program_release(lig_linear_program* p) { linear_program_release(p); }
+extern "C" int lig_linear_program_bytes(const lig_linear_program* p, uint64_t* program_bytes, uint64_t* attachment_bytes) {
+    if (!p || !program_bytes || !attachment_bytes) return LIG_E_ARG;
+    *program_bytes = p->dev_bytes;
+    *attachment_bytes = linear_r_bytes(p) + linear_part_bytes(p);
+    return LIG_OK;
+}
+extern "C" int lig_linear_program_form(lig_ctx* c, const lig_linear_program* p, const uint8_t key32[32], const uint8_t* coefs, uint64_t n_coefs, void* rands_dev,
+                                       uint8_t const_sum[32]) {
+    CHECK_CTX(c);
+    if (!p || !key32 || !const_sum || (p->rows && !rands_dev)) return LIG_E_ARG;
+    if (p->sharded || c->device != p->device || c->l != p->l || c->k != p->k) FAIL(c, LIG_E_ARG, "lig_linear_program_form: the program was prepared for another device or another (l, k)");
+    if (coefs && n_coefs != p->n_coefs) FAIL(c, LIG_E_ARG, "lig_linear_program_form: n_coefs differs from the program's");
+    lig_linear* L = nullptr;
+    TRY(lig_internal_linear_attach(c, p, &L));
+    const int rc = lig_internal_linear_set_values(c, L, coefs, n_coefs, c->stream);
+    if (rc != LIG_OK) { const std::string why = c->err; lig_internal_linear_destroy(L); c->err = why; return rc; }
+    return linear_form_once(c, L, key32, rands_dev, const_sum, "lig_linear_program_form");
 }

@@ -1303,6 +1303,39 @@ int lig_rows_set_linear(lig_trace* T, const lig_linear_system* sys) {
     return LIG_OK;
 }
 
+int lig_rows_attach_linear(lig_trace* T, const lig_linear_program* p) {
+    if (!T) return LIG_E_ARG;
+    lig_ctx* c = T->c;
+    CHECK_CTX(c);
+    if (!T->from_rows || !(T->loaded || T->committed)) FAIL(c, LIG_E_STATE, "lig_rows_attach_linear: between lig_rows_begin and lig_rows_prove");
+    if (T->rands_pushed) FAIL(c, LIG_E_STATE, "lig_rows_attach_linear: randomness rows have already been pushed");
+    if (!p) {
+        lig_internal_linear_destroy(T->linear);
+        T->linear = nullptr;
+        return LIG_OK;
+    }
+    if (T->dense_rands) FAIL(c, LIG_E_ARG, "lig_rows_attach_linear: the job has dense_rands_per_row");
+    std::vector<uint8_t> kinds(T->R);
+    for (size_t r = 0; r < T->R; r++) kinds[r] = T->rows[r].kind;
+    if (!lig_internal_linear_fits(c, p, kinds.data(), T->R)) FAIL(c, LIG_E_ARG, "lig_rows_attach_linear: the program was prepared for another device, (l, k), row count or row kinds");
+    lig_linear* L = nullptr;
+    TRY(lig_internal_linear_attach(c, p, &L));
+    if (!T->rands_full) {
+        const hipError_t e = hipMalloc((void**)&T->rands_full, (T->R ? T->R : 1) * (size_t)c->k * 32);
+        if (e != hipSuccess) { lig_internal_linear_destroy(L); FAIL(c, LIG_E_NOMEM, std::string("lig_rows_attach_linear: randomness matrix: ") + hipGetErrorString(e)); }
+    }
+    lig_internal_linear_destroy(T->linear);
+    T->linear = L;
+    return LIG_OK;
+}
+int lig_rows_set_linear_values(lig_trace* T, const uint8_t* coefs, uint64_t n_coefs) {
+    if (!T) return LIG_E_ARG;
+    lig_ctx* c = T->c;
+    CHECK_CTX(c);
+    if (!T->from_rows || !T->linear) FAIL(c, LIG_E_STATE, "lig_rows_set_linear_values: no linear program is attached (lig_rows_attach_linear)");
+    return lig_internal_linear_set_values(c, T->linear, coefs, n_coefs, c->stream2);      // the stream lig_rows_prove forms on
+}
+
 int lig_rows_push_rands(lig_trace* T, uint64_t first_row, uint64_t n_rows, const void* host_rows) {
     return lig_rows_push_rands_sparse(T, first_row, n_rows, nullptr, host_rows);
 }

@@ -383,7 +383,15 @@ struct lig_tune {
 // a sparse linear system on the device (linear.hip; lig_hip.h: lig_linear_system): create = lig_linear_check + upload + regroup by
 // slot, synchronous on the context stream; form = enqueue on `st` the rows x k randomness matrix for the stream whose round keys are
 // in rk60_dev -- the constant (32 bytes, pinned host memory) is valid once the work queued on `st` has been waited for
+// Two objects (linear.hip): lig_linear_program = the regrouped structure, immutable after the prepare, reference counted, shared;
+// lig_linear = one user's ATTACHMENT to a program: a reference plus everything a form writes (r, partial sums, the pinned constant,
+// an overriding coefficient table).  create = prepare + attach + release: a program nobody else holds.
 struct lig_linear;
+int lig_internal_linear_prepare(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, lig_linear_program** out);
+int lig_internal_linear_attach(lig_ctx* c, const lig_linear_program* P, lig_linear** out);
+bool lig_internal_linear_fits(const lig_ctx* c, const lig_linear_program* P, const uint8_t* kinds, uint64_t rows);      // device, l, k, rows, kinds (host only)
+// canonical table -> the attachment's own Montgomery copy, enqueued on `st` (the stream its forms run on); NULL: the program's table
+int lig_internal_linear_set_values(lig_ctx* c, lig_linear* L, const uint8_t* coefs, uint64_t n_coefs, hipStream_t st);
 int lig_internal_linear_create(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, lig_linear** out);
 void lig_internal_linear_destroy(lig_linear* L);
 int lig_internal_linear_form(lig_ctx* c, lig_linear* L, const uint32_t* rk60_dev, fr* rands_dev, hipStream_t st);

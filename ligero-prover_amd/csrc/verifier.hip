@@ -411,6 +411,29 @@ int lig_rows_verify_set_linear(lig_vtrace* V, const lig_linear_system* sys) {
     return LIG_OK;
 }
 
+int lig_rows_verify_attach_linear(lig_vtrace* V, const lig_linear_program* p) {
+    if (!V) return LIG_E_ARG;
+    lig_ctx* c = V->c;
+    CHECK_CTX(c);
+    lig_linear* L = nullptr;
+    if (p) {
+        std::vector<uint8_t> kinds(V->rows.size());
+        for (size_t r = 0; r < kinds.size(); r++) kinds[r] = V->rows[r].kind;
+        if (!lig_internal_linear_fits(c, p, kinds.data(), kinds.size())) FAIL(c, LIG_E_ARG, "lig_rows_verify_attach_linear: the program was prepared for another device, (l, k), row count or row kinds");
+        TRY(lig_internal_linear_attach(c, p, &L));
+    }
+    lig_internal_linear_destroy(V->linear);
+    V->linear = L;
+    return LIG_OK;
+}
+int lig_rows_verify_set_linear_values(lig_vtrace* V, const uint8_t* coefs, uint64_t n_coefs) {
+    if (!V) return LIG_E_ARG;
+    lig_ctx* c = V->c;
+    CHECK_CTX(c);
+    if (!V->linear) FAIL(c, LIG_E_STATE, "lig_rows_verify_set_linear_values: no linear program is attached (lig_rows_verify_attach_linear)");
+    return lig_internal_linear_set_values(c, V->linear, coefs, n_coefs, c->stream);      // the stream lig_rows_verify_finish forms on
+}
+
 // with a linear system: the randomness matrix and the constant are formed from the public structure and the re-derived stage-1 seed
 static int verify_finish_linear(lig_vtrace* V, const uint8_t* const_sum, lig_verify_info* out) {
     lig_ctx* c = V->c;
