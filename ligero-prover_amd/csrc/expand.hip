@@ -103,3 +103,15 @@ void launch_expand_rows(hipStream_t s, const uint8_t* packed, const uint64_t* of
     hipLaunchKernelGGL(k_expand_product, pgrid, dim3(EXPAND_WG), 0, s, packed, off_dev, widths_dev, prod_rows_dev, (uint32_t)n_prod, l, k, out);
 }
 }  // namespace lig
+
+int lig_internal_upload_narrow_plan(lig_ctx* c, const lig::NarrowPlan& plan, uint64_t** src_off_dev, uint8_t** widths_dev, ProductRows* prod) {
+    HIP_TRY(c, hipMalloc((void**)src_off_dev, plan.src_off.size() * sizeof(uint64_t)));
+    HIP_TRY(c, hipMalloc((void**)widths_dev, plan.widths.size()));
+    HIP_TRY(c, hipMemcpy(*src_off_dev, plan.src_off.data(), plan.src_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(*widths_dev, plan.widths.data(), plan.widths.size(), hipMemcpyHostToDevice));
+    prod->rows = plan.prod_rows;
+    if (prod->rows.empty()) return LIG_OK;
+    HIP_TRY(c, hipMalloc((void**)&prod->dev, prod->rows.size() * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemcpy(prod->dev, prod->rows.data(), prod->rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return LIG_OK;
+}

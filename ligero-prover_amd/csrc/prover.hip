@@ -30,9 +30,7 @@ struct lig_trace {
     bool dense_rands = false;           // lig_rows_job.dense_rands_per_row given: randomness rows may be generated here
     fr* msgs_alt = nullptr;             // second message matrix: the next trace is uploaded while the current one is proved
     bool alt_pending = false;           // the rows for the next commit are (arriving) in msgs_alt
-    uint8_t encoding_seed[32] = {0}, program_hash[32] = {0}, ih[32] = {0};
-    int64_t generated_at = 0;
-    char version[17] = {0};
+    JobHeader hdr;
     std::vector<RowDesc> rows;          // committed non-mask rows in commit order
     std::vector<PadRun> pad_runs;       // pads drawn at commit time (pad_encoding_random), runs of consecutive rows
     uint64_t mask_pos = 0;              // encoding-stream position of the first mask element
@@ -55,11 +53,10 @@ struct lig_trace {
     std::atomic<int> up_abort{0};       // a failed lig_rows_prove: the uploader drops the randomness-row copies it still holds
     std::atomic<int> up_pending{0};     // chunk copies of this trace the uploader thread still has to make
     std::atomic<int> up_failed{0}, rand_pending{0}, rand_failed{0};      // hipError_t of a chunk copy that failed (the chunk is published all the same: no stream may hang)   -- rand_*: the same for randomness-row uploads, kept apart: lig_rows_prove must not wait for (or swallow the error of) the NEXT trace's witness prefetch
-    // narrow row format (lig_rows_job.elem_bytes): packed byte offset of every row (+1 entry), the widths, the device staging
+    // narrow row format (lig_rows_job.elem_bytes): packed byte offset of every row (+1 entry), the device staging
     // area the packed rows are uploaded to (expanded into `msgs` chunk by chunk in stage 1)
     bool narrow = false;
     std::vector<uint64_t> src_off;
-    std::vector<uint8_t> widths;
     uint64_t* src_off_dev = nullptr; uint8_t* widths_dev = nullptr; uint8_t* packed_dev = nullptr;
     ProductRows prod;                   // derived rows (LIG_ELEM_PRODUCT): formed next to the expansion from the packed x and y rows
     lig_proof_info info1;               // stage-1 results kept between lig_rows_commit and lig_rows_prove
@@ -235,6 +232,20 @@ int lig_internal_synth_witness(lig_ctx* c, const uint8_t witness_key[32], const 
     return LIG_OK;
 }
 
+int lig_internal_form_mask_rows(lig_ctx* c, hipStream_t s, uint64_t epos, fr* mask, fr* dots) {
+    const uint32_t l = c->l, n = c->n, pad = c->k - l;
+    HIP_TRY(c, hipMemsetAsync(mask, 0, 3 * (size_t)n * 32, s));
+    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mask, 1, l, 0, 0, 1, 0); epos += l;               // code mask: l randoms, zeros to k
+    fr* mlin = mask + n; fr* mquad = mask + 2 * (size_t)n;
+    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mlin, 1, l - 1, 0, 1, 2, 0); epos += l - 1;       // (0, r) x (l-1)
+    // last odd slot = -(sum of the others) (witness_manager.hpp:283-297), on the device: no host round trip
+    lig::launch_sum_elems(s, mlin + 1, l - 1, 2, dots, mlin + 2 * (size_t)(l - 1) + 1);
+    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mlin, 1, 2 * pad, 0, 2 * l, 1, 0); epos += 2 * pad;
+    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mquad, 1, l, 0, 1, 2, 0); epos += l;              // (0, r) x l
+    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mquad, 1, 2 * pad, 0, 2 * l, 1, 0);
+    return LIG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // shared by lig_synth_* and lig_rows_*: buffers of a trace whose row plan (T->rows) is known
 static int trace_alloc(lig_ctx* c, lig_trace* T) {
@@ -283,20 +294,6 @@ static int trace_alloc(lig_ctx* c, lig_trace* T) {
     return LIG_OK;
 }
 
-// instance_hash over arg0 = "Ligero\0" and the public arguments (src/webgpu_prover.cpp:110-168)
-static bool instance_hash_of(const uint8_t* args, const uint64_t* lens, uint64_t n_args, uint8_t out[32]) {
-    if (n_args && (!args || !lens)) return false;
-    std::memset(out, 0, 32);
-    Sha256().add(out, 32).add("Ligero", 7).finish(out);
-    for (uint64_t i = 0; i < n_args; i++) {
-        uint8_t prev[32];
-        std::memcpy(prev, out, 32);
-        Sha256().add(prev, 32).add(args, lens[i]).finish(out);
-        args += lens[i];
-    }
-    return true;
-}
-
 // ================= stage 1: row forming (pads + masks from the encoding stream), encode, column hash, Merkle root
 static int prove_stage1(lig_trace* T, lig_proof_info* info, const std::function<void(const char*)>& mark) {
     lig_ctx* c = T->c;
@@ -304,25 +301,15 @@ static int prove_stage1(lig_trace* T, lig_proof_info* info, const std::function<
     const size_t k3 = 3 * (size_t)k;
     hipStream_t s = c->stream;
     uint32_t rk[60];
-    lig::aes256_expand_host(T->encoding_seed, rk);
+    lig::aes256_expand_host(T->hdr.encoding_seed, rk);
     TRY(lig_internal_upload_small(c, c->rk_dev, rk, sizeof rk, s));
     const bool streamed = T->host_msgs != nullptr;       // rows arrive chunk by chunk: their pads are drawn per chunk below
     if (!streamed)
         for (const PadRun& pr : T->pad_runs)             // pad_encoding_random of every row that draws at commit time
             lig::launch_rng_fill_rows(s, c->rk_dev, pr.pos, T->msgs + pr.first * (size_t)k, pr.count, pad, k, l, 1, pad);
     mark("  pads");
-    uint64_t epos = T->mask_pos;
-    fr* mask = T->maskcw;                                                                           // the 3 mask rows are formed in place
-    HIP_TRY(c, hipMemsetAsync(mask, 0, 3 * (size_t)n * 32, s));
-    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mask, 1, l, 0, 0, 1, 0); epos += l;               // code mask: l randoms, zeros to k
-    fr* mlin = mask + n; fr* mquad = mask + 2 * (size_t)n;
-    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mlin, 1, l - 1, 0, 1, 2, 0); epos += l - 1;       // (0, r) x (l-1)
-    // last odd slot = -(sum of the others) (witness_manager.hpp:283-297), on the device: no host round trip
-    lig::launch_sum_elems(s, mlin + 1, l - 1, 2, T->dots, mlin + 2 * (size_t)(l - 1) + 1);
-    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mlin, 1, 2 * pad, 0, 2 * l, 1, 0); epos += 2 * pad;
-    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mquad, 1, l, 0, 1, 2, 0); epos += l;              // (0, r) x l
-    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mquad, 1, 2 * pad, 0, 2 * l, 1, 0); epos += 2 * pad;
-
+    fr* mask = T->maskcw; fr* mlin = mask + n;                                                      // the 3 mask rows are formed in place
+    TRY(lig_internal_form_mask_rows(c, s, T->mask_pos, mask, T->dots));
     mark("row forming (pads, masks)");
     // Encode chunk by chunk on the main stream; the column hash of chunk b runs on the side stream while chunk
     // b+1 is being encoded (the hash has only n = 32768 lanes of parallelism -- 512 waves -- and would otherwise
@@ -425,7 +412,7 @@ static int prove_stage1(lig_trace* T, lig_proof_info* info, const std::function<
     }
     std::memcpy(info->root, T->h_nodes, 32);
     TRY(lig_internal_download(c, T->h_nodes, T->nodes, lig_merkle_nodes(n) * 32, s));      // ... the tree for the decommitment (stage 3) under stage 2
-    Sha256().add("LigetronStage1", 15).add(info->root, 32).add(T->ih, 32).finish(info->stage1_seed);
+    stage1_seed(info->root, T->hdr.ih, info->stage1_seed);
     mark("merkle + seed");
     return LIG_OK;
 }
@@ -535,17 +522,7 @@ static int prove_stage23(lig_trace* T, const RandSource& rs, const uint8_t* cons
         return LIG_OK;
     };
     {   // coefficients: one code-stream draw per row, one quadratic-stream draw per triple (the sampler's fused pass reads them)
-        std::vector<H::Fr> rc, rq;
-        FieldStream code_s(info->stage1_seed), quad_s(info->stage1_seed);
-        size_t n_code = 0;
-        for (size_t r = 0; r < R; r++) n_code += has_code_check(T->rows[r].kind);
-        code_s.next(n_code, rc);
-        quad_s.next(NT, rq);
-        std::vector<lig::f29s> coef(R + 2 * NT + 1);
-        std::memset(coef.data(), 0, coef.size() * sizeof(lig::f29s));
-        const H::Fr R261sq = H::mul(R261, R261);
-        for (size_t r = 0, ci = 0; r < R; r++) if (has_code_check(T->rows[r].kind)) coef[r] = to_f29s_host(rc[ci++], R261);
-        for (size_t i = 0; i < NT; i++) { coef[R + i] = to_f29s_host(rq[i], R261sq); coef[R + NT + i] = to_f29s_host(rq[i], R261); }
+        const std::vector<lig::f29s> coef = coef_table(draw_coefficients(info->stage1_seed, T->rows), nullptr, nullptr);
         TRY(lig_internal_upload_small(c, T->coef_dev, coef.data(), coef.size() * sizeof(lig::f29s), s));
     }
     HIP_TRY(c, hipEventRecord(c->ev_fork, s));            // the side stream starts after the key / coefficient uploads and the memsets above
@@ -668,23 +645,14 @@ static int prove_stage23(lig_trace* T, const RandSource& rs, const uint8_t* cons
     const size_t n_nodes = lig_merkle_nodes(n);
     const std::vector<uint8_t> sib = decommit(T->h_nodes, (n_nodes + 1) / 2, idx);
     const size_t smp_bytes = (R + 3) * (size_t)t * 32;
-    const EnvelopeLayout lay = write_envelope(T->h_proof, T->h_proof_cap, T->version, T->program_hash, T->generated_at, k, n, t,
+    const EnvelopeLayout lay = write_envelope(T->h_proof, T->h_proof_cap, T->hdr.version, T->hdr.program_hash, T->hdr.generated_at, k, n, t,
                                               info->root, sib, idx, nullptr, smp_bytes);       // framing only: the layout is known now
     if (lay.total > T->h_proof_cap) FAIL(c, LIG_E_NOMEM, "proof buffer too small");
     TRY(lig_internal_download(c, T->h_proof + lay.samples_off, T->samples, smp_bytes, s));   // opened columns land in place (any byte offset)
     for (int a3 = 0; a3 < 3; a3++) std::memcpy(T->h_proof + lay.vec_off[a3], enc + (size_t)a3 * vec_bytes, vec_bytes);     // 3 MiB, under the 13 MB download
     HIP_TRY(c, wait_event(c->ev_join));          // decoded accumulators are on the host
-    auto is_zero = [](const H::Fr& v) { return !(v.v[0] | v.v[1] | v.v[2] | v.v[3]); };
-    info->valid_code = 1;
-    for (uint32_t i = k; i < n; i++) if (!is_zero(dec[i])) info->valid_code = 0;
-    {
-        H::Fr a;
-        std::memcpy(a.v, info->const_sum, 32);
-        for (uint32_t i = 0; i < l; i++) a = H::add(a, dec[(size_t)n + i]);
-        info->valid_linear = is_zero(a);
-    }
-    info->valid_quad = 1;
-    for (uint32_t i = 0; i < l; i++) if (!is_zero(dec[2 * (size_t)n + i])) info->valid_quad = 0;
+    const SelfCheck ok = self_check(dec, info->const_sum, l, k, n);
+    info->valid_code = ok.valid_code; info->valid_linear = ok.valid_linear; info->valid_quad = ok.valid_quad;
     HIP_TRY(c, wait_stream(s));
     *proof = T->h_proof;
     *proof_len = lay.total;
@@ -731,11 +699,7 @@ static int synth_prepare_impl(lig_ctx* c, const lig_synth_job* job, lig_trace* T
     if (l >= k || l < 2 || t > n || k - l < t) FAIL(c, LIG_E_ARG, "synthetic trace: need 2 <= l <= k - 192 (k - l random pads cover the 192 opened columns)");
     if (!plan_rows(*job, l, T->rows, T->n_init)) FAIL(c, LIG_E_ARG, "malformed batch program");
     if (T->n_init && k - l != 192) FAIL(c, LIG_E_ARG, "batch program: on_batch_init draws params::sample_size = 192 pads, k - l must be 192");
-    if (!instance_hash_of(job->public_args, job->public_arg_lens, job->n_public_args, T->ih)) FAIL(c, LIG_E_ARG, "public arguments: null pointer");
-    std::memcpy(T->encoding_seed, job->encoding_seed, 32);
-    std::memcpy(T->program_hash, job->program_hash, 32);
-    std::memcpy(T->version, job->version, 16);
-    T->generated_at = job->generated_at;
+    if (!fill_job_header(*job, T->hdr)) FAIL(c, LIG_E_ARG, "public arguments: null pointer");
     const size_t R = T->rows.size();
     for (T->RB = 0; T->RB < R && T->rows[T->RB].kind >= RK_INIT; T->RB++) {}
     TRY(trace_alloc(c, T));
@@ -1065,63 +1029,25 @@ static int rows_begin_impl(lig_ctx* c, const lig_rows_job* job, lig_trace* T) {
     const uint32_t l = c->l, k = c->k, n = c->n, t = 192, pad = k - l;
     if (l >= k || l < 2 || t > n || k - l < t) FAIL(c, LIG_E_ARG, "rows job: need 2 <= l <= k - 192");
     if (job->rows && (!job->kinds || !job->msgs)) FAIL(c, LIG_E_ARG, "rows job: null kinds / msgs");
-    if (!instance_hash_of(job->public_args, job->public_arg_lens, job->n_public_args, T->ih)) FAIL(c, LIG_E_ARG, "public arguments: null pointer");
-    std::memcpy(T->encoding_seed, job->encoding_seed, 32);
-    std::memcpy(T->program_hash, job->program_hash, 32);
-    std::memcpy(T->version, job->version, 16);
-    T->generated_at = job->generated_at;
+    if (!fill_job_header(*job, T->hdr)) FAIL(c, LIG_E_ARG, "public arguments: null pointer");
     T->from_rows = true;
     const size_t R = job->rows;
-    // row kinds: groups must be complete and consecutive; which kinds draw padding from the encoding stream at the time
-    // they are formed: linear rows and the rows of a quadratic triple (witness_manager.hpp:200-269), on_batch_init rows
-    // (nonbatch_context.hpp:497-510); bit / equal / batch-quadratic rows are copies of variables and draw nothing
-    T->rows.resize(R);
-    std::vector<uint8_t> draw(R, 0);
-    std::vector<uint64_t> pos(R + 1, 0);
-    for (size_t r = 0; r < R; r++) {
-        const uint8_t kd = job->kinds[r] & 0x7f;
-        if (kd > RK_BQZ) FAIL(c, LIG_E_ARG, "rows job: unknown row kind");
-        const bool first_of_3 = kd == 1 || kd == RK_BQX, first_of_2 = kd == RK_EQX;
-        if (first_of_3 && !(r + 2 < R && (job->kinds[r + 1] & 0x7f) == kd + 1 && (job->kinds[r + 2] & 0x7f) == kd + 2)) FAIL(c, LIG_E_ARG, "rows job: incomplete x,y,z triple");
-        if (first_of_2 && !(r + 1 < R && (job->kinds[r + 1] & 0x7f) == RK_EQY)) FAIL(c, LIG_E_ARG, "rows job: incomplete equality pair");
-        const bool follower = kd == 2 || kd == 3 || kd == RK_EQY || kd == RK_BQY || kd == RK_BQZ;
-        if (follower && !(r > 0 && (job->kinds[r - 1] & 0x7f) == kd - 1)) FAIL(c, LIG_E_ARG, "rows job: row of a group without its predecessor");
-        const bool draws = kd <= 3 || kd == RK_INIT;
-        // on_batch_init draws params::sample_size = 192 elements (nonbatch_context.hpp:497-510), the rows of witness_manager
-        // k - l; upstream the two are the same number (params.hpp:27-30).  Batch rows are only accepted in that geometry:
-        // otherwise the encoding stream would run out of step with the reference's
-        if (kd == RK_INIT && pad != 192) FAIL(c, LIG_E_ARG, "rows job: on_batch_init rows need k - l = 192 (params::sample_size)");
-        if ((job->kinds[r] & LIG_ROW_DRAW_PAD) && !draws) FAIL(c, LIG_E_ARG, "rows job: LIG_ROW_DRAW_PAD on a row kind that draws no padding upstream");
-        draw[r] = (job->kinds[r] & LIG_ROW_DRAW_PAD) ? 1 : 0;
-        pos[r + 1] = pos[r] + (draws ? pad : 0);
-        const uint32_t dense = job->dense_rands_per_row ? job->dense_rands_per_row[r] : 0;
-        if (dense > k || (dense && kd > 3)) FAIL(c, LIG_E_ARG, "rows job: dense_rands_per_row out of range or on a batch row");
-        T->rows[r] = RowDesc{kd, dense};
-    }
+    std::vector<uint8_t> draw;
+    std::vector<uint64_t> pos;
+    if (const char* why = lig::parse_row_kinds(*job, l, k, true, T->rows, draw, pos)) FAIL(c, LIG_E_ARG, std::string("rows job: ") + why);
     T->dense_rands = job->dense_rands_per_row != nullptr;
     T->mask_pos = pos[R];
-    if (job->elem_bytes) {            // the narrow row format
-        T->src_off.assign(R + 1, 0);
-        T->widths.assign(R ? R : 1, 32);
-        for (size_t r = 0; r < R; r++) {
-            const uint8_t w = job->elem_bytes[r] ? job->elem_bytes[r] : 32;
-            if (const char* why = lig::narrow_row_refusal(job->elem_bytes, r, T->rows[r].kind, draw[r] != 0, l, k)) FAIL(c, LIG_E_ARG, std::string("rows job: ") + why);
-            T->narrow = T->narrow || w != 32;          // (a derived row alone takes the packed path as well)
-            if (w == LIG_ELEM_PRODUCT) T->prod.rows.push_back((uint32_t)r);
-            T->widths[r] = w;
-            T->src_off[r + 1] = T->src_off[r] + lig::narrow_row_bytes(w, l, k);
-        }
+    lig::NarrowPlan np;
+    if (job->elem_bytes) {            // the narrow row format; every row is local
+        std::vector<size_t> all(R);
+        for (size_t r = 0; r < R; r++) all[r] = r;
+        if (const char* why = lig::plan_narrow_rows(job->elem_bytes, T->rows, draw, l, k, all, np)) FAIL(c, LIG_E_ARG, std::string("rows job: ") + why);
     }
+    T->narrow = np.packed;
     TRY(trace_alloc(c, T));
     if (T->narrow) {
-        HIP_TRY(c, hipMalloc((void**)&T->src_off_dev, (R + 1) * sizeof(uint64_t)));
-        HIP_TRY(c, hipMalloc((void**)&T->widths_dev, R));
-        HIP_TRY(c, hipMemcpy(T->src_off_dev, T->src_off.data(), (R + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(T->widths_dev, T->widths.data(), R, hipMemcpyHostToDevice));
-        if (!T->prod.rows.empty()) {
-            HIP_TRY(c, hipMalloc((void**)&T->prod.dev, T->prod.rows.size() * sizeof(uint32_t)));
-            HIP_TRY(c, hipMemcpy(T->prod.dev, T->prod.rows.data(), T->prod.rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
+        TRY(lig_internal_upload_narrow_plan(c, np, &T->src_off_dev, &T->widths_dev, &T->prod));
+        T->src_off = std::move(np.src_off);
         if (!job->msgs_on_device) HIP_TRY(c, hipMalloc((void**)&T->packed_dev, T->src_off[R] ? T->src_off[R] : 16));
     }
     // pad runs: consecutive flagged rows whose stream positions are consecutive, never straddling a stage-1 chunk
@@ -1429,7 +1355,7 @@ int lig_public_arg_bytes(int kind, const char* text, uint8_t* out, size_t cap, s
     return LIG_OK;
 }
 int lig_instance_hash(const uint8_t* args, const uint64_t* lens, size_t n_args, uint8_t out[32]) {
-    if (!out || !instance_hash_of(args, lens, n_args, out)) return LIG_E_ARG;
+    if (!out || !instance_hash(args, lens, n_args, out)) return LIG_E_ARG;
     return LIG_OK;
 }
 int lig_sample_columns(const uint8_t seed[32], uint32_t n, uint32_t t, uint32_t* out_sorted) {

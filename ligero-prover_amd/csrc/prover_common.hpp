@@ -1,6 +1,7 @@
 // prover_common.hpp -- host-side helpers shared by the prover, the sharded prover and the verifier: transcript hashing
-// and samplers (OpenSSL), column sampling, Merkle decommitment, the protobuf envelope writer, the row plan of a job and
-// the batch-program interpreter.  Everything here is internal to liblig_hip.so.
+// and samplers (OpenSSL), the instance hash, the stage-1 seed, the coefficient draws and the self-check of stage 2, column
+// sampling, Merkle decommitment, the protobuf envelope writer and the row plan of a synthetic job.  The rules of a ROWS job (kinds,
+// narrow format) are in rows_plan.hpp, host only.  Everything here is internal to liblig_hip.so.
 #pragma once
 #include <openssl/evp.h>
 
@@ -18,6 +19,7 @@
 #include "ctx_internal.hpp"
 #include "fr29.hpp"
 #include "host_field.hpp"
+#include "rows_plan.hpp"
 
 namespace H = lig::host;
 
@@ -45,29 +47,6 @@ void launch_copy_from_host(hipStream_t s, uint8_t* dst_dev, const uint8_t* src_m
 // sources of the two rows in front of each (which may lie before first_row: they only have to be in `packed`)
 void launch_expand_rows(hipStream_t s, const uint8_t* packed, const uint64_t* off_dev, const uint8_t* widths_dev, size_t first_row,
                         size_t rows, uint32_t l, uint32_t k, fr* out, const uint32_t* prod_rows_dev = nullptr, size_t n_prod = 0);
-// packed bytes of one row of width w (NOT_A_WIDTH = no width of the format): 32 -> all k slots; bits, 1, 2, 4, 8 -> the l data
-// slots, rounded up to a multiple of 4 so that every row starts 4-byte aligned; LIG_ELEM_PRODUCT -> 0, the row is derived
-static constexpr uint64_t NOT_A_WIDTH = ~(uint64_t)0;
-inline uint64_t narrow_row_bytes(uint32_t w, uint32_t l, uint32_t k) {
-    switch (w) {
-        case 32: return (uint64_t)k * 32;
-        case LIG_ELEM_BIT: return ((uint64_t)l + 31) / 32 * 4;
-        case 1: case 2: case 4: case 8: return ((uint64_t)l * w + 3) & ~(uint64_t)3;
-        case LIG_ELEM_PRODUCT: return 0;
-        default: return NOT_A_WIDTH;
-    }
-}
-// elem_bytes[r] of a rows job checked against the row's kind (kind: without the flag; draws: LIG_ROW_DRAW_PAD given).  nullptr = accepted.
-inline const char* narrow_row_refusal(const uint8_t* elem_bytes, size_t r, uint8_t kind, bool draws, uint32_t l, uint32_t k) {
-    const uint8_t w = elem_bytes[r] ? elem_bytes[r] : 32;
-    if (narrow_row_bytes(w, l, k) == NOT_A_WIDTH) return "elem_bytes must be 0, 1, 2, 4, 8, 32, LIG_ELEM_BIT or LIG_ELEM_PRODUCT";
-    if (w == LIG_ELEM_PRODUCT) {
-        // (a QZ row has its QX and QY in front of it -- the kinds were checked first -- and neither of them can be derived)
-        return kind == 3 && draws ? nullptr : "LIG_ELEM_PRODUCT is only accepted on a QZ row with LIG_ROW_DRAW_PAD";
-    }
-    if (w != 32 && (kind > 3 || !draws)) return "a narrow row must be LINEAR / QX / QY / QZ with LIG_ROW_DRAW_PAD";
-    return nullptr;
-}
 }  // namespace lig
 
 // ---- host rows -> device through the library's uploader thread (prover.hip; one thread per device, shared by every trace and
@@ -87,16 +66,20 @@ extern "C" void lig_internal_uploader_submit(int device, const std::vector<Uploa
 std::string lig_internal_uploader_state(int device);                  // diagnostics: queue length, the copy in progress and for how long
 
 // (outside the anonymous namespace: these types appear in functions shared between translation units)
-// kind: 0 linear, 1 x, 2 y, 3 z of the synthetic stream; >= 4: rows committed by the batch program (RK_* below)
-struct RowDesc { uint8_t kind; uint32_t data; };
-// `count` consecutive rows from `first` whose k-l pads are element pos, pos + (k-l), ... of the encoding stream
-struct PadRun { size_t first, count; uint64_t pos; };
 // the derived rows of a packed matrix, ascending, and their copy on the device: what launch_expand_rows takes for rows [b, e)
 struct ProductRows {
     std::vector<uint32_t> rows;
     uint32_t* dev = nullptr;
     const uint32_t* first(size_t b) const { return dev + (std::lower_bound(rows.begin(), rows.end(), (uint32_t)b) - rows.begin()); }
     size_t count(size_t b, size_t e) const { return std::lower_bound(rows.begin(), rows.end(), (uint32_t)e) - std::lower_bound(rows.begin(), rows.end(), (uint32_t)b); }
+};
+// a packed plan (rows_plan.hpp) -> what launch_expand_rows reads on the device (expand.hip; synchronous copies, the caller frees)
+int lig_internal_upload_narrow_plan(lig_ctx* c, const lig::NarrowPlan& plan, uint64_t** src_off_dev, uint8_t** widths_dev, ProductRows* prod);
+// what a trace or a shard keeps of its job's header; ih = instance_hash of the public arguments
+struct JobHeader {
+    uint8_t encoding_seed[32] = {0}, program_hash[32] = {0}, ih[32] = {0};
+    int64_t generated_at = 0;
+    char version[17] = {0};
 };
 
 namespace {
@@ -135,6 +118,31 @@ struct FieldStream {
         }
     }
 };
+
+// instance_hash over arg0 = "Ligero\0" and the public arguments (src/webgpu_prover.cpp:110-168; src/webgpu_verifier.cpp mirrors it)
+bool instance_hash(const uint8_t* args, const uint64_t* lens, uint64_t n_args, uint8_t out[32]) {
+    if (n_args && (!args || !lens)) return false;
+    std::memset(out, 0, 32);
+    Sha256().add(out, 32).add("Ligero", 7).finish(out);
+    for (uint64_t i = 0; i < n_args; i++) {
+        uint8_t prev[32];
+        std::memcpy(prev, out, 32);
+        Sha256().add(prev, 32).add(args, lens[i]).finish(out);
+        args += lens[i];
+    }
+    return true;
+}
+// lig_synth_job or lig_rows_job -> header; false: public arguments announced but not given
+template <class Job> bool fill_job_header(const Job& job, JobHeader& h) {
+    std::memcpy(h.encoding_seed, job.encoding_seed, 32);
+    std::memcpy(h.program_hash, job.program_hash, 32);
+    std::memcpy(h.version, job.version, 16);
+    h.generated_at = job.generated_at;
+    return instance_hash(job.public_args, job.public_arg_lens, job.n_public_args, h.ih);
+}
+void stage1_seed(const uint8_t root[32], const uint8_t ih[32], uint8_t out[32]) {
+    Sha256().add("LigetronStage1", 15).add(root, 32).add(ih, 32).finish(out);
+}
 
 // hash_random_engine<sha256> (include/zkp/random.hpp:87-146)
 struct HashRandomEngine {
@@ -279,12 +287,6 @@ EnvelopeLayout write_envelope(uint8_t* dst, size_t cap, const char* version, con
     return L;
 }
 
-// kind: 0 linear, 1 x, 2 y, 3 z of the synthetic stream; rows committed by the batch program (lig_hip.h, lig_batch_op):
-// 4 init, 5 bit, 6 / 7 the two rows of an equality, 8 / 9 / 10 the x, y, z of a batch product or quotient
-
-enum : uint8_t { RK_INIT = 4, RK_BIT = 5, RK_EQX = 6, RK_EQY = 7, RK_BQX = 8, RK_BQY = 9, RK_BQZ = 10 };
-inline bool has_code_check(uint8_t kind) { return kind != RK_EQX && kind != RK_EQY; }      // nonbatch_context.hpp:811-825
-
 // Commit order: rows of the batch program in program order, then witness_manager's order for the synthetic stream
 // (witness_manager.hpp:497-503): full linear rows, full quadratic triples, partial linear row, partial quadratic triple.
 // Returns false for a malformed batch program.  n_init = rows that draw padding from the encoding stream at init time.
@@ -322,19 +324,6 @@ bool plan_rows(const lig_synth_job& job, uint32_t l, std::vector<RowDesc>& rows,
     if (qp) for (uint8_t q = 1; q <= 3; q++) rows.push_back({q, (uint32_t)qp});
     return true;
 }
-// quadratic-test terms in hook order (one quadratic-stream draw each): (x, y, z) row indices; y = 0xFFFFFFFF marks the
-// equality term r * (x - z) (prover_kernels.hip k_quad_rows)
-std::vector<uint32_t> quad_terms(const std::vector<RowDesc>& rows) {
-    std::vector<uint32_t> t;
-    for (size_t r = 0; r < rows.size(); r++) {
-        const uint8_t kd = rows[r].kind;
-        if (kd == 3 || kd == RK_BQZ) { t.push_back((uint32_t)r - 2); t.push_back((uint32_t)r - 1); t.push_back((uint32_t)r); }
-        else if (kd == RK_BIT) { t.push_back((uint32_t)r); t.push_back((uint32_t)r); t.push_back((uint32_t)r); }
-        else if (kd == RK_EQY) { t.push_back((uint32_t)r - 1); t.push_back(0xFFFFFFFFu); t.push_back((uint32_t)r); }
-    }
-    return t;
-}
-
 // Row-chunk schedule [begin, end) pairs.  Chunks are `big` rows except that the exposed end of a two-stream pipeline
 // is kept short: `head` rows first (stage 2: the encode stream waits for the first randomness rows) and/or a short
 // last chunk of `tail` rows (stage 1: the column hash of the last chunk runs after the last encode).
@@ -361,6 +350,55 @@ lig::f29s to_f29s_host(const H::Fr& plain, const H::Fr& scale) {
     return o;
 }
 const H::Fr R261 = {{0x2fd4e1568fffff57ull, 0x75bba827a494b01aull, 0x5301fa84819caa80ull, 0x0dc83629563d4475ull}};   // 2^261 mod p
+
+// Stage-2 coefficients, both streams keyed by the stage-1 seed: one code-stream draw per row that has a code check, in commit order
+// (code[r]; zero for a row without one), one quadratic-stream draw per term of quad_terms (quad[i])
+struct Coefficients { std::vector<H::Fr> code, quad; };
+Coefficients draw_coefficients(const uint8_t seed1[32], const std::vector<RowDesc>& rows) {
+    Coefficients cf;
+    std::vector<H::Fr> rc;
+    FieldStream code_s(seed1), quad_s(seed1);
+    size_t n_code = 0;
+    for (const RowDesc& d : rows) n_code += has_code_check(d.kind);
+    code_s.next(n_code, rc);
+    quad_s.next(quad_terms(rows).size() / 3, cf.quad);
+    cf.code.assign(rows.size(), H::from_u64(0));
+    for (size_t r = 0, ci = 0; r < rows.size(); r++) if (has_code_check(rows[r].kind)) cf.code[r] = rc[ci++];
+    return cf;
+}
+// the table the stage-2 kernels read, for the rows and terms a device holds (global indices; nullptr: all of them, in order):
+// [rc of every row | rq * 2^522 of every term | rq * 2^261 of every term | one spare], 29-bit limbs
+std::vector<lig::f29s> coef_table(const Coefficients& cf, const std::vector<size_t>* rows, const std::vector<size_t>* terms) {
+    const size_t nr = rows ? rows->size() : cf.code.size(), nt = terms ? terms->size() : cf.quad.size();
+    const H::Fr R261sq = H::mul(R261, R261);
+    std::vector<lig::f29s> coef(nr + 2 * nt + 1);
+    std::memset(coef.data(), 0, coef.size() * sizeof(lig::f29s));
+    for (size_t r = 0; r < nr; r++) coef[r] = to_f29s_host(cf.code[rows ? (*rows)[r] : r], R261);
+    for (size_t i = 0; i < nt; i++) {
+        const H::Fr& rq = cf.quad[terms ? (*terms)[i] : i];
+        coef[nr + i] = to_f29s_host(rq, R261sq);
+        coef[nr + nt + i] = to_f29s_host(rq, R261);
+    }
+    return coef;
+}
+
+// The self-check on the three decoded accumulators (dec: 3 x n; src/webgpu_prover.cpp:355-386,465-469, webgpu_verifier.cpp:412-442):
+// the code polynomial has degree < k, the linear polynomial sums to minus the constant over the l data slots, the quadratic one
+// vanishes on them
+struct SelfCheck { int valid_code, valid_linear, valid_quad; };
+SelfCheck self_check(const H::Fr* dec, const uint8_t const_sum[32], uint32_t l, uint32_t k, uint32_t n) {
+    auto is_zero = [](const H::Fr& v) { return !(v.v[0] | v.v[1] | v.v[2] | v.v[3]); };
+    SelfCheck ok;
+    ok.valid_code = 1;
+    for (uint32_t i = k; i < n; i++) if (!is_zero(dec[i])) ok.valid_code = 0;
+    H::Fr a;
+    std::memcpy(a.v, const_sum, 32);
+    for (uint32_t i = 0; i < l; i++) a = H::add(a, dec[(size_t)n + i]);
+    ok.valid_linear = is_zero(a);
+    ok.valid_quad = 1;
+    for (uint32_t i = 0; i < l; i++) if (!is_zero(dec[2 * (size_t)n + i])) ok.valid_quad = 0;
+    return ok;
+}
 
 }  // namespace
 
@@ -412,3 +450,6 @@ int lig_run_batch_program(lig_ctx* c, const lig_synth_job& job, fr* rows_out);
 // witness values of the synthetic stream rows [first, rows.size()) (one draw of the witness_key stream per data slot of every
 // linear / x / y row in commit order, z = x*y); row r is written to msgs + r*k.  Enqueued on the context stream.
 int lig_internal_synth_witness(lig_ctx* c, const uint8_t witness_key[32], const std::vector<RowDesc>& rows, size_t first, fr* msgs);
+// the three mask rows of stage 1 in place (maskcw: 3 x n, reference layout) from element epos of the encoding stream, whose round keys
+// are in c->rk_dev: a memset and six launches on `stream`; dots = one device element of scratch (prover.hip)
+int lig_internal_form_mask_rows(lig_ctx* c, hipStream_t stream, uint64_t epos, fr* maskcw, fr* dots);

@@ -36,15 +36,12 @@ struct lig_shard {
     std::vector<size_t> lrow0;                 // local row offset of my c-th chunk (rounds + 1 entries)
     std::vector<size_t> grow;                  // global row of every local row
     std::vector<uint64_t> wit_pos, lin_pos;    // stream position of every global row (+1 entry)
-    std::vector<uint64_t> code_ord;            // code-test draws before every global row (+1 entry)
     std::vector<uint8_t> draw;                 // per global row: its k-l pads are drawn here at commit time (pad_encoding_random)
     std::vector<uint64_t> enc_pos;             // encoding-stream position of every global row's pads (+1 entry = the masks' position)
     bool from_rows = false;                    // lig_shard_rows_*: the local rows and their randomness rows come from the caller
     bool dense_rands = false, committed = false;
     lig_proof_info info1;                      // stage-1 results kept between lig_shard_rows_commit and lig_shard_rows_prove
-    uint8_t encoding_seed[32] = {0}, program_hash[32] = {0};
-    int64_t generated_at = 0;
-    char version[17] = {0};
+    JobHeader hdr;
     size_t RB = 0, n_init = 0;                 // leading rows committed by the batch program, of those: init rows
     size_t R = 0, Rl = 0, rows_max = 0, ncol = 0, rounds = 0, G = 0, ch_cap = 0;
     fr *msgs = nullptr, *cw = nullptr, *maskcw = nullptr, *send = nullptr, *recv = nullptr, *randb = nullptr, *rhalf = nullptr, *acc = nullptr,
@@ -55,7 +52,6 @@ struct lig_shard {
     std::vector<size_t> triple_ord;            // global ordinal of each local triple
     uint8_t *h_proof = nullptr, *h_enc = nullptr, *h_nodes = nullptr, *h_small = nullptr;
     size_t h_proof_cap = 0;
-    uint8_t ih[32] = {0};
     hipEvent_t ev_enc[2] = {nullptr, nullptr}, ev_comm[2] = {nullptr, nullptr}, ev_hash[2] = {nullptr, nullptr};
     // caller rows in host memory (lig_shard_rows_*): uploaded by the library's uploader thread, as in lig_rows_* (prover.hip).  Flag words
     // in pinned host memory: [round c: local rows of my c-th chunk arrived | round c: randomness rows arrived | ... consumed]
@@ -139,23 +135,8 @@ int lig_shard_prepare(lig_ctx* c, const lig_synth_job* job, uint32_t rank, uint3
     lig_shard* S = new lig_shard();
     S->c = c; S->job = *job; S->comm = *comm; S->rank = rank; S->world = world;
     S->job.batch_ops = nullptr; S->job.batch_data = nullptr;
-    std::memcpy(S->encoding_seed, job->encoding_seed, 32);
-    std::memcpy(S->program_hash, job->program_hash, 32);
-    std::memcpy(S->version, job->version, 16);
-    S->generated_at = job->generated_at;
-    {   // instance_hash over arg0 = "Ligero\0" and the public arguments (src/webgpu_prover.cpp:110-168)
-        if (job->n_public_args && (!job->public_args || !job->public_arg_lens)) { delete S; return LIG_E_ARG; }
-        std::memset(S->ih, 0, 32);
-        Sha256().add(S->ih, 32).add("Ligero", 7).finish(S->ih);
-        const uint8_t* a = job->public_args;
-        for (uint64_t i = 0; i < job->n_public_args; i++) {
-            uint8_t prev[32];
-            std::memcpy(prev, S->ih, 32);
-            Sha256().add(prev, 32).add(a, job->public_arg_lens[i]).finish(S->ih);
-            a += job->public_arg_lens[i];
-        }
-        S->job.public_args = nullptr; S->job.public_arg_lens = nullptr;
-    }
+    S->job.public_args = nullptr; S->job.public_arg_lens = nullptr;
+    if (!fill_job_header(*job, S->hdr)) { delete S; return LIG_E_ARG; }
     const int rc = shard_prepare_impl(c, job, rank, world, S);
     if (rc != LIG_OK) { lig_shard_destroy(S); return rc; }
     *out = S;
@@ -170,13 +151,12 @@ static int shard_prepare_impl(lig_ctx* c, const lig_synth_job* job, uint32_t ran
     if (S->n_init && k - l != 192) FAIL(c, LIG_E_ARG, "batch program: on_batch_init draws params::sample_size = 192 pads, k - l must be 192");
     const size_t R = S->R = S->rows.size();
     for (S->RB = 0; S->RB < R && S->rows[S->RB].kind >= RK_INIT; S->RB++) {}
-    S->wit_pos.assign(R + 1, 0); S->lin_pos.assign(R + 1, 0); S->code_ord.assign(R + 1, 0);
+    S->wit_pos.assign(R + 1, 0); S->lin_pos.assign(R + 1, 0);
     S->draw.assign(R, 0); S->enc_pos.assign(R + 1, 0);
     for (size_t r = 0; r < R; r++) {
         const uint8_t kd = S->rows[r].kind;
         S->wit_pos[r + 1] = S->wit_pos[r] + ((kd == 3 || kd >= RK_INIT) ? 0 : S->rows[r].data);   // z rows and batch rows draw nothing
         S->lin_pos[r + 1] = S->lin_pos[r] + S->rows[r].data;
-        S->code_ord[r + 1] = S->code_ord[r] + has_code_check(kd);                                    // position in the code-test stream
         S->draw[r] = kd <= 3;                                                                        // stream rows draw at commit time; init rows drew theirs in the program
         S->enc_pos[r + 1] = S->enc_pos[r] + ((kd <= 3 || kd == RK_INIT) ? (k - l) : 0);             // rows that draw k-l pads upstream
     }
@@ -443,7 +423,7 @@ static int shard_stage1(lig_shard* S, lig_proof_info* info) {
     ShardDebugScope dbg(S, "stage 1", nullptr);
     // ---------------- stage 1
     uint32_t rk[60];
-    lig::aes256_expand_host(S->encoding_seed, rk);
+    lig::aes256_expand_host(S->hdr.encoding_seed, rk);
     TRY(lig_internal_upload_small(c, c->rk_dev, rk, sizeof rk, s));
     // pads of the local rows that draw them at commit time (batch init rows carry theirs from the program): the position
     // of a row's pads = number of pad-drawing rows before it in commit order; runs of consecutive rows = one launch
@@ -459,16 +439,9 @@ static int shard_stage1(lig_shard* S, lig_proof_info* info) {
         }
     };
     if (!S->rows_by_thread) draw_pads(0, Rl);
-    uint64_t epos = S->enc_pos[R];
-    fr* mask = S->maskcw; fr* mlin = mask + n; fr* mquad = mask + 2 * (size_t)n;                        // masks: formed by every rank
+    fr* mask = S->maskcw; fr* mlin = mask + n;                                                           // masks: formed by every rank
     const size_t k3 = 3 * (size_t)k, kq = ncol / 4;                                                      // kq = positions per coset of a rank's columns
-    HIP_TRY(c, hipMemsetAsync(mask, 0, 3 * (size_t)n * 32, s));
-    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mask, 1, l, 0, 0, 1, 0); epos += l;
-    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mlin, 1, l - 1, 0, 1, 2, 0); epos += l - 1;
-    lig::launch_sum_elems(s, mlin + 1, l - 1, 2, S->dots, mlin + 2 * (size_t)(l - 1) + 1);      // closing slot = -(sum of the others), on the device
-    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mlin, 1, 2 * pad, 0, 2 * l, 1, 0); epos += 2 * pad;
-    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mquad, 1, l, 0, 1, 2, 0); epos += l;
-    lig::launch_rng_fill_rows(s, c->rk_dev, epos, mquad, 1, 2 * pad, 0, 2 * l, 1, 0); epos += 2 * pad;
+    TRY(lig_internal_form_mask_rows(c, s, S->enc_pos[R], mask, S->dots));
     TRY(lig_sha_init(c, S->sha_state, ncol));
     HIP_TRY(c, hipEventRecord(c->ev_fork, s));
     HIP_TRY(c, hipStreamWaitEvent(s_hash, c->ev_fork, 0));
@@ -538,7 +511,7 @@ static int shard_stage1(lig_shard* S, lig_proof_info* info) {
         S->rows_by_thread = false;
         if (const int e = S->up_failed.exchange(0)) FAIL(c, LIG_E_HIP, std::string("rows upload failed: ") + hipGetErrorString((hipError_t)e));
     }
-    Sha256().add("LigetronStage1", 15).add(info->root, 32).add(S->ih, 32).finish(info->stage1_seed);
+    stage1_seed(info->root, S->hdr.ih, info->stage1_seed);
     return LIG_OK;
 }
 
@@ -551,17 +524,8 @@ static int shard_stage23(lig_shard* S, const ShardRands& rs, const uint8_t* cons
 
     // ---------------- stage 2
     const size_t NTl = S->triple_ord.size();
-    {
-        std::vector<H::Fr> rc, rq;
-        const size_t NT = quad_terms(S->rows).size() / 3;
-        FieldStream code_s(info->stage1_seed), quad_s(info->stage1_seed);
-        code_s.next(S->code_ord[R], rc);
-        quad_s.next(NT, rq);
-        std::vector<lig::f29s> coef(Rl + 2 * NTl + 1);
-        const H::Fr R261sq = H::mul(R261, R261);
-        std::memset(coef.data(), 0, coef.size() * sizeof(lig::f29s));
-        for (size_t lr = 0; lr < Rl; lr++) if (has_code_check(S->rows[S->grow[lr]].kind)) coef[lr] = to_f29s_host(rc[S->code_ord[S->grow[lr]]], R261);
-        for (size_t i = 0; i < NTl; i++) { coef[Rl + i] = to_f29s_host(rq[S->triple_ord[i]], R261sq); coef[Rl + NTl + i] = to_f29s_host(rq[S->triple_ord[i]], R261); }
+    {   // the draws of the whole trace, the table of the local rows and terms
+        const std::vector<lig::f29s> coef = coef_table(draw_coefficients(info->stage1_seed, S->rows), &S->grow, &S->triple_ord);
         TRY(lig_internal_upload_small(c, S->coef_dev, coef.data(), coef.size() * sizeof(lig::f29s), s));
         lig::aes256_expand_host(info->stage1_seed, rk);
         TRY(lig_internal_upload_small(c, c->rk_dev, rk, sizeof rk, s));
@@ -731,17 +695,8 @@ static int shard_stage23(lig_shard* S, const ShardRands& rs, const uint8_t* cons
     const std::vector<uint32_t> idx = sample_columns(info->stage2_seed, n, t);
     TRY(lig_sample_init(c, idx.data(), idx.size()));
     TRY(drain_event(c->ev_join, "stage 2 (decodes)"));     // decoded accumulators and Merkle nodes are on the host
-    auto is_zero = [](const H::Fr& v) { return !(v.v[0] | v.v[1] | v.v[2] | v.v[3]); };
-    info->valid_code = 1;
-    for (uint32_t i = k; i < n; i++) if (!is_zero(dec[i])) info->valid_code = 0;
-    {
-        H::Fr a;
-        std::memcpy(a.v, info->const_sum, 32);
-        for (uint32_t i = 0; i < l; i++) a = H::add(a, dec[(size_t)n + i]);
-        info->valid_linear = is_zero(a);
-    }
-    info->valid_quad = 1;
-    for (uint32_t i = 0; i < l; i++) if (!is_zero(dec[2 * (size_t)n + i])) info->valid_quad = 0;
+    const SelfCheck ok = self_check(dec, info->const_sum, l, k, n);
+    info->valid_code = ok.valid_code; info->valid_linear = ok.valid_linear; info->valid_quad = ok.valid_quad;
     const std::vector<uint8_t> sib = decommit(S->h_nodes, (n_nodes + 1) / 2, idx);
     info->ms_stage2 = ms_since(t0);
     t0 = clk::now();
@@ -750,10 +705,8 @@ static int shard_stage23(lig_shard* S, const ShardRands& rs, const uint8_t* cons
     lig::launch_gather_rows_planar(s, view, Rl, c->sample_idx, t, S->smp);                      // local rows, then the 3 masks
     lig::launch_gather_rows(s, S->maskcw, n, 3, c->sample_idx, t, S->smp + Rl * (size_t)t);
     TRY(all_gather(S->smp, S->smpg, RM * (size_t)t * 32, s, "all_gather(opened columns)"));
-    char ver[17] = {0};
-    std::memcpy(ver, S->version, 16);
     const size_t smp_bytes = (R + 3) * (size_t)t * 32;
-    const EnvelopeLayout lay = write_envelope(S->h_proof, S->h_proof_cap, ver, S->program_hash, S->generated_at, k, n, t,
+    const EnvelopeLayout lay = write_envelope(S->h_proof, S->h_proof_cap, S->hdr.version, S->hdr.program_hash, S->hdr.generated_at, k, n, t,
                                               info->root, sib, idx, enc, smp_bytes);
     if (lay.total > S->h_proof_cap) FAIL(c, LIG_E_NOMEM, "proof buffer too small");
     // opened columns in commit order: global chunk g = the (g / W)-th chunk of rank g mod W
@@ -797,29 +750,6 @@ int lig_shard_prove(lig_shard* S, const uint8_t** proof, size_t* proof_len, lig_
 // stream positions are global) and the message rows of ITS chunks only, in commit order; after the commit every rank's
 // constraint generator derives the randomness rows of its own rows from the stage-1 seed.
 // Replaces the per-row callbacks of include/zkp/nonbatch_context.hpp:445-471 (stage 1), :654-780 (stage 2), :924-970 (stage 3).
-static bool kinds_to_rows(lig_ctx* c, const lig_rows_job* job, std::vector<RowDesc>& rows, std::vector<uint8_t>& draw, std::vector<uint64_t>& pos) {
-    const uint32_t k = c->k, l = c->l, pad = k - l;
-    const size_t R = job->rows;
-    rows.resize(R); draw.assign(R, 0); pos.assign(R + 1, 0);
-    for (size_t r = 0; r < R; r++) {
-        const uint8_t kd = job->kinds[r] & 0x7f;
-        if (kd > RK_BQZ) { c->err = "rows job: unknown row kind"; return false; }
-        const bool first_of_3 = kd == 1 || kd == RK_BQX, first_of_2 = kd == RK_EQX;
-        if (first_of_3 && !(r + 2 < R && (job->kinds[r + 1] & 0x7f) == kd + 1 && (job->kinds[r + 2] & 0x7f) == kd + 2)) { c->err = "rows job: incomplete x,y,z triple"; return false; }
-        if (first_of_2 && !(r + 1 < R && (job->kinds[r + 1] & 0x7f) == RK_EQY)) { c->err = "rows job: incomplete equality pair"; return false; }
-        const bool follower = kd == 2 || kd == 3 || kd == RK_EQY || kd == RK_BQY || kd == RK_BQZ;
-        if (follower && !(r > 0 && (job->kinds[r - 1] & 0x7f) == kd - 1)) { c->err = "rows job: row of a group without its predecessor"; return false; }
-        const bool draws = kd <= 3 || kd == RK_INIT;
-        if (kd == RK_INIT && pad != 192) { c->err = "rows job: on_batch_init rows need k - l = 192 (params::sample_size)"; return false; }
-        if ((job->kinds[r] & LIG_ROW_DRAW_PAD) && !draws) { c->err = "rows job: LIG_ROW_DRAW_PAD on a row kind that draws no padding upstream"; return false; }
-        draw[r] = (job->kinds[r] & LIG_ROW_DRAW_PAD) ? 1 : 0;
-        pos[r + 1] = pos[r] + (draws ? pad : 0);
-        const uint32_t dense = job->dense_rands_per_row ? job->dense_rands_per_row[r] : 0;
-        if (dense > k || (dense && kd > 3)) { c->err = "rows job: dense_rands_per_row out of range or on a batch row"; return false; }
-        rows[r] = RowDesc{kd, dense};
-    }
-    return true;
-}
 
 int lig_shard_rows_plan(const uint8_t* kinds, size_t n_rows, uint32_t world, uint64_t* rounds_out, uint64_t* boundaries, size_t cap) {
     if ((n_rows && !kinds) || !world || !rounds_out) return LIG_E_ARG;
@@ -893,37 +823,6 @@ static int shard_rows_load(lig_shard* S, const void* local_msgs, bool on_device)
     return LIG_OK;
 }
 
-// the narrow row format: widths of all rows checked as lig_rows_begin does, packed offsets of the local rows (commit order); the staging
-// buffer of host rows is allocated by the first load from host memory (device rows are expanded where they are)
-static int shard_narrow_setup(lig_shard* S, const lig_rows_job* job, uint32_t l, uint32_t k) {
-    lig_ctx* c = S->c;
-    std::vector<uint8_t> widths(S->R);
-    for (size_t r = 0; r < S->R; r++) {
-        const uint8_t w = job->elem_bytes[r] ? job->elem_bytes[r] : 32;
-        if (const char* why = lig::narrow_row_refusal(job->elem_bytes, r, S->rows[r].kind, S->draw[r] != 0, l, k)) FAIL(c, LIG_E_ARG, std::string("sharded rows job: ") + why);
-        widths[r] = w;
-        S->narrow = S->narrow || w != 32;
-    }
-    if (!S->narrow) return LIG_OK;                     // every row full width: the plain path
-    const size_t Rl = S->Rl;
-    std::vector<uint8_t> local_w(Rl ? Rl : 1, 32);
-    S->src_off.assign(Rl + 1, 0);
-    for (size_t lr = 0; lr < Rl; lr++) {
-        local_w[lr] = widths[S->grow[lr]];
-        S->src_off[lr + 1] = S->src_off[lr] + lig::narrow_row_bytes(local_w[lr], l, k);
-        if (local_w[lr] == LIG_ELEM_PRODUCT) S->prod.rows.push_back((uint32_t)lr);       // x, y are local rows lr - 2, lr - 1: the deal never splits a triple
-    }
-    if (!S->prod.rows.empty()) {
-        HIP_TRY(c, hipMalloc((void**)&S->prod.dev, S->prod.rows.size() * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemcpy(S->prod.dev, S->prod.rows.data(), S->prod.rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(c, hipMalloc((void**)&S->src_off_dev, (Rl + 1) * sizeof(uint64_t)));
-    HIP_TRY(c, hipMalloc((void**)&S->widths_dev, local_w.size()));
-    HIP_TRY(c, hipMemcpy(S->src_off_dev, S->src_off.data(), (Rl + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(S->widths_dev, local_w.data(), local_w.size(), hipMemcpyHostToDevice));
-    return LIG_OK;
-}
-
 int lig_shard_rows_begin(lig_ctx* c, const lig_rows_job* job, uint32_t rank, uint32_t world, const lig_comm* comm, lig_shard** out) {
     CHECK_CTX(c);
     if (!job || !out || !comm || world == 0 || rank >= world) return LIG_E_ARG;
@@ -935,31 +834,24 @@ int lig_shard_rows_begin(lig_ctx* c, const lig_rows_job* job, uint32_t rank, uin
     lig_shard* S = new lig_shard();
     S->c = c; S->comm = *comm; S->rank = rank; S->world = world; S->from_rows = true;
     std::memset(&S->job, 0, sizeof S->job);
-    std::memcpy(S->encoding_seed, job->encoding_seed, 32);
-    std::memcpy(S->program_hash, job->program_hash, 32);
-    std::memcpy(S->version, job->version, 16);
-    S->generated_at = job->generated_at;
     S->dense_rands = job->dense_rands_per_row != nullptr;
     auto fail = [&](int rc) { lig_shard_destroy(S); return rc; };
-    if (job->n_public_args && (!job->public_args || !job->public_arg_lens)) return fail(LIG_E_ARG);
-    std::memset(S->ih, 0, 32);
-    Sha256().add(S->ih, 32).add("Ligero", 7).finish(S->ih);
-    const uint8_t* a = job->public_args;
-    for (uint64_t i = 0; i < job->n_public_args; i++) {
-        uint8_t prev[32];
-        std::memcpy(prev, S->ih, 32);
-        Sha256().add(prev, 32).add(a, job->public_arg_lens[i]).finish(S->ih);
-        a += job->public_arg_lens[i];
-    }
-    if (!kinds_to_rows(c, job, S->rows, S->draw, S->enc_pos)) return fail(LIG_E_ARG);
+    if (!fill_job_header(*job, S->hdr)) return fail(LIG_E_ARG);
+    if (const char* why = lig::parse_row_kinds(*job, l, k, true, S->rows, S->draw, S->enc_pos)) { c->err = std::string("rows job: ") + why; return fail(LIG_E_ARG); }
     const size_t R = S->R = S->rows.size();
-    S->lin_pos.assign(R + 1, 0); S->code_ord.assign(R + 1, 0); S->wit_pos.assign(R + 1, 0);
-    for (size_t r = 0; r < R; r++) {
-        S->lin_pos[r + 1] = S->lin_pos[r] + S->rows[r].data;
-        S->code_ord[r + 1] = S->code_ord[r] + has_code_check(S->rows[r].kind);
-    }
+    S->lin_pos.assign(R + 1, 0); S->wit_pos.assign(R + 1, 0);
+    for (size_t r = 0; r < R; r++) S->lin_pos[r + 1] = S->lin_pos[r] + S->rows[r].data;
     int rc = shard_alloc(c, rank, world, S);
-    if (rc == LIG_OK && job->elem_bytes) rc = shard_narrow_setup(S, job, l, k);
+    if (rc == LIG_OK && job->elem_bytes) {
+        // the narrow row format: every row of the job is checked as lig_rows_begin does, the plan is of the local rows; the staging
+        // buffer of host rows is allocated by the first load from host memory (device rows are expanded where they are)
+        lig::NarrowPlan np;
+        if (const char* why = lig::plan_narrow_rows(job->elem_bytes, S->rows, S->draw, l, k, S->grow, np)) { c->err = std::string("sharded rows job: ") + why; rc = LIG_E_ARG; }
+        else if ((S->narrow = np.packed)) {
+            rc = lig_internal_upload_narrow_plan(c, np, &S->src_off_dev, &S->widths_dev, &S->prod);
+            S->src_off = std::move(np.src_off);
+        }
+    }
     if (rc == LIG_OK) rc = shard_rows_load(S, job->msgs, job->msgs_on_device != 0);
     if (rc != LIG_OK) return fail(rc);
     *out = S;

@@ -123,10 +123,8 @@ static int verify_core(lig_ctx* c, const std::vector<RowDesc>& rows, const uint8
     out->parsed = 1;
     // ---- seeds and sample indices (src/webgpu_verifier.cpp:268-293)
     uint8_t seed1[32], seed2[32];
-    {
-        Sha256().add("LigetronStage1", 15).add(root, 32).add(ih, 32).finish(seed1);
-        Sha256().add("LigetronStage2", 15).add(root, 32).add(pcode, vec).add(plin, vec).add(pquad, vec).finish(seed2);
-    }
+    stage1_seed(root, ih, seed1);
+    Sha256().add("LigetronStage2", 15).add(root, 32).add(pcode, vec).add(plin, vec).add(pquad, vec).finish(seed2);
     const std::vector<uint32_t> idx = sample_columns(seed2, n, t);
     mark("parse, canonical checks, seeds, indices");
     out->indices_match = idx == pidx;
@@ -196,17 +194,7 @@ static int verify_core(lig_ctx* c, const std::vector<RowDesc>& rows, const uint8
     HIP_TRY(c, hipMemcpyAsync(dpoly + 2 * (size_t)n, pquad, vec, hipMemcpyHostToDevice, s));
     if (!triples.empty()) TRY(lig_internal_upload_small(c, dtri, triples.data(), triples.size() * 4, s));
     {
-        std::vector<H::Fr> rc, rq;
-        FieldStream code(seed1), quad(seed1);
-        size_t n_code = 0;
-        for (size_t r = 0; r < R; r++) n_code += has_code_check(rows[r].kind);
-        code.next(n_code, rc);
-        quad.next(NT, rq);
-        std::vector<lig::f29s> coef(R + 2 * NT + 1);
-        std::memset(coef.data(), 0, coef.size() * sizeof(lig::f29s));
-        const H::Fr R261sq = H::mul(R261, R261);
-        for (size_t r = 0, ci = 0; r < R; r++) if (has_code_check(rows[r].kind)) coef[r] = to_f29s_host(rc[ci++], R261);
-        for (size_t i = 0; i < NT; i++) { coef[R + i] = to_f29s_host(rq[i], R261sq); coef[R + NT + i] = to_f29s_host(rq[i], R261); }
+        const std::vector<lig::f29s> coef = coef_table(draw_coefficients(seed1, rows), nullptr, nullptr);
         TRY(lig_internal_upload_small(c, dcoef, coef.data(), coef.size() * sizeof(lig::f29s), s));
         uint32_t rk[60];
         lig::aes256_expand_host(seed1, rk);
@@ -304,18 +292,12 @@ static int verify_core(lig_ctx* c, const std::vector<RowDesc>& rows, const uint8
     size_t P = 1;
     while (P < n) P <<= 1;
     out->valid_merkle = recommit(P, idx, leaves.data(), sib, vroot) && !std::memcmp(vroot, root, 32);
-    auto is_zero = [](const H::Fr& v) { return !(v.v[0] | v.v[1] | v.v[2] | v.v[3]); };
-    out->valid_code = 1;
-    for (uint32_t i = k; i < n; i++) if (!is_zero(dec[i])) out->valid_code = 0;
-    {
-        H::Fr a;
-        if (derive) a = H::neg(derived);
-        else { std::memcpy(a.v, const_sum, 32); if (H::geq(a, H::P)) return LIG_OK; }
-        for (uint32_t i = 0; i < l; i++) a = H::add(a, dec[(size_t)n + i]);
-        out->valid_linear = is_zero(a);
-    }
-    out->valid_quad = 1;
-    for (uint32_t i = 0; i < l; i++) if (!is_zero(dec[2 * (size_t)n + i])) out->valid_quad = 0;
+    H::Fr cs = H::neg(derived);
+    if (!derive) std::memcpy(cs.v, const_sum, 32);
+    const SelfCheck ok = self_check(dec.data(), reinterpret_cast<const uint8_t*>(cs.v), l, k, n);
+    out->valid_code = ok.valid_code;
+    if (H::geq(cs, H::P)) return LIG_OK;                        // a constant that is no canonical residue: nothing further is accepted
+    out->valid_linear = ok.valid_linear; out->valid_quad = ok.valid_quad;
     out->code_equal = out->linear_equal = out->quad_equal = 1;
     for (uint32_t i = 0; i < t; i++) {
         if (std::memcmp(pcode + 32 * (size_t)idx[i], &vacc[i], 32)) out->code_equal = 0;
@@ -325,19 +307,6 @@ static int verify_core(lig_ctx* c, const std::vector<RowDesc>& rows, const uint8
     out->accept = out->valid_merkle && out->valid_code && out->valid_linear && out->valid_quad && out->code_equal && out->linear_equal && out->quad_equal;
     HIP_TRY(c, hipGetLastError());
     return LIG_OK;
-}
-
-static bool instance_hash_v(const uint8_t* args, const uint64_t* lens, uint64_t n_args, uint8_t ih[32]) {
-    if (n_args && (!args || !lens)) return false;
-    std::memset(ih, 0, 32);
-    Sha256().add(ih, 32).add("Ligero", 7).finish(ih);
-    for (uint64_t i = 0; i < n_args; i++) {
-        uint8_t prev[32];
-        std::memcpy(prev, ih, 32);
-        Sha256().add(prev, 32).add(args, lens[i]).finish(ih);
-        args += lens[i];
-    }
-    return true;
 }
 
 // the verifier's side of a rows job (lig_rows_verify_*): kinds + public data, the proof, and between the two calls the
@@ -363,7 +332,7 @@ int lig_synth_verify(lig_ctx* c, const lig_synth_job* job, const uint8_t* const_
     size_t n_init = 0;
     uint8_t ih[32];
     if (!plan_rows(*job, c->l, rows, n_init)) return LIG_E_ARG;
-    if (!instance_hash_v(job->public_args, job->public_arg_lens, job->n_public_args, ih)) return LIG_E_ARG;   // src/webgpu_verifier.cpp mirrors webgpu_prover.cpp:110-168
+    if (!instance_hash(job->public_args, job->public_arg_lens, job->n_public_args, ih)) return LIG_E_ARG;
     VSource src;
     src.witness_key = job->witness_key;
     return verify_core(c, rows, ih, src, const_sum, proof, proof_len, out, nullptr, false);
@@ -376,17 +345,10 @@ int lig_rows_verify_begin(lig_ctx* c, const lig_rows_job* job, const uint8_t* pr
     *vt = nullptr;
     lig_vtrace* V = new lig_vtrace();
     V->c = c;
-    V->rows.resize(job->rows);
-    for (size_t r = 0; r < job->rows; r++) {
-        const uint8_t kd = job->kinds[r] & 0x7f;
-        if (kd > RK_BQZ) { delete V; FAIL(c, LIG_E_ARG, "rows job: unknown row kind"); }
-        const bool first_of_3 = kd == 1 || kd == RK_BQX, first_of_2 = kd == RK_EQX, follower = kd == 2 || kd == 3 || kd == RK_EQY || kd == RK_BQY || kd == RK_BQZ;
-        const bool ok = (!first_of_3 || (r + 2 < job->rows && (job->kinds[r + 1] & 0x7f) == kd + 1 && (job->kinds[r + 2] & 0x7f) == kd + 2)) &&
-                        (!first_of_2 || (r + 1 < job->rows && (job->kinds[r + 1] & 0x7f) == RK_EQY)) && (!follower || (r > 0 && (job->kinds[r - 1] & 0x7f) == kd - 1));
-        if (!ok) { delete V; FAIL(c, LIG_E_ARG, "rows job: incomplete row group"); }
-        V->rows[r] = RowDesc{kd, 0};
-    }
-    if (!instance_hash_v(job->public_args, job->public_arg_lens, job->n_public_args, V->ih)) { delete V; return LIG_E_ARG; }
+    std::vector<uint8_t> draw;                                  // (of the prover's side: unused here)
+    std::vector<uint64_t> pos;
+    if (const char* why = lig::parse_row_kinds(*job, c->l, c->k, false, V->rows, draw, pos)) { delete V; FAIL(c, LIG_E_ARG, std::string("rows job: ") + why); }
+    if (!instance_hash(job->public_args, job->public_arg_lens, job->n_public_args, V->ih)) { delete V; return LIG_E_ARG; }
     V->proof.assign(proof, proof + proof_len);
     const int rc = verify_core(c, V->rows, V->ih, VSource{}, nullptr, V->proof.data(), V->proof.size(), out, stage1_seed, true);
     if (rc != LIG_OK || !out->parsed || !out->indices_match) { delete V; return rc; }      // malformed envelope: accept = 0, no trace
