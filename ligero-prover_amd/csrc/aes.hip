@@ -226,7 +226,7 @@ __global__ void __launch_bounds__(LIG_RLC_THREADS) k_rand_rlc(const uint32_t* __
             if (++since == 6) { ac = f29_qnorm(ac); al = f29_qnorm(al); since = 0; }
         }
         if (rc != nullptr) fr_store(code_part + (size_t)g * k + j, pack29(f29_reduce_2p(ac)));
-        f29 w = f29_montmul(f29_qnorm(al), f29_const_r2());                                   // plain value, < 1.2p
+        f29 w = f29_montmul(f29_qnorm(al), f29_const_r2());                                   // plain value, < 2p (p + 1.2p*group*p/2^261)
         w = f29_reduce_2p(f29_add(w, unpack29(fr_load(lin_part + (size_t)g * k + j))));
         fr_store(lin_part + (size_t)g * k + j, pack29(w));
     }

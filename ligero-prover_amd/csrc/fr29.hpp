@@ -79,7 +79,7 @@ __device__ __forceinline__ uint32_t f29_p0_opaque() {
 }
 
 // Montgomery product a*b/2^261 mod p.  a: lazy, limbs < 1.25 * 2^31 (top limb < 2^31); b: normalised, < p.
-// Result: normalised limbs, value < a*p/2^261 + p  (< 1.2 p for value(a) < 32 p).
+// Result: normalised limbs, value < a*b/2^261 + p  (< 1.2 p for value(a) < 32 p; b only needs normalised limbs).
 // 81 + 81 v_mad_u64_u32 chained through one 64-bit accumulator, 9 v_mul_lo_u32, 17 v_lshrrev_b64.  The columns are
 // written as inline-asm blocks: left to itself hipcc starts every column in a fresh accumulator and joins it to the
 // carried sum with a v_lshl_add_u64 (17 extra quarter-rate instructions per product, to shorten a dependency chain that
@@ -198,17 +198,21 @@ __device__ __forceinline__ f29 f29_add(const f29& a, const f29& b) {
     for (int i = 0; i < 9; i++) r.v[i] = a.v[i] + b.v[i];
     return r;
 }
-// a - b + K with K a borrow-proof multiple of p (every K limb >= the matching limb of b, value(K) >= value(b))
+// a - b + K with K a borrow-proof multiple of p (every K limb >= the matching limb of b, value(K) >= value(b)).
+// K = m*p with c * 2^29 lent to every limb below the top one, so its top limb is (m*p >> 232) - c: the subtrahend's value has to
+// stay below m*p - c * 2^232, not merely below m*p (tools/check_fr29.py; every call site subtracts far less: products < 1.2p from
+// K2P, < 3p from K4P, < 6p from K8P, < 12p from K16P).
 #define F29_SUBK(r, a, b, KMAC)                                              \
     do {                                                                     \
         _Pragma("unroll") for (int i_ = 0; i_ < 9; i_++)(r).v[i_] = (a).v[i_] + (KMAC(i_) - (b).v[i_]); \
     } while (0)
-__device__ __forceinline__ f29 f29_sub_k2(const f29& a, const f29& b) { f29 r; F29_SUBK(r, a, b, F29_K2P_C1); return r; }   // b normalised, < 2p
-__device__ __forceinline__ f29 f29_sub_k4(const f29& a, const f29& b) { f29 r; F29_SUBK(r, a, b, F29_K4P_C2); return r; }   // b limbs < 2^30, < 4p
-__device__ __forceinline__ f29 f29_sub_k8(const f29& a, const f29& b) { f29 r; F29_SUBK(r, a, b, F29_K8P_C4); return r; }   // b limbs < 2^31, < 8p
-__device__ __forceinline__ f29 f29_sub_k16(const f29& a, const f29& b) { f29 r; F29_SUBK(r, a, b, F29_K16P_C2); return r; } // b limbs < 2^30, < 16p
+__device__ __forceinline__ f29 f29_sub_k2(const f29& a, const f29& b) { f29 r; F29_SUBK(r, a, b, F29_K2P_C1); return r; }   // b normalised, < 2p - 2^232
+__device__ __forceinline__ f29 f29_sub_k4(const f29& a, const f29& b) { f29 r; F29_SUBK(r, a, b, F29_K4P_C2); return r; }   // b limbs < 2^30 - 1, < 4p - 2^233
+__device__ __forceinline__ f29 f29_sub_k8(const f29& a, const f29& b) { f29 r; F29_SUBK(r, a, b, F29_K8P_C4); return r; }   // b limbs < 2^31 - 3, < 8p - 2^234
+__device__ __forceinline__ f29 f29_sub_k16(const f29& a, const f29& b) { f29 r; F29_SUBK(r, a, b, F29_K16P_C2); return r; } // b limbs < 2^30 - 1, < 16p - 2^233
 
-// parallel carry pass: limbs < 2^32 -> limbs < 2^29 + 8 (top limb absorbs), value unchanged
+// parallel carry pass: limbs < 2^32 -> limbs < 2^29 + 8, value unchanged.  The top limb absorbs the carry of limb 7 unmasked, so it
+// has to be below 2^32 - 7 on entry (every caller's top limb is below 2^30).
 __device__ __forceinline__ f29 f29_qnorm(const f29& a) {
     f29 r;
     r.v[0] = a.v[0] & F29_MASK;

@@ -234,7 +234,7 @@ __global__ void __launch_bounds__(256, 2) k_encode_out_dot(const fr* __restrict_
     fr* out = part + (size_t)blockIdx.y * K + q2;
 #pragma unroll
     for (int q1 = 0; q1 < 8; q1++) {
-        f29 v = f29_montmul(f29_qnorm(acc[q1]), f29_const_r2());          // plain value, < 1.2p
+        f29 v = f29_montmul(f29_qnorm(acc[q1]), f29_const_r2());          // plain value, < 2p (p + 1.2p*group*p/2^261)
         v = f29_reduce_2p(f29_add(v, unpack29(fr_load(out + (size_t)B * q1))));
         fr_store(out + (size_t)B * q1, pack29(v));
     }

@@ -14,7 +14,9 @@ namespace lig {
 //   lin_part[g][j]  = sum_r U[r][j*ues] * Rn[r][j]                                                if Rn  != null
 // U rows are urs elements apart and read with element stride ues (ues = 2 picks the codeword values on the
 // order-2k subgroup <w_n^2>), Rn rows are rrs elements apart.  Products are added lazily (limbs renormalised every
-// 6 terms, value < 1.2p * group <= 2^261 for group <= 128).
+// 6 terms, value < 1.2p * group <= 2^261 for group <= 128).  The linear sum goes back to a plain value through one
+// f29_montmul with a < 1.2p * group, which gives < p + 0.0071p * group: below 2p up to group = 128, not below 1.2p
+// (tools/check_fr29.py: check_accumulation).
 __global__ void __launch_bounds__(256) k_rlc_partial(const fr* __restrict__ U, size_t urs, uint32_t ues, const fr* __restrict__ Rn,
                                                      size_t rrs, size_t rows, uint32_t count, const f29s* __restrict__ rc,
                                                      uint32_t group_rows, fr* __restrict__ code_part, fr* __restrict__ lin_part, int accumulate) {
@@ -33,7 +35,7 @@ __global__ void __launch_bounds__(256) k_rlc_partial(const fr* __restrict__ U, s
     }
     if (rc != nullptr) fr_store(code_part + (size_t)blockIdx.y * count + j, pack29(f29_reduce_2p(ac)));
     if (Rn != nullptr) {
-        f29 v = f29_montmul(f29_qnorm(al), f29_const_r2());                                                     // plain value, < 1.2p
+        f29 v = f29_montmul(f29_qnorm(al), f29_const_r2());                                                     // plain value, < 2p (p + 1.2p*group*p/2^261)
         if (accumulate) v = f29_reduce_2p(f29_add(v, unpack29(fr_load(lin_part + (size_t)blockIdx.y * count + j))));
         fr_store(lin_part + (size_t)blockIdx.y * count + j, pack29(v));
     }
