@@ -452,6 +452,45 @@ int  lig_rows_verify_set_linear_values(lig_vtrace *trace, const uint8_t *coefs, 
 int  lig_linear_program_form(lig_ctx *ctx, const lig_linear_program *p, const uint8_t key32[32], const uint8_t *coefs, uint64_t n_coefs,
                              void *rands_dev, uint8_t const_sum[32]);
 
+/* ---- which constraints does the committed witness violate?  (csrc/diagnose.hip)
+ * Upstream a bad witness is caught while the guest runs: constrain_equal / constrain_bit assert on the values
+ * (include/zkp/backend/witness_manager.hpp:418-431).  A caller of the entries above no longer runs that code, and what is left are
+ * the prover's self-check bits: valid_linear is ONE bit computed from a random combination, valid_quad is vacuous for a derived
+ * triple (LIG_ELEM_PRODUCT).  lig_rows_diagnose evaluates the statement itself on the committed witness matrix -- exactly, without
+ * randomness -- and names the violated constraints.
+ *   linear     res_c = sum_j a_cj * w[slot_cj] - b_c mod p (canonical) for every constraint c of `sys`, over the data slots of the
+ *              committed trace (derived rows included); b_c = the table entry named by rhs_coef when c is in rhs_constraint, else 0.
+ *              The coefficient table is sys->coefs AS PASSED HERE (a caller of lig_rows_set_linear_values passes that statement's
+ *              values).  sys goes through lig_linear_check against the trace's kinds before anything is launched (LIG_E_ARG); the
+ *              system or program attached to the trace is neither used nor modified.  sys == NULL: the quadratic part only.
+ *   quadratic  for every quadratic-test term of the job in commit order -- a QX,QY,QZ / BQX,BQY,BQZ triple: x[i] * y[i] - z[i]; a BIT
+ *              row b (row_x = row_y = row_z = that row): b[i] * b[i] - b[i]; an EQX,EQY pair: x[i] - z[i] with row_y = 0xFFFFFFFF
+ *              and row_z = the EQY row -- and every column i < l.  Row numbers count the job's committed rows (masks excluded).
+ *   output     the first lin_cap violated constraints in ascending constraint number, the first quad_cap violated (term, column)
+ *              pairs in ascending (term, column) order: the same bytes on every run.  The counts in *info cover ALL violations,
+ *              reported or not.  A cap of 0 (the array may then be NULL) gives counts only; NULL with a cap > 0 is LIG_E_ARG.
+ * WHEN: from the return of lig_rows_commit until the committed matrix is replaced -- by the next lig_rows_commit on the trace, or by
+ * a lig_rows_restart issued AFTER lig_rows_prove (it loads straight into the matrix); a lig_rows_restart between commit and prove
+ * writes the second matrix and does not end the window.  Before or after lig_rows_prove.  Outside the window, and for a trace made
+ * by lig_synth_prepare: LIG_E_STATE.  The call blocks, only reads the matrix and runs on the context stream; it changes nothing a
+ * proof depends on (the envelope of a diagnosed trace is byte-identical to that of one that was not).  Scratch is allocated inside
+ * the call and freed before it returns: this is not the proving path.  Its work is enqueued on the context stream alone, but freeing
+ * the scratch waits for the whole device: while the rows of a lig_rows_restart are still arriving, the call returns after them.
+ * info->ms_total is the whole call, the host pass of lig_linear_check over sys (one step per term) included.
+ * lig_shard_rows_* is NOT covered: a rank holds only the rows it was dealt and a constraint may span ranks.  There is no verifier
+ * side: the verifier has no witness. */
+typedef struct { uint32_t constraint, reserved; uint8_t residual[32]; } lig_diag_linear;          /* 40 bytes */
+typedef struct { uint32_t row_x, row_y, row_z, column; uint8_t residual[32]; } lig_diag_quad;     /* 48 bytes */
+typedef struct {
+    uint32_t struct_bytes, reserved;     /* sizeof(lig_diag_info) as the caller sees it; smaller than the library's: LIG_E_ARG */
+    uint64_t n_linear_bad;               /* constraints of sys with a nonzero residual (all of them, not only the reported ones) */
+    uint64_t n_quad_bad;                 /* (quadratic term, column < l) pairs with a nonzero residual */
+    uint64_t n_linear_reported, n_quad_reported;
+    double   ms_total;                   /* wall time of the call */
+} lig_diag_info;
+int lig_rows_diagnose(lig_trace *trace, const lig_linear_system *sys, lig_diag_linear *lin_out, uint64_t lin_cap,
+                      lig_diag_quad *quad_out, uint64_t quad_cap, lig_diag_info *info);
+
 /* ==== proof file framing (src/webgpu_prover.cpp:437-457 writes gzip(level 6) of the serialized envelope with
  * Boost.iostreams; src/webgpu_verifier.cpp:249-253 reads it back).  Host-only helpers on zlib: the output is a standard
  * gzip member that any gzip reader (the reference's gzip_decompressor included) accepts; compressed BYTES depend on the

@@ -297,6 +297,21 @@ public:
         pass_ = 3;
         return proof;
     }
+    // ---- when valid_linear or valid_quad came out 0 (or before prove(), to save the proof): WHICH constraints does the committed
+    // witness violate?  lig_rows_diagnose (lig_hip.h) with the system given to set_linear_system -- with the table of
+    // set_linear_values, if one was set -- after commit(), before or after prove(), until the next commit().  A batcher that was
+    // given a prepared program (set_linear_program) or no system has no term list to evaluate: the quadratic part only.  Upstream
+    // the same witness would have tripped the asserts of constrain_equal / constrain_bit while the guest ran
+    // (witness_manager.hpp:418-431).  Not for a sharded batcher (a constraint may span ranks).
+    void diagnose(lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
+        if (sharded_) throw std::logic_error("hip_row_batcher::diagnose: not for a sharded batcher");
+        if (pass_ == 1 || !trace_) throw std::logic_error("hip_row_batcher::diagnose before commit");
+        if (!info) throw std::invalid_argument("hip_row_batcher::diagnose: null info");
+        lig_linear_system sys = *linear_.get();
+        if (values_set_) { sys.coefs = values_.data(); sys.n_coefs = values_.size() / 32; }
+        info->struct_bytes = sizeof(lig_diag_info);
+        check(lig_rows_diagnose(trace_, linear_.is_set() ? &sys : nullptr, lin_out, lin_cap, quad_out, quad_cap, info), "lig_rows_diagnose");
+    }
     // the next proof with this batcher: staging and (for the same row kinds) every device buffer of the trace are kept
     void reset(const hip_proof_meta* meta = nullptr) {
         if (pass_ == 2) throw std::logic_error("hip_row_batcher::reset between commit and prove");

@@ -42,6 +42,7 @@ EXPORTS = [
     "lig_shard_rows_set_linear", "lig_shard_rows_linear_stats", "lig_linear_shard_count",
     "lig_linear_prepare", "lig_linear_program_release", "lig_linear_program_bytes", "lig_rows_attach_linear", "lig_rows_verify_attach_linear",
     "lig_rows_set_linear_values", "lig_rows_verify_set_linear_values", "lig_linear_program_form",
+    "lig_rows_diagnose",
 ]
 
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
@@ -201,6 +202,17 @@ class LinearProgram:
             pass
 
 
+class DiagInfo(C.Structure):
+    """lig_diag_info: the counts cover every violation, the *_reported ones what fitted the caps"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("reserved", C.c_uint32), ("n_linear_bad", C.c_uint64), ("n_quad_bad", C.c_uint64),
+                ("n_linear_reported", C.c_uint64), ("n_quad_reported", C.c_uint64), ("ms_total", C.c_double)]
+
+
+# lig_diag_linear (40 bytes) / lig_diag_quad (48 bytes) as numpy records; residual = 32 little-endian bytes, canonical
+DIAG_LINEAR = np.dtype([("constraint", "<u4"), ("reserved", "<u4"), ("residual", "u1", (32,))])
+DIAG_QUAD = np.dtype([("row_x", "<u4"), ("row_y", "<u4"), ("row_z", "<u4"), ("column", "<u4"), ("residual", "u1", (32,))])
+
+
 class ProofInfo(C.Structure):
     _fields_ = [("root", C.c_uint8 * 32), ("stage1_seed", C.c_uint8 * 32), ("stage2_seed", C.c_uint8 * 32),
                 ("const_sum", C.c_uint8 * 32), ("rows", C.c_uint64), ("valid_code", C.c_int32),
@@ -348,6 +360,7 @@ def load_library():
     L.lig_rows_set_linear_values.argtypes = [vp, vp, u64]
     L.lig_rows_verify_set_linear_values.argtypes = [vp, vp, u64]
     L.lig_linear_program_form.argtypes = [vp, vp, vp, vp, u64, vp, vp]
+    L.lig_rows_diagnose.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, u64, C.POINTER(DiagInfo)]
     return L
 
 
@@ -972,6 +985,17 @@ class Context:
         self.check(self.L.lig_linear_program_form(self.h, program._handle(), _hptr(kb), _hptr(tab) if tab is not None and len(tab) else None,
                                                   len(tab) if tab is not None else 0, out, _hptr(cs)))
         return cs.tobytes()
+
+    def rows_diagnose(self, trace, system=None, lin_cap=1024, quad_cap=1024):
+        """lig_rows_diagnose: which constraints of `system` (None: the quadratic part only) and which quadratic terms does the committed
+        witness violate -> (DiagInfo, linear records, quadratic records): numpy record arrays (DIAG_LINEAR, DIAG_QUAD) of the first
+        lin_cap / quad_cap violations in ascending order; the counts in DiagInfo cover all of them"""
+        info = DiagInfo()
+        info.struct_bytes = C.sizeof(DiagInfo)
+        lin, quad = np.zeros(lin_cap, dtype=DIAG_LINEAR), np.zeros(quad_cap, dtype=DIAG_QUAD)
+        self.check(self.L.lig_rows_diagnose(trace, C.byref(system) if system is not None else None, _hptr(lin) if lin_cap else None, lin_cap,
+                                            _hptr(quad) if quad_cap else None, quad_cap, C.byref(info)))
+        return info, lin[:info.n_linear_reported], quad[:info.n_quad_reported]
 
     def vtrace_destroy(self, vtrace):
         """give up a verification between begin and finish (finish frees the trace itself)"""

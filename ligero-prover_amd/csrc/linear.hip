@@ -32,12 +32,11 @@
 
 #include <rocprim/device/device_scan.hpp>
 
+#include "lin_common.hpp"
 #include "prover_common.hpp"
 
 namespace lig {
-static constexpr uint32_t LIN_WG = 256;
-static constexpr uint32_t HEAVY_MIN = 2048;       // a slot with more terms than this is summed by HEAVY_PARTS workgroups
-static constexpr uint32_t HEAVY_PARTS = 32;
+static constexpr uint32_t HEAVY_PARTS = 32;       // a slot with more than HEAVY_MIN terms is summed by this many workgroups
 static constexpr uint32_t CONST_BLOCKS = 256;     // partial sums of the constant (one per workgroup), reduced by a last block
 
 // ---------------------------------------------------------------- prepare
@@ -125,16 +124,6 @@ static __device__ __forceinline__ fr lin_accumulate(const fr& acc, const uint2 e
     if (e.y == LIG_COEF_NEG_ONE) return fr_sub(acc, v);
     return fr_add(acc, fr_montmul(v, fr_load(coef_mont + e.y)));      // (a R) * r / R = a * r, canonical
 }
-// sum of the workgroup's LIN_WG values (fixed tree: the same bytes on every run); valid in thread 0
-static __device__ __forceinline__ fr lin_block_sum(fr v, fr* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (uint32_t w = LIN_WG / 2; w; w >>= 1) {
-        if (threadIdx.x < w) sh[threadIdx.x] = fr_add(sh[threadIdx.x], sh[threadIdx.x + w]);
-        __syncthreads();
-    }
-    return sh[0];
-}
 // lane = slot `col` of touched row trows[blockIdx.y + ...]; heavy slots are left to k_lin_heavy_*
 __global__ void __launch_bounds__(LIN_WG) k_lin_form(const uint32_t* __restrict__ trows, uint32_t n_trows, uint32_t l, uint32_t k,
                                                      const uint32_t* __restrict__ begin, const uint2* __restrict__ ent, const fr* __restrict__ r,
@@ -194,10 +183,14 @@ __global__ void __launch_bounds__(LIN_WG) k_lin_const_fin(const fr* __restrict__
 }
 // per-proof coefficient table (lig_rows_set_linear_values): canonical -> Montgomery form in place, one lane per entry, a * R^2 / R = a R;
 // 16-byte loads and stores (fr_load / fr_store), no LDS, no atomics; the host has checked every entry < p
-static constexpr uint32_t COEFS_MAX_BLOCKS = 1024;
 __global__ void __launch_bounds__(LIN_WG) k_lin_coefs_mont(fr* __restrict__ tab, uint64_t n) {
     const fr r2 = fr_const(FR_R2);
     for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG) fr_store(tab + i, fr_montmul(fr_load(tab + i), r2));
+}
+void launch_lin_coefs_mont(hipStream_t st, fr* tab, uint64_t n) {
+    if (!n) return;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + LIN_WG - 1) / LIN_WG, COEFS_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_lin_coefs_mont, dim3(blocks), dim3(LIN_WG), 0, st, tab, n);
 }
 }  // namespace lig
 
@@ -511,8 +504,7 @@ int lig_internal_linear_set_values(lig_ctx* c, lig_linear* L, const uint8_t* coe
     std::memcpy(L->h_vals, coefs, bytes);
     HIP_TRY(c, hipMemcpyAsync(L->vals, L->h_vals, bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipEventRecord(L->ev_vals, st));
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_coefs + lig::LIN_WG - 1) / lig::LIN_WG, lig::COEFS_MAX_BLOCKS);
-    hipLaunchKernelGGL(lig::k_lin_coefs_mont, dim3(blocks), dim3(lig::LIN_WG), 0, st, L->vals, n_coefs);
+    lig::launch_lin_coefs_mont(st, L->vals, n_coefs);
     HIP_TRY(c, hipGetLastError());
     L->coef = L->vals;
     return LIG_OK;

@@ -28,6 +28,7 @@ struct lig_trace {
     bool from_rows = false;             // rows supplied by the caller (lig_rows_*): no witness generation here
     bool loaded = false, committed = false;   // lig_rows_*: rows for the next commit are loaded / stage 1 done, proof pending
     bool dense_rands = false;           // lig_rows_job.dense_rands_per_row given: randomness rows may be generated here
+    bool diag_ok = false;               // `msgs` holds a committed trace (lig_rows_diagnose): from lig_rows_commit until the matrix is replaced
     fr* msgs_alt = nullptr;             // second message matrix: the next trace is uploaded while the current one is proved
     bool alt_pending = false;           // the rows for the next commit are (arriving) in msgs_alt
     JobHeader hdr;
@@ -109,6 +110,7 @@ static hipError_t wait_event(hipEvent_t ev) {
         if ((spins & 255) == 255 && ms_since(t0) > (double)lig::knobs().spin_wait_ms) return hipEventSynchronize(ev);
     }
 }
+hipError_t lig_internal_wait_stream(hipStream_t st) { return wait_stream(st); }      // (diagnose.hip waits the way a proof does)
 static void uploader_drain(lig_trace* T);      // (below, with the uploader thread)
 static void rand_drain(lig_trace* T);
 static int ensure_up_flags(lig_ctx* c, lig_trace* T);
@@ -1081,6 +1083,7 @@ int lig_rows_restart(lig_trace* T, const void* msgs, int msgs_on_device) {
     if (T->R && !msgs) FAIL(c, LIG_E_ARG, "lig_rows_restart: null rows");
     if (T->leak) FAIL(c, LIG_E_STATE, "lig_rows_restart: a transfer into this trace's buffers never completed (lig_upload_health): destroy the trace");
     if (T->loaded && T->host_msgs) { uploader_drain(T); if (c->stream3) HIP_TRY(c, hipStreamSynchronize(c->stream3)); }      // an upload nobody committed: let it finish first
+    if (!T->committed) T->diag_ok = false;                // the rows go straight into the matrix: the window of lig_rows_diagnose ends
     return rows_load(c, T, msgs, msgs_on_device != 0);
 }
 int lig_rows_commit(lig_trace* T, uint8_t root[32], uint8_t stage1_seed[32]) {
@@ -1089,6 +1092,7 @@ int lig_rows_commit(lig_trace* T, uint8_t root[32], uint8_t stage1_seed[32]) {
     CHECK_CTX(c);
     if (!T->from_rows || !T->loaded) FAIL(c, LIG_E_STATE, "lig_rows_commit: no rows loaded (lig_rows_begin / lig_rows_restart)");
     if (T->committed) FAIL(c, LIG_E_STATE, "lig_rows_commit: the committed trace has not been proved yet");
+    T->diag_ok = false;
     if (T->alt_pending) { std::swap(T->msgs, T->msgs_alt); T->alt_pending = false; }
     std::memset(&T->info1, 0, sizeof T->info1);
     T->info1.rows = T->R + 3;
@@ -1122,6 +1126,7 @@ int lig_rows_commit(lig_trace* T, uint8_t root[32], uint8_t stage1_seed[32]) {
     }
     T->info1.ms_stage1 = ms_since(t_begin);
     T->committed = true;
+    T->diag_ok = true;
     T->loaded = false;
     T->host_msgs = nullptr;                               // the caller's memory is no longer referenced
     if (root) std::memcpy(root, T->info1.root, 32);
@@ -1260,6 +1265,29 @@ int lig_rows_set_linear_values(lig_trace* T, const uint8_t* coefs, uint64_t n_co
     CHECK_CTX(c);
     if (!T->from_rows || !T->linear) FAIL(c, LIG_E_STATE, "lig_rows_set_linear_values: no linear program is attached (lig_rows_attach_linear)");
     return lig_internal_linear_set_values(c, T->linear, coefs, n_coefs, c->stream2);      // the stream lig_rows_prove forms on
+}
+
+// which constraints does the committed witness violate (diagnose.hip); blocking, reads T->msgs only, main stream only
+int lig_rows_diagnose(lig_trace* T, const lig_linear_system* sys, lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap,
+                      lig_diag_info* info) {
+    if (!T || !info || info->struct_bytes < sizeof(lig_diag_info)) return LIG_E_ARG;
+    if ((lin_cap && !lin_out) || (quad_cap && !quad_out)) return LIG_E_ARG;
+    const auto t_begin = clk::now();                      // ms_total is the whole call: the host check of the system included
+    lig_ctx* c = T->c;
+    CHECK_CTX(c);
+    if (!T->from_rows) FAIL(c, LIG_E_STATE, "lig_rows_diagnose: not a rows trace");
+    if (!T->diag_ok) FAIL(c, LIG_E_STATE, "lig_rows_diagnose: no committed matrix (between lig_rows_commit and the next commit, or a lig_rows_restart after lig_rows_prove)");
+    if (sys) {
+        std::vector<uint8_t> kinds(T->R);
+        for (size_t r = 0; r < T->R; r++) kinds[r] = T->rows[r].kind;
+        if (lig_linear_check(sys, kinds.data(), T->R, c->l) != LIG_OK) FAIL(c, LIG_E_ARG, "lig_rows_diagnose: linear system rejected by lig_linear_check");
+    }
+    const uint32_t struct_bytes = info->struct_bytes;
+    std::memset(info, 0, sizeof *info);
+    info->struct_bytes = struct_bytes;
+    TRY(lig_internal_rows_diagnose(c, T->msgs, T->R, T->tri_dev, T->triples.size() / 3, sys, lin_out, lin_cap, quad_out, quad_cap, info));
+    info->ms_total = ms_since(t_begin);
+    return LIG_OK;
 }
 
 int lig_rows_push_rands(lig_trace* T, uint64_t first_row, uint64_t n_rows, const void* host_rows) {

@@ -445,6 +445,13 @@ void lig_internal_linear_stats(const lig_linear* L, uint64_t* local_terms, uint6
 const fr* lig_internal_linear_partial_dev(const lig_linear* L);
 uint8_t* lig_internal_linear_const_buf(lig_linear* L);
 
+// lig_rows_diagnose (diagnose.hip): the residual of every linear constraint of `sys` (NULL: none; it has passed lig_linear_check) and of every
+// (quadratic term, column < l) over the committed rows x k matrix `msgs`; tri_dev = the trace's quadratic terms, 3 row indices each.
+// Blocking, on the context's main stream; waits the way a proof does (lig_internal_wait_stream, prover.hip).
+int lig_internal_rows_diagnose(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* tri_dev, uint64_t n_quad_terms, const lig_linear_system* sys,
+                               lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info);
+hipError_t lig_internal_wait_stream(hipStream_t st);
+
 // the batch program of a job on the device: committed rows are written to rows_out in program order (prover.hip)
 int lig_run_batch_program(lig_ctx* c, const lig_synth_job& job, fr* rows_out);
 // witness values of the synthetic stream rows [first, rows.size()) (one draw of the witness_key stream per data slot of every
