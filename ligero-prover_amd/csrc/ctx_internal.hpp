@@ -65,6 +65,8 @@ inline hipStream_t lig_internal_copy_stream(lig_ctx* c) {
     if (!c->stream3 && hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); c->stream3 = c->stream; c->copy_is_main = true; }
     return c->stream3;
 }
+// blocking: everything queued on the context's streams (the ones it has) is done
+inline void sync_all_streams(lig_ctx* c) { for (hipStream_t st : {c->stream, c->stream2, c->stream3, c->stream_sha}) if (st) (void)hipStreamSynchronize(st); }
 inline void lig_internal_set_debug_state(lig_ctx* c, std::function<std::string()> f) { std::lock_guard<std::mutex> lk(c->debug_mu); c->debug_state = std::move(f); }
 inline std::string lig_internal_debug_state(lig_ctx* c) { std::lock_guard<std::mutex> lk(c->debug_mu); return c->debug_state ? c->debug_state() : std::string(); }
 

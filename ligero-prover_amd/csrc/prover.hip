@@ -13,14 +13,9 @@
 // constraint stream of BASELINE.md 3: n_linear witness slots + n_quad slots of x*y=z, one dense linear-test
 // coefficient per witness.
 #include "prover_common.hpp"
+#include "upload.hpp"
 #include <cerrno>
 #include <functional>
-#include <atomic>
-#include <condition_variable>
-#include <deque>
-#include <memory>
-#include <mutex>
-#include <thread>
 
 struct lig_trace {
     lig_ctx* c = nullptr;
@@ -38,22 +33,18 @@ struct lig_trace {
     std::vector<std::pair<size_t, size_t>> sched1;     // stage-1 chunk schedule
     const uint8_t* host_msgs = nullptr; // lig_rows_begin with host memory: uploaded chunk by chunk under the encodes
     std::vector<hipEvent_t> ev_up;      // one per stage-1 chunk: its rows have arrived (per-context copy stream, LIG_UPLOAD_MODE=1)
-    volatile uint32_t* up_flag = nullptr; uint32_t* up_flag_dev = nullptr;   // pinned: word ci = sequence number of the last upload whose chunk ci has arrived
-    uint32_t up_seq = 0;                // sequence number of the last witness-rows upload (what stage 1 waits for)
-    uint32_t rand_seq = 0;              // ... of the last randomness-rows upload (its own flag words, its own counter: a restart
-                                        // between commit and prove must not move what the next commit waits for)
+    FlagPage flags;                     // pinned: word ci = sequence number of the last upload whose chunk ci has arrived; then the words of flag_layout()
+    UploadLane up, rand;                // witness rows (what stage 1 waits for) | randomness rows, kept apart: a restart between commit and prove must not move what
+                                        // the next commit waits for, and lig_rows_prove must not wait for (or swallow the error of) the NEXT trace's witness prefetch
     bool up_by_thread = false;
     fr* rands_full = nullptr;           // lig_rows_push_rands / lig_rows_set_linear: R x k, device resident
     lig_linear* linear = nullptr;       // lig_rows_set_linear: the sparse linear system, regrouped by slot (linear.hip); survives lig_rows_restart
-    uint64_t rands_pushed = 0;          // rows handed to the uploader so far (word up_words - 1 counts the rows that have ARRIVED)
-    size_t up_words = 0;                // words in up_flag: [stage-1 chunks | stage-2 chunks: randomness rows arrived | ... consumed]
+    uint64_t rands_pushed = 0;          // rows handed to the uploader so far (the page's push word counts the rows that have ARRIVED)
     bool push_sync = false;             // lig_rows_push_rands without an uploader thread: the pushed rows were copied synchronously
     std::vector<UploadJob> push_log;    // the pushes of the committed trace (their host rows stay valid until lig_rows_prove returns): what a retry copies again
     bool up_retry = false;              // prove_stage1 failed because a witness-rows transfer timed out (LIG_UPLOAD_TIMEOUT_S): lig_rows_commit makes the upload again
     bool leak = false;                  // an abandoned transfer of this trace is still pending and cannot be cancelled: its buffers are never freed or reused
     std::atomic<int> up_abort{0};       // a failed lig_rows_prove: the uploader drops the randomness-row copies it still holds
-    std::atomic<int> up_pending{0};     // chunk copies of this trace the uploader thread still has to make
-    std::atomic<int> up_failed{0}, rand_pending{0}, rand_failed{0};      // hipError_t of a chunk copy that failed (the chunk is published all the same: no stream may hang)   -- rand_*: the same for randomness-row uploads, kept apart: lig_rows_prove must not wait for (or swallow the error of) the NEXT trace's witness prefetch
     // narrow row format (lig_rows_job.elem_bytes): packed byte offset of every row (+1 entry), the device staging
     // area the packed rows are uploaded to (expanded into `msgs` chunk by chunk in stage 1)
     bool narrow = false;
@@ -63,6 +54,8 @@ struct lig_trace {
     lig_proof_info info1;               // stage-1 results kept between lig_rows_commit and lig_rows_prove
     size_t R = 0, RB = 0, n_init = 0;   // all rows, leading rows committed by the batch program, of those: init rows
     fr* msgs = nullptr;                 // R x k witness matrix (pads are re-drawn by every prove)
+    // [stage-1 chunks: rows arrived | stage-2 chunks: randomness rows arrived | ... consumed]; n_chunks of the stage-2 schedule
+    lig::FlagLayout flag_layout(size_t n_chunks = 0) const { return lig::trace_flags(sched1.size(), R, lig_tune::CHUNK, n_chunks); }
     bool zres = false;                  // LIG_ZRES: `cw` holds the encoder's Z tiles (lig::ENC_ZRES) instead of planes -- K3 runs inside the column hash,
                                         // stage 2 / 3 take single radix-8 outputs from the tiles (linear rows only: a trace with quadratic triples keeps planes)
     fr* cw = nullptr;                   // R x 3k: cosets 1..3 of every codeword as planes (lig::ENC_PLANAR), resident across the stages;
@@ -90,30 +83,19 @@ struct lig_trace {
 // interrupt: every wake-up costs tens of microseconds during which the GPU has nothing of this proof to run.  LIG_SPIN_WAIT=1 (default)
 // polls instead (the calling thread yields between polls for LIG_SPIN_WAIT_MS, then falls back on the blocking wait): A/B in
 // profiles/r05_spin_wait_ab.md.
-static hipError_t wait_stream(hipStream_t st) {
-    if (!lig::knobs().spin_wait) return hipStreamSynchronize(st);
+template <class Query, class Sync> static hipError_t spin_wait(Query query, Sync sync) {
+    if (!lig::knobs().spin_wait) return sync();
     const auto t0 = clk::now();
     for (unsigned spins = 0;; spins++) {
-        const hipError_t e = hipStreamQuery(st);
+        const hipError_t e = query();
         if (e != hipErrorNotReady) return e;
         std::this_thread::yield();
-        if ((spins & 255) == 255 && ms_since(t0) > (double)lig::knobs().spin_wait_ms) return hipStreamSynchronize(st);
+        if ((spins & 255) == 255 && ms_since(t0) > (double)lig::knobs().spin_wait_ms) return sync();
     }
 }
-static hipError_t wait_event(hipEvent_t ev) {
-    if (!lig::knobs().spin_wait) return hipEventSynchronize(ev);
-    const auto t0 = clk::now();
-    for (unsigned spins = 0;; spins++) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e != hipErrorNotReady) return e;
-        std::this_thread::yield();
-        if ((spins & 255) == 255 && ms_since(t0) > (double)lig::knobs().spin_wait_ms) return hipEventSynchronize(ev);
-    }
-}
+static hipError_t wait_stream(hipStream_t st) { return spin_wait([st] { return hipStreamQuery(st); }, [st] { return hipStreamSynchronize(st); }); }
+static hipError_t wait_event(hipEvent_t ev) { return spin_wait([ev] { return hipEventQuery(ev); }, [ev] { return hipEventSynchronize(ev); }); }
 hipError_t lig_internal_wait_stream(hipStream_t st) { return wait_stream(st); }      // (diagnose.hip waits the way a proof does)
-static void uploader_drain(lig_trace* T);      // (below, with the uploader thread)
-static void rand_drain(lig_trace* T);
-static int ensure_up_flags(lig_ctx* c, lig_trace* T);
 
 // The batch program on the device (lig_hip.h, lig_batch_op): k-element variables in a slab, every operation one eltwise
 // kernel into a temporary + a copy (as vbn254fr_module does), every hook a device-to-device copy of the rows it names
@@ -333,7 +315,7 @@ static int prove_stage1(lig_trace* T, lig_proof_info* info, const std::function<
     auto pre = [&](size_t ci, hipStream_t s_enc) -> int {
         const size_t b = T->sched1[ci].first, nb = T->sched1[ci].second - b;
         if (streamed) {
-            if (T->up_by_thread) HIP_TRY(c, hipStreamWaitValue32(s_enc, T->up_flag_dev + ci, T->up_seq, hipStreamWaitValueGte, 0xffffffffu));
+            if (T->up_by_thread) HIP_TRY(c, hipStreamWaitValue32(s_enc, T->flags.dev + ci, T->up.seq, hipStreamWaitValueGte, 0xffffffffu));
             else HIP_TRY(c, hipStreamWaitEvent(s_enc, T->ev_up[ci], 0));                   // this chunk's rows have arrived
             // (a derived row whose x / y rows belong to the previous chunk reads them from the staging area: that chunk's arrival was waited for earlier on this stream)
             if (T->narrow) lig::launch_expand_rows(s_enc, T->packed_dev, T->src_off_dev, T->widths_dev, b, nb, l, k, T->msgs, T->prod.first(b), T->prod.count(b, b + nb));
@@ -407,7 +389,7 @@ static int prove_stage1(lig_trace* T, lig_proof_info* info, const std::function<
     HIP_TRY(c, wait_stream(s));
     if (streamed && T->up_by_thread) {
         // every chunk has been waited for by now; a copy the uploader thread could not make leaves garbage rows behind
-        if (const int e = T->up_failed.exchange(0)) {
+        if (const int e = T->up.take_error()) {
             T->up_retry = e == (int)hipErrorLaunchTimeOut;
             FAIL(c, LIG_E_HIP, std::string("rows upload failed: ") + hipGetErrorString((hipError_t)e));
         }
@@ -483,22 +465,15 @@ static int prove_stage23(lig_trace* T, const RandSource& rs, const uint8_t* cons
     // on the side stream that this replaces is LIG_UPLOAD_MODE=1, profiles/r04_caller_rands_ab.md).
     const bool rands_by_thread = rs.host && lig::knobs().upload_mode == 2 && lig::knobs().rands_upload_mode == 2 && lig_internal_uploader_available(c) && n_chunks;
     uint32_t rseq = 0;
-    size_t rflag0 = 0, uflag0 = 0;
+    const lig::FlagLayout fl = T->flag_layout(n_chunks);
     if (rands_by_thread) {
-        TRY(ensure_up_flags(c, T));
-        rflag0 = T->sched1.size(); uflag0 = rflag0 + n_chunks;
-        if (uflag0 + n_chunks > T->up_words) FAIL(c, LIG_E_STATE, "rows job: flag page too small for the stage-2 schedule");
-        rseq = ++T->rand_seq;
+        TRY(T->flags.ensure(c, fl.words));
+        if (fl.consumed + n_chunks > fl.words) FAIL(c, LIG_E_STATE, "rows job: flag page too small for the stage-2 schedule");
+        rseq = ++T->rand.seq;
         T->up_abort.store(0, std::memory_order_release);
-        std::vector<UploadJob> jobs;
-        for (size_t ci = 0; ci < n_chunks; ci++) {
-            const size_t b = sched2[ci].first, nb = sched2[ci].second - b;
-            UploadJob j{(uint8_t*)rand_buf(ci), rs.host + b * (size_t)k * 32, nb * (size_t)k * 32, T->up_flag + rflag0 + ci, rseq, &T->rand_failed};
-            if (ci >= 2) { j.wait = T->up_flag + uflag0 + ci - 2; j.wait_val = rseq; }
-            j.abort = &T->up_abort; j.prio = 1;
-            jobs.push_back(j);
-        }
-        lig_internal_uploader_submit(c->device, jobs, &T->rand_pending);
+        std::vector<lig::UploadChunk> chunks;
+        for (size_t ci = 0; ci < n_chunks; ci++) chunks.push_back({(uint8_t*)rand_buf(ci), rs.host + sched2[ci].first * (size_t)k * 32, (sched2[ci].second - sched2[ci].first) * (size_t)k * 32});
+        lig_internal_uploader_submit(c->device, lig::chunk_jobs(chunks, T->flags.host + fl.rands, rseq, &T->rand.failed, T->flags.host + fl.consumed, &T->up_abort, 1), &T->rand.pending);
     }
     auto form_rand_chunk = [&](size_t ci) -> int {        // enqueued on the side stream
         const size_t b = sched2[ci].first, nb = sched2[ci].second - sched2[ci].first;
@@ -556,8 +531,8 @@ static int prove_stage23(lig_trace* T, const RandSource& rs, const uint8_t* cons
         const size_t b = sched2[ci].first, nb = sched2[ci].second - sched2[ci].first;
         fr* rb = rand_buf(ci);
         if (ci + 1 < n_chunks) TRY(form_rand_chunk(ci + 1));
-        if (rs.pushed && !T->push_sync) HIP_TRY(c, hipStreamWaitValue32(s, T->up_flag_dev + T->up_words - 1, (uint32_t)sched2[ci].second, hipStreamWaitValueGte, 0xffffffffu));
-        else if (rands_by_thread) HIP_TRY(c, hipStreamWaitValue32(s, T->up_flag_dev + rflag0 + ci, rseq, hipStreamWaitValueGte, 0xffffffffu));
+        if (rs.pushed && !T->push_sync) HIP_TRY(c, hipStreamWaitValue32(s, T->flags.dev + fl.push, (uint32_t)sched2[ci].second, hipStreamWaitValueGte, 0xffffffffu));
+        else if (rands_by_thread) HIP_TRY(c, hipStreamWaitValue32(s, T->flags.dev + fl.rands + ci, rseq, hipStreamWaitValueGte, 0xffffffffu));
         else HIP_TRY(c, hipStreamWaitEvent(s, T->ev_ready[ci & 1], 0));
         if (c->fast) {
             // coset-2 values of the randomness rows times the coset-2 plane of the codewords, summed per group of rows inside the
@@ -569,7 +544,7 @@ static int prove_stage23(lig_trace* T, const RandSource& rs, const uint8_t* cons
         }
         // k columns per pass: groups of 16 rows (4x more workgroups than the n-column grouping; same partial-sum space)
         if (!fused_rlc) lig::launch_rlc_accumulate29(s, T->msgs + b * k, k, 1, rb, k, nb, k, rc_loop ? rc_loop + b : nullptr, p_code, p_linH, lig_tune::GROUP / 4);
-        if (rands_by_thread) HIP_TRY(c, hipStreamWriteValue32(s, T->up_flag_dev + uflag0 + ci, rseq, 0));      // chunk consumed: its half of the buffer is free
+        if (rands_by_thread) HIP_TRY(c, hipStreamWriteValue32(s, T->flags.dev + fl.consumed + ci, rseq, 0));      // chunk consumed: its half of the buffer is free
         else HIP_TRY(c, hipEventRecord(T->ev_used[ci & 1], s));
     }
     {   // one combine per accumulator and proof
@@ -719,13 +694,10 @@ static int synth_prepare_impl(lig_ctx* c, const lig_synth_job* job, lig_trace* T
 void lig_trace_destroy(lig_trace* T) {
     if (!T) return;
     (void)hipSetDevice(T->c->device);
-    (void)hipStreamSynchronize(T->c->stream);
-    (void)hipStreamSynchronize(T->c->stream2);
-    if (T->c->stream3) (void)hipStreamSynchronize(T->c->stream3);
+    sync_all_streams(T->c);
     T->up_abort.store(1, std::memory_order_release);      // (copies that wait for a buffer of a proof that never ran)
-    uploader_drain(T);                                    // an upload still in flight
-    rand_drain(T);
-    if (T->c->stream_sha) (void)hipStreamSynchronize(T->c->stream_sha);      // (experiment knob LIG_SHA_CUMASK: the stage-1 hash stream)
+    T->up.drain();                                        // an upload still in flight
+    T->rand.drain();
     lig_internal_linear_destroy(T->linear);
     T->c->sha.erase(T->sha_state);
     if (T->leak) {      // destinations of a transfer that was given up on and has never completed (upload_settled): they outlive the trace
@@ -740,7 +712,7 @@ void lig_trace_destroy(lig_trace* T) {
     if (T->ev_k1) (void)hipEventDestroy(T->ev_k1);
     for (int a3 = 0; a3 < 3; a3++) if (T->ev_acc[a3]) (void)hipEventDestroy(T->ev_acc[a3]);
     for (hipEvent_t e : T->ev_up) (void)hipEventDestroy(e);
-    if (T->up_flag) (void)hipHostFree((void*)T->up_flag);
+    T->flags.release();
     (void)hipFree(T->src_off_dev); (void)hipFree(T->widths_dev); (void)hipFree(T->packed_dev); (void)hipFree(T->prod.dev);
     (void)hipHostFree(T->h_proof); (void)hipHostFree(T->h_enc); (void)hipHostFree(T->h_nodes); (void)hipHostFree(T->h_small);
     delete T;
@@ -764,211 +736,37 @@ int lig_synth_prove(lig_trace* T, const uint8_t** proof, size_t* proof_len, lig_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Host rows -> device without a HIP stream of the prover in the path.
-//
-// What was measured (tools/time_rows2.py, tools/h2d_under_load.py; profiles/r03_h2d_pipeline.md): the PCIe link delivers
-// 57 GB/s to this process whatever the GPU is doing (550 MB = one 2^24-constraint trace in 9.7 ms, idle or under two proving
-// contexts), and a foreign stream's upload does not slow the proofs down.  The prover's own chunked upload did: HIP maps the
-// streams of a process onto GPU_MAX_HW_QUEUES = 4 hardware queues, every event recorded behind a copy (and every wait for one)
-// is a barrier packet in such a queue, and while it waits for a 2 ms .. 10 ms transfer the kernels of whichever proof stream
-// shares the queue do not start (stage 2 of a proof 4.9 -> 10-16 ms; two alternating contexts: 12.8 ms per proof, slower
-// than one).  Priorities (own queue pool) and a shared copy stream move the problem around (A/B table in the profile).
-// So: one uploader thread per device copies chunk after chunk on a stream of its own and waits for each copy ON THE HOST
-// (no event, no packet behind the copy), then publishes the chunk's arrival in pinned host memory; the encode stream of the
-// trace waits for that word with a stream memory operation (hipStreamWaitValue32 -- a wait in ITS OWN queue, where it has to
-// wait anyway).  Uploads of all contexts go through the one thread: one at a time, in the order of the calls -- two contexts
-// that alternate keep the link busy without ever sharing it.
-namespace {
-struct Uploader {
-    std::atomic<uint64_t> cur_bytes{0}, cur_since_us{0}, done_jobs{0};      // diagnostics
-    std::atomic<int> phase{0};                                              // 0 idle, 1 copy call, 2 waiting for the copy, 3 publishing
-    std::atomic<bool> broken{false};                                        // a transfer timed out: no further jobs
-    bool fault_done = false;                                                // LIG_FAULT_UPLOAD: the injected fault has been spent
-    std::atomic<uint32_t> abandoned{0};                                     // transfers given up on that may still be in flight on `st` (cleared by settle())
-    std::atomic<uint32_t> retries{0};                                       // calls that re-made a timed-out upload with stream-ordered copies
-    // The copy this thread stopped waiting for is still queued on `st` and cannot be cancelled.  settle(): has it finished by now?  (Bounded
-    // poll from the calling thread; hipStreamQuery is thread-safe.)  Until it has, its source rows and its destination must stay alive.
-    bool settle(double seconds) {
-        if (!abandoned.load(std::memory_order_acquire)) return true;
-        const auto t0 = clk::now();
-        for (;;) {
-            const hipError_t e = hipStreamQuery(st);
-            if (e != hipErrorNotReady) { (void)hipGetLastError(); abandoned.store(0, std::memory_order_release); return true; }
-            if (std::chrono::duration<double>(clk::now() - t0).count() > seconds) return false;
-            std::this_thread::sleep_for(std::chrono::microseconds(200));
-        }
-    }
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<std::pair<UploadJob, std::atomic<int>*>> q;
-    std::thread th;
-    hipStream_t st = nullptr;
-    int device = 0;
-    bool ok = false;
-    void run() {
-        if (hipSetDevice(device) != hipSuccess) return;
-        for (;;) {
-            std::pair<UploadJob, std::atomic<int>*> j;
-            {
-                // the first job whose destination is free: a job that waits for its buffer must not hold up the other contexts'
-                // uploads queued behind it (jobs of one trace stay in order: their wait words become true in order)
-                std::unique_lock<std::mutex> lk(mu);
-                for (;;) {
-                    auto it = q.end();
-                    for (auto i2 = q.begin(); i2 != q.end(); ++i2) {
-                        const UploadJob& u = i2->first;
-                        const bool ready = !u.wait || (int32_t)(__atomic_load_n(u.wait, __ATOMIC_ACQUIRE) - u.wait_val) >= 0 || (u.abort && u.abort->load(std::memory_order_acquire));
-                        if (!ready) continue;
-                        if (it == q.end()) it = i2;                                  // the oldest ready job ...
-                        if (u.prio > it->first.prio) { it = i2; break; }             // ... unless a ready one is urgent
-                    }
-                    if (it != q.end()) { j = *it; q.erase(it); break; }
-                    if (q.empty()) cv.wait(lk, [&] { return !q.empty(); });
-                    else cv.wait_for(lk, std::chrono::microseconds(20));       // every queued job waits for the GPU: poll
-                }
-            }
-            const bool dead = broken.load(std::memory_order_acquire);             // jobs queued behind a transfer that timed out fail at once
-            const bool skip = dead || (j.first.abort && j.first.abort->load(std::memory_order_acquire));
-            cur_bytes.store(j.first.bytes, std::memory_order_relaxed);
-            cur_since_us.store((uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now().time_since_epoch()).count(), std::memory_order_relaxed);
-            phase.store(1, std::memory_order_release);
-            hipError_t e = dead ? hipErrorLaunchTimeOut : hipSuccess;
-            if (!skip && j.first.segs) {
-                for (const UploadSeg& g : *j.first.segs) {
-                    if (!g.bytes || e != hipSuccess) continue;
-                    e = g.src ? hipMemcpyAsync(g.dst, g.src, g.bytes, hipMemcpyHostToDevice, st) : hipMemsetAsync(g.dst, 0, g.bytes, st);
-                }
-            } else if (!skip && j.first.bytes) e = hipMemcpyAsync(j.first.dst, j.first.src, j.first.bytes, hipMemcpyHostToDevice, st);
-            phase.store(2, std::memory_order_release);
-            // bounded: a transfer that does not complete (seen with several processes on one GPU, profiles/r05_rows_entry_hang.md) must
-            // not hang every stream that waits for its word -- after LIG_UPLOAD_TIMEOUT_S the job is reported as failed (the word is
-            // published; lig_rows_commit / _prove let their streams drain, wait -- bounded -- for the abandoned copy to leave the bus and
-            // make the upload again with stream-ordered copies: rows_retry_*) and this thread takes no more jobs: callers fall back on
-            // stream-ordered copies from then on (lig_internal_uploader_available turns false)
-            hipError_t e2 = e;
-            // tests (LIG_FAULT_UPLOAD): one transfer "never completes" -- 1: the first one of witness rows, 2: the first one of randomness rows
-            const int fu = lig::knobs().fault_upload;
-            const bool injected = fu && !skip && !fault_done && (fu == 2) == (j.first.prio == 1);
-            if (injected) fault_done = true;
-            if (e == hipSuccess) {
-                const auto t_wait = clk::now();
-                const double limit = (double)lig::knobs().upload_timeout_s;
-                for (unsigned spins = 0;; spins++) {
-                    e2 = injected ? hipErrorNotReady : hipStreamQuery(st);
-                    if (e2 != hipErrorNotReady) break;
-                    if (spins < 20000) std::this_thread::yield(); else std::this_thread::sleep_for(std::chrono::microseconds(20));
-                    if ((spins & 1023) == 1023 && std::chrono::duration<double>(clk::now() - t_wait).count() > limit) { e2 = hipErrorLaunchTimeOut; abandoned.fetch_add(1, std::memory_order_acq_rel); broken.store(true, std::memory_order_release); break; }
-                }
-                if (e2 == hipErrorNotReady) e2 = hipSuccess;
-            }
-            phase.store(3, std::memory_order_release);
-            // (a failed copy publishes too: no stream may hang on the flag; lig_rows_commit reports the error once stage 1 has drained)
-            if (e2 != hipSuccess) { (void)hipGetLastError(); j.first.failed->store((int)e2, std::memory_order_release); }
-            __atomic_store_n(j.first.flag, j.first.seq, __ATOMIC_RELEASE);
-            j.second->fetch_sub(1, std::memory_order_acq_rel);
-            done_jobs.fetch_add(1, std::memory_order_relaxed);
-            phase.store(0, std::memory_order_release);
-        }
-    }
-};
-Uploader* g_uploader[64] = {nullptr};
-std::mutex g_uploader_mu;
-}  // namespace
-bool lig_internal_uploader_available(lig_ctx* c) {
-    if (c->device < 0 || c->device >= 64) return false;
-    std::lock_guard<std::mutex> lk(g_uploader_mu);
-    Uploader*& u = g_uploader[c->device];
-    if (!u) {
-        int can = 0;
-        (void)hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, c->device);
-        u = new Uploader();                         // lives for the process: its thread sleeps on the condition variable
-        u->device = c->device;
-        // The uploader's stream must not share a HARDWARE queue with a stream that may hold a pending hipStreamWaitValue32 for the word this
-        // thread publishes: HIP maps the streams of a process onto GPU_MAX_HW_QUEUES (4) hardware queues per priority class, a pending stream
-        // wait occupies its queue, and a small host-to-device copy is a blit KERNEL in the copying stream's queue (tools/queue_share_probe.hip,
-        // profiles/r05_queue_share_probe.txt) -- behind the wait it would never run.  (A latent deadlock found while hunting the round-4 hang
-        // of the sharded rows entry; not its cause, profiles/r05_rows_entry_hang.md.)  Queues are pooled per priority class, the library's
-        // proof streams are normal priority: the uploader takes the highest.
-        int lo = 0, hi = 0;
-        const bool prio = lig::knobs().upload_prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo;
-        u->ok = can && (prio ? hipStreamCreateWithPriority(&u->st, hipStreamNonBlocking, hi) : hipStreamCreateWithFlags(&u->st, hipStreamNonBlocking)) == hipSuccess;
-        if (u->ok) { u->th = std::thread([u] { u->run(); }); u->th.detach(); }
-    }
-    return u->ok && !u->broken.load(std::memory_order_acquire);
-}
-}  // extern "C"
-std::string lig_internal_uploader_state(int device) {
-    if (device < 0 || device >= 64 || !g_uploader[device]) return "uploader: none";
-    Uploader* u = g_uploader[device];
-    size_t queued = 0;
-    { std::lock_guard<std::mutex> lk(u->mu); queued = u->q.size(); }
-    const uint64_t now = (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(clk::now().time_since_epoch()).count();
-    const int ph = u->phase.load();
-    static const char* names[4] = {"idle", "in the copy call", "waiting for the copy", "publishing"};
-    return "uploader: " + std::string(names[ph & 3]) + (ph ? " (" + std::to_string(u->cur_bytes.load()) + " bytes, for " + std::to_string((now - u->cur_since_us.load()) / 1000) + " ms)" : "") +
-           ", " + std::to_string(queued) + " queued, " + std::to_string(u->done_jobs.load()) + " done";
-}
-extern "C" {
-int lig_upload_health(lig_ctx* c, uint32_t* retries, uint32_t* unsettled) {
-    CHECK_CTX(c);
-    Uploader* u = (c->device >= 0 && c->device < 64) ? g_uploader[c->device] : nullptr;
-    if (u && u->abandoned.load(std::memory_order_acquire)) (void)u->settle(0.0);      // one query: has it finished in the meantime?
-    if (retries) *retries = u ? u->retries.load(std::memory_order_relaxed) : 0;
-    if (unsettled) *unsettled = u ? u->abandoned.load(std::memory_order_acquire) : 0;
-    return LIG_OK;
-}
-void lig_internal_uploader_submit(int device, const std::vector<UploadJob>& jobs, std::atomic<int>* pending) {
-    Uploader* u = g_uploader[device];
-    pending->fetch_add((int)jobs.size(), std::memory_order_acq_rel);
-    {
-        std::lock_guard<std::mutex> lk(u->mu);
-        for (const UploadJob& j : jobs) u->q.push_back({j, pending});
-    }
-    u->cv.notify_one();
-}
-// every copy of this trace's uploads has been made (its host rows and its device matrix are no longer touched by the thread)
-static void uploader_drain(lig_trace* T) {
-    while (T->up_pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();
-}
-static void rand_drain(lig_trace* T) {
-    while (T->rand_pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();
-}
-// pinned flag words of a trace: one per stage-1 chunk (rows arrived), two per stage-2 chunk (caller randomness rows arrived / consumed)
-static int ensure_up_flags(lig_ctx* c, lig_trace* T) {
-    if (T->up_flag) return LIG_OK;
-    T->up_words = T->sched1.size() + 2 * (T->R / lig_tune::CHUNK + 3) + 8;        // (the last word: rows of lig_rows_push_rands that have arrived)
-    const size_t bytes = (T->up_words * 4 + 4095) & ~(size_t)4095;
-    HIP_TRY(c, hipHostMalloc((void**)&T->up_flag, bytes, hipHostMallocDefault));
-    std::memset((void*)T->up_flag, 0, bytes);
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&T->up_flag_dev, (void*)T->up_flag, 0));
-    return LIG_OK;
+// Host rows -> device: through the uploader thread (upload.hip: why, and what it guarantees) or by stream-ordered copies.
+// the byte range of every stage-1 chunk in the caller's matrix (T->host_msgs) and the destination of its copy
+static std::vector<lig::UploadChunk> stage1_chunks(const lig_trace* T, uint8_t* up_dst) {
+    auto chunk_src = [&](size_t b) -> size_t { return T->narrow ? (size_t)T->src_off[b] : b * (size_t)T->c->k * 32; };
+    std::vector<lig::UploadChunk> chunks;
+    for (const auto& ch : T->sched1) chunks.push_back({up_dst + chunk_src(ch.first), T->host_msgs + chunk_src(ch.first), chunk_src(ch.second) - chunk_src(ch.first)});
+    return chunks;
 }
 // witness rows by stream-ordered copies on the context's copy stream, one event per stage-1 chunk (LIG_UPLOAD_MODE=1, devices without
 // stream memory operations, and the second attempt after a transfer of the uploader thread has timed out)
 static int rows_copy_by_stream(lig_ctx* c, lig_trace* T, uint8_t* up_dst) {
-    const uint32_t k = c->k;
-    auto chunk_src = [&](size_t b) -> size_t { return T->narrow ? (size_t)T->src_off[b] : b * (size_t)k * 32; };
+    const std::vector<lig::UploadChunk> chunks = stage1_chunks(T, up_dst);
     T->up_by_thread = false;
     if (T->ev_up.empty()) {
         T->ev_up.resize(T->sched1.size(), nullptr);
         for (auto& e : T->ev_up) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    for (size_t ci = 0; ci < T->sched1.size(); ci++) {
-        const size_t b = T->sched1[ci].first, e = T->sched1[ci].second;
-        const size_t off = chunk_src(b), bytes = chunk_src(e) - off;
-        if (bytes) HIP_TRY(c, hipMemcpyAsync(up_dst + off, T->host_msgs + off, bytes, hipMemcpyHostToDevice, lig_internal_copy_stream(c)));
+    for (size_t ci = 0; ci < chunks.size(); ci++) {
+        if (chunks[ci].bytes) HIP_TRY(c, hipMemcpyAsync(chunks[ci].dst, chunks[ci].src, chunks[ci].bytes, hipMemcpyHostToDevice, lig_internal_copy_stream(c)));
         HIP_TRY(c, hipEventRecord(T->ev_up[ci], lig_internal_copy_stream(c)));
     }
     HIP_TRY(c, hipGetLastError());
     return LIG_OK;
 }
-// A transfer of the uploader thread timed out (Uploader::run): the waiting streams were released and have drained.  The copy itself is
+// A transfer of the uploader thread timed out (Uploader::run): the waiting streams were released and drain here.  The copy itself is
 // still queued on the uploader's stream and cannot be cancelled.  Bounded wait for it to leave the bus: true = it has (its bytes are where
-// they belong or will be overwritten by the second attempt); false = it is still pending -- what it reads (the caller's rows) and writes
-// (this trace's buffers) must stay alive: the trace is marked, its buffers are never freed or reused, lig_upload_health() reports it.
+// they belong or will be overwritten by the second attempt, which is counted); false = it is still pending -- what it reads (the caller's rows)
+// and writes (this trace's buffers) must stay alive: the trace is marked, its buffers are never freed or reused, lig_upload_health() reports it.
 static bool upload_settled(lig_ctx* c, lig_trace* T) {
-    Uploader* u = g_uploader[c->device];
-    if (!u || u->settle((double)lig::knobs().upload_timeout_s)) return true;
+    sync_all_streams(c);
+    if (lig_internal_upload_settle(c->device, (double)lig::knobs().upload_timeout_s)) { lig_internal_upload_count_retry(c->device); return true; }
     T->leak = true;
     return false;
 }
@@ -1001,24 +799,15 @@ static int rows_load(lig_ctx* c, lig_trace* T, const void* msgs, bool on_device)
     }
     T->host_msgs = (const uint8_t*)msgs;
     if (T->narrow && !T->packed_dev) HIP_TRY(c, hipMalloc((void**)&T->packed_dev, T->src_off[R] ? T->src_off[R] : 16));   // (the job began with device rows)
-    // byte range of a stage-1 chunk in the caller's matrix / the destination of its copy
-    auto chunk_src = [&](size_t b) -> size_t { return T->narrow ? (size_t)T->src_off[b] : b * (size_t)k * 32; };
     uint8_t* up_dst = T->narrow ? T->packed_dev : (uint8_t*)dst;
     // (every earlier reader of `dst` has finished: lig_rows_prove returns only after its stream work is done)
     // (A copy kernel reading the pinned rows over PCIe instead of the DMA engine was measured: 37 GB/s against 56 GB/s, and
     // the long-running kernel serialises with the proof's kernels whenever both streams share a hardware queue:
     // stage 2 5.6 -> 13.8 ms.  The DMA engine it is.)
-    const int mode = lig::knobs().upload_mode;   // 2: uploader thread (default), 1: per-context copy stream + events
-    if (mode == 2 && lig_internal_uploader_available(c)) {
-        TRY(ensure_up_flags(c, T));
-        T->up_seq++;
-        std::vector<UploadJob> jobs;
-        for (size_t ci = 0; ci < T->sched1.size(); ci++) {
-            const size_t b = T->sched1[ci].first, e = T->sched1[ci].second;
-            const size_t off = chunk_src(b), bytes = chunk_src(e) - off;
-            jobs.push_back(UploadJob{up_dst + off, T->host_msgs + off, bytes, T->up_flag + ci, T->up_seq, &T->up_failed});
-        }
-        lig_internal_uploader_submit(c->device, jobs, &T->up_pending);
+    if (lig::knobs().upload_mode == 2 && lig_internal_uploader_available(c)) {      // 2: uploader thread (default), 1: per-context copy stream + events
+        TRY(T->flags.ensure(c, T->flag_layout().words));
+        T->up.seq++;
+        lig_internal_uploader_submit(c->device, lig::chunk_jobs(stage1_chunks(T, up_dst), T->flags.host, T->up.seq, &T->up.failed), &T->up.pending);
         T->up_by_thread = true;
         return LIG_OK;
     }
@@ -1082,7 +871,7 @@ int lig_rows_restart(lig_trace* T, const void* msgs, int msgs_on_device) {
     if (!T->from_rows) FAIL(c, LIG_E_STATE, "lig_rows_restart: not a rows trace");
     if (T->R && !msgs) FAIL(c, LIG_E_ARG, "lig_rows_restart: null rows");
     if (T->leak) FAIL(c, LIG_E_STATE, "lig_rows_restart: a transfer into this trace's buffers never completed (lig_upload_health): destroy the trace");
-    if (T->loaded && T->host_msgs) { uploader_drain(T); if (c->stream3) HIP_TRY(c, hipStreamSynchronize(c->stream3)); }      // an upload nobody committed: let it finish first
+    if (T->loaded && T->host_msgs) { T->up.drain(); if (c->stream3) HIP_TRY(c, hipStreamSynchronize(c->stream3)); }      // an upload nobody committed: let it finish first
     if (!T->committed) T->diag_ok = false;                // the rows go straight into the matrix: the window of lig_rows_diagnose ends
     return rows_load(c, T, msgs, msgs_on_device != 0);
 }
@@ -1107,20 +896,16 @@ int lig_rows_commit(lig_trace* T, uint8_t root[32], uint8_t stage1_seed[32]) {
             // stage 1 runs again -- the caller sees a slow commit, not an error
             T->up_retry = false;
             const std::string why = c->err;
-            uploader_drain(T);
-            for (hipStream_t st : {c->stream, c->stream2, c->stream3, c->stream_sha}) if (st) (void)hipStreamSynchronize(st);
+            T->up.drain();
             if (upload_settled(c, T)) {
-                g_uploader[c->device]->retries.fetch_add(1, std::memory_order_relaxed);
                 rc = rows_copy_by_stream(c, T, T->narrow ? T->packed_dev : (uint8_t*)T->msgs);
                 if (rc == LIG_OK) rc = prove_stage1(T, &T->info1, make_mark(c));
             } else c->err = why + UPLOAD_PENDING_MSG;
         }
         if (rc != LIG_OK) {           // the caller is told it may free its rows: nothing of ours may still read them (but see T->leak)
-            const std::string why = c->err;
-            uploader_drain(T);
-            for (hipStream_t st : {c->stream, c->stream2, c->stream3, c->stream_sha}) if (st) (void)hipStreamSynchronize(st);
+            T->up.drain();
+            sync_all_streams(c);
             T->loaded = false; T->host_msgs = nullptr;
-            c->err = why;
             return rc;
         }
     }
@@ -1151,9 +936,9 @@ int lig_rows_prove(lig_trace* T, const void* rands, int rands_on_device, const u
     RandSource rs;                                        // default: generated from the dense counts of the job
     if (rands && T->rands_pushed) {                       // explicit rows win over rows pushed earlier: drop what the uploader still holds of those
         T->up_abort.store(1, std::memory_order_release);
-        rand_drain(T);
+        T->rand.drain();
         T->up_abort.store(0, std::memory_order_release);
-        (void)T->rand_failed.exchange(0);
+        (void)T->rand.take_error();
         T->rands_pushed = 0;
     }
     if (rands && rands_on_device) rs.dev = (const fr*)rands; else if (rands) rs.host = (const uint8_t*)rands;
@@ -1164,51 +949,51 @@ int lig_rows_prove(lig_trace* T, const void* rands, int rands_on_device, const u
     }
     for (int attempt = 0;; attempt++) {
         int rc = prove_stage23(T, rs, const_sum, proof, proof_len, info, make_mark(c));
-        const std::string why = c->err;
         if (rc != LIG_OK) {           // randomness-row copies the uploader thread still holds read the caller's memory: drop them, wait
-            T->rands_pushed = 0;
-            T->push_log.clear();
+            T->rands_pushed = 0; T->push_log.clear();
             T->up_abort.store(1, std::memory_order_release);
-            rand_drain(T);
-            for (hipStream_t st : {c->stream, c->stream2, c->stream3, c->stream_sha}) if (st) (void)hipStreamSynchronize(st);
-            c->err = why;
+            T->rand.drain();
+            sync_all_streams(c);
             return rc;
         }
         if (!(rs.host || rs.pushed)) break;
-        rand_drain(T);
-        const int e = T->rand_failed.exchange(0);
+        T->rand.drain();
+        const int e = T->rand.take_error();
         if (!e) break;
-        if (e == (int)hipErrorLaunchTimeOut && attempt == 0) {
-            // a randomness-row transfer timed out: stages 2 / 3 ran over garbage and are discarded.  Same second attempt as in
-            // lig_rows_commit: host rows come by stream-ordered copies now (the uploader is out of service), pushed rows are copied again
-            // from the pushes' host memory (valid until this call returns)
-            for (hipStream_t st : {c->stream, c->stream2, c->stream3, c->stream_sha}) if (st) (void)hipStreamSynchronize(st);
-            if (upload_settled(c, T)) {
-                g_uploader[c->device]->retries.fetch_add(1, std::memory_order_relaxed);
-                if (rs.pushed) {
-                    for (const UploadJob& j : T->push_log) {
-                        if (j.segs) { for (const UploadSeg& g : *j.segs) { if (!g.bytes) continue; HIP_TRY(c, g.src ? hipMemcpyAsync(g.dst, g.src, g.bytes, hipMemcpyHostToDevice, lig_internal_copy_stream(c)) : hipMemsetAsync(g.dst, 0, g.bytes, lig_internal_copy_stream(c))); } }
-                        else if (j.bytes) HIP_TRY(c, hipMemcpyAsync(j.dst, j.src, j.bytes, hipMemcpyHostToDevice, lig_internal_copy_stream(c)));
-                    }
-                    if (c->stream3) HIP_TRY(c, hipStreamSynchronize(c->stream3));
-                    T->push_sync = true;          // every row is there: stage 2 has no arrival word to wait for
-                }
-                *info = T->info1;
-                continue;
+        // a randomness-row transfer timed out: stages 2 / 3 ran over garbage and are discarded.  Same second attempt as in
+        // lig_rows_commit: host rows come by stream-ordered copies now (the uploader is out of service), pushed rows are copied again
+        // from the pushes' host memory (valid until this call returns)
+        const bool again = e == (int)hipErrorLaunchTimeOut && attempt == 0;
+        if (again && upload_settled(c, T)) {
+            if (rs.pushed) {
+                for (const UploadJob& j : T->push_log) HIP_TRY(c, lig_internal_copy_job(j, lig_internal_copy_stream(c)));
+                if (c->stream3) HIP_TRY(c, hipStreamSynchronize(c->stream3));
+                T->push_sync = true;          // every row is there: stage 2 has no arrival word to wait for
             }
-            T->rands_pushed = 0; T->push_log.clear();
-            FAIL(c, LIG_E_HIP, std::string("randomness rows upload failed: ") + hipGetErrorString((hipError_t)e) + UPLOAD_PENDING_MSG);
+            *info = T->info1;
+            continue;
         }
         T->rands_pushed = 0; T->push_log.clear();
-        FAIL(c, LIG_E_HIP, std::string("randomness rows upload failed: ") + hipGetErrorString((hipError_t)e));
+        FAIL(c, LIG_E_HIP, std::string("randomness rows upload failed: ") + hipGetErrorString((hipError_t)e) + (again ? UPLOAD_PENDING_MSG : ""));
     }
-    T->rands_pushed = 0;
-    T->push_log.clear();
+    T->rands_pushed = 0; T->push_log.clear();
     info->ms_total = info->ms_stage1 + ms_since(t_begin);
     T->committed = false;
     return LIG_OK;
 }
 
+// the shared end of lig_rows_set_linear / lig_rows_attach_linear (fn, for the error text): the randomness matrix the forms write, then L
+// takes the place of the trace's system
+static int trace_take_linear(lig_trace* T, lig_linear* L, const char* fn) {
+    lig_ctx* c = T->c;
+    if (!T->rands_full) {
+        const hipError_t e = hipMalloc((void**)&T->rands_full, (T->R ? T->R : 1) * (size_t)c->k * 32);
+        if (e != hipSuccess) { lig_internal_linear_destroy(L); FAIL(c, LIG_E_NOMEM, std::string(fn) + ": randomness matrix: " + hipGetErrorString(e)); }
+    }
+    lig_internal_linear_destroy(T->linear);
+    T->linear = L;
+    return LIG_OK;
+}
 int lig_rows_set_linear(lig_trace* T, const lig_linear_system* sys) {
     if (!T) return LIG_E_ARG;
     lig_ctx* c = T->c;
@@ -1221,17 +1006,9 @@ int lig_rows_set_linear(lig_trace* T, const lig_linear_system* sys) {
         return LIG_OK;
     }
     if (T->dense_rands) FAIL(c, LIG_E_ARG, "lig_rows_set_linear: the job has dense_rands_per_row");
-    std::vector<uint8_t> kinds(T->R);
-    for (size_t r = 0; r < T->R; r++) kinds[r] = T->rows[r].kind;
     lig_linear* L = nullptr;
-    TRY(lig_internal_linear_create(c, sys, kinds.data(), T->R, &L));       // lig_linear_check first: nothing is launched for a system it rejects
-    if (!T->rands_full) {
-        const hipError_t e = hipMalloc((void**)&T->rands_full, (T->R ? T->R : 1) * (size_t)c->k * 32);
-        if (e != hipSuccess) { lig_internal_linear_destroy(L); FAIL(c, LIG_E_NOMEM, std::string("lig_rows_set_linear: randomness matrix: ") + hipGetErrorString(e)); }
-    }
-    lig_internal_linear_destroy(T->linear);
-    T->linear = L;
-    return LIG_OK;
+    TRY(lig_internal_linear_create(c, sys, kinds_of(T->rows).data(), T->R, &L));       // lig_linear_check first: nothing is launched for a system it rejects
+    return trace_take_linear(T, L, "lig_rows_set_linear");
 }
 
 int lig_rows_attach_linear(lig_trace* T, const lig_linear_program* p) {
@@ -1246,18 +1023,10 @@ int lig_rows_attach_linear(lig_trace* T, const lig_linear_program* p) {
         return LIG_OK;
     }
     if (T->dense_rands) FAIL(c, LIG_E_ARG, "lig_rows_attach_linear: the job has dense_rands_per_row");
-    std::vector<uint8_t> kinds(T->R);
-    for (size_t r = 0; r < T->R; r++) kinds[r] = T->rows[r].kind;
-    if (!lig_internal_linear_fits(c, p, kinds.data(), T->R)) FAIL(c, LIG_E_ARG, "lig_rows_attach_linear: the program was prepared for another device, (l, k), row count or row kinds");
+    if (!lig_internal_linear_fits(c, p, kinds_of(T->rows).data(), T->R)) FAIL(c, LIG_E_ARG, "lig_rows_attach_linear: the program was prepared for another device, (l, k), row count or row kinds");
     lig_linear* L = nullptr;
     TRY(lig_internal_linear_attach(c, p, &L));
-    if (!T->rands_full) {
-        const hipError_t e = hipMalloc((void**)&T->rands_full, (T->R ? T->R : 1) * (size_t)c->k * 32);
-        if (e != hipSuccess) { lig_internal_linear_destroy(L); FAIL(c, LIG_E_NOMEM, std::string("lig_rows_attach_linear: randomness matrix: ") + hipGetErrorString(e)); }
-    }
-    lig_internal_linear_destroy(T->linear);
-    T->linear = L;
-    return LIG_OK;
+    return trace_take_linear(T, L, "lig_rows_attach_linear");
 }
 int lig_rows_set_linear_values(lig_trace* T, const uint8_t* coefs, uint64_t n_coefs) {
     if (!T) return LIG_E_ARG;
@@ -1277,11 +1046,7 @@ int lig_rows_diagnose(lig_trace* T, const lig_linear_system* sys, lig_diag_linea
     CHECK_CTX(c);
     if (!T->from_rows) FAIL(c, LIG_E_STATE, "lig_rows_diagnose: not a rows trace");
     if (!T->diag_ok) FAIL(c, LIG_E_STATE, "lig_rows_diagnose: no committed matrix (between lig_rows_commit and the next commit, or a lig_rows_restart after lig_rows_prove)");
-    if (sys) {
-        std::vector<uint8_t> kinds(T->R);
-        for (size_t r = 0; r < T->R; r++) kinds[r] = T->rows[r].kind;
-        if (lig_linear_check(sys, kinds.data(), T->R, c->l) != LIG_OK) FAIL(c, LIG_E_ARG, "lig_rows_diagnose: linear system rejected by lig_linear_check");
-    }
+    if (sys && lig_linear_check(sys, kinds_of(T->rows).data(), T->R, c->l) != LIG_OK) FAIL(c, LIG_E_ARG, "lig_rows_diagnose: linear system rejected by lig_linear_check");
     const uint32_t struct_bytes = info->struct_bytes;
     std::memset(info, 0, sizeof *info);
     info->struct_bytes = struct_bytes;
@@ -1306,47 +1071,27 @@ int lig_rows_push_rands_sparse(lig_trace* T, uint64_t first_row, uint64_t n_rows
     if (n_present && !host_rows) FAIL(c, LIG_E_ARG, "lig_rows_push_rands: null rows");
     const size_t row_bytes = (size_t)c->k * 32;
     if (!T->rands_full) HIP_TRY(c, hipMalloc((void**)&T->rands_full, T->R * row_bytes));
+    // one job per push: the uploader publishes the number of rows that have arrived in the page's push word (jobs of a trace are taken in order)
+    UploadJob j{(uint8_t*)T->rands_full + first_row * row_bytes, (const uint8_t*)host_rows, n_rows * row_bytes, nullptr, (uint32_t)(first_row + n_rows), &T->rand.failed};
+    // runs of present rows are copied from where they follow each other in host_rows, the others zero-filled on the device
+    if (present && n_present != n_rows) j.segs = std::make_shared<std::vector<UploadSeg>>(lig::presence_runs(present, n_rows, row_bytes, j.dst, j.src));
+    j.abort = &T->up_abort; j.prio = 1;
     if (lig::knobs().upload_mode != 2 || !lig_internal_uploader_available(c)) {
         // no uploader thread (LIG_UPLOAD_MODE=1, or a device without stream memory operations): the same rows by plain copies on the
         // copy stream, waited for here -- slower (the transfer sits in a HIP queue of the context) but every caller of the push
         // interface (include/lig_hip_row_batcher.hpp) keeps working.  ADVICE r4.
         if (first_row == 0) T->push_sync = true;
         if (!T->push_sync) FAIL(c, LIG_E_STATE, "lig_rows_push_rands: the uploader became unavailable in the middle of a trace");
-        uint8_t* dst = (uint8_t*)T->rands_full + first_row * row_bytes;
-        const uint8_t* src = (const uint8_t*)host_rows;
-        for (uint64_t i = 0; i < n_rows;) {
-            uint64_t e = i + 1;
-            const bool p = !present || present[i] != 0;
-            while (e < n_rows && (!present || (present[e] != 0) == p)) e++;
-            if (p) { HIP_TRY(c, hipMemcpyAsync(dst + i * row_bytes, src, (size_t)(e - i) * row_bytes, hipMemcpyHostToDevice, lig_internal_copy_stream(c))); src += (e - i) * row_bytes; }
-            else HIP_TRY(c, hipMemsetAsync(dst + i * row_bytes, 0, (size_t)(e - i) * row_bytes, lig_internal_copy_stream(c)));
-            i = e;
-        }
+        HIP_TRY(c, lig_internal_copy_job(j, lig_internal_copy_stream(c)));
         if (c->stream3) HIP_TRY(c, hipStreamSynchronize(c->stream3));
         T->rands_pushed = first_row + n_rows;
         return LIG_OK;
     }
-    if (first_row == 0) T->push_sync = false;
-    TRY(ensure_up_flags(c, T));
-    volatile uint32_t* arrived = T->up_flag + T->up_words - 1;
-    if (first_row == 0) { __atomic_store_n(arrived, 0u, __ATOMIC_RELEASE); T->up_abort.store(0, std::memory_order_release); T->push_log.clear(); }
-    // one job per push: the uploader publishes the number of rows that have arrived (jobs of a trace are taken in order)
-    UploadJob j{(uint8_t*)T->rands_full + first_row * row_bytes, (const uint8_t*)host_rows, n_rows * row_bytes, arrived, (uint32_t)(first_row + n_rows), &T->rand_failed};
-    if (present && n_present != n_rows) {       // runs of present rows are copied from where they follow each other in host_rows, the others zero-filled on the device
-        j.segs = std::make_shared<std::vector<UploadSeg>>();
-        const uint8_t* src = (const uint8_t*)host_rows;
-        for (uint64_t i = 0; i < n_rows;) {
-            uint64_t e = i + 1;
-            const bool p = present[i] != 0;
-            while (e < n_rows && (present[e] != 0) == p) e++;
-            j.segs->push_back(UploadSeg{j.dst + i * row_bytes, p ? src : nullptr, (size_t)(e - i) * row_bytes});
-            if (p) src += (e - i) * row_bytes;
-            i = e;
-        }
-    }
-    j.abort = &T->up_abort; j.prio = 1;
+    TRY(T->flags.ensure(c, T->flag_layout().words));
+    j.flag = T->flags.host + T->flag_layout().push;
+    if (first_row == 0) { T->push_sync = false; __atomic_store_n(j.flag, 0u, __ATOMIC_RELEASE); T->up_abort.store(0, std::memory_order_release); T->push_log.clear(); }
     T->push_log.push_back(j);
-    lig_internal_uploader_submit(c->device, {j}, &T->rand_pending);
+    lig_internal_uploader_submit(c->device, {j}, &T->rand.pending);
     T->rands_pushed = first_row + n_rows;
     return LIG_OK;
 }

@@ -1,7 +1,8 @@
 // prover_common.hpp -- host-side helpers shared by the prover, the sharded prover and the verifier: transcript hashing
 // and samplers (OpenSSL), the instance hash, the stage-1 seed, the coefficient draws and the self-check of stage 2, column
 // sampling, Merkle decommitment, the protobuf envelope writer and the row plan of a synthetic job.  The rules of a ROWS job (kinds,
-// narrow format) are in rows_plan.hpp, host only.  Everything here is internal to liblig_hip.so.
+// narrow format) are in rows_plan.hpp, those of bringing caller rows from host memory (upload jobs, flag words) in upload_plan.hpp, both
+// host only; the uploader thread is behind upload.hpp.  Everything here is internal to liblig_hip.so.
 #pragma once
 #include <openssl/evp.h>
 
@@ -20,6 +21,7 @@
 #include "fr29.hpp"
 #include "host_field.hpp"
 #include "rows_plan.hpp"
+#include "upload_plan.hpp"
 
 namespace H = lig::host;
 
@@ -48,22 +50,6 @@ void launch_copy_from_host(hipStream_t s, uint8_t* dst_dev, const uint8_t* src_m
 void launch_expand_rows(hipStream_t s, const uint8_t* packed, const uint64_t* off_dev, const uint8_t* widths_dev, size_t first_row,
                         size_t rows, uint32_t l, uint32_t k, fr* out, const uint32_t* prod_rows_dev = nullptr, size_t n_prod = 0);
 }  // namespace lig
-
-// ---- host rows -> device through the library's uploader thread (prover.hip; one thread per device, shared by every trace and
-// shard): no copy, event or barrier packet of such a transfer sits in a HIP queue of a proof.  A job copies `bytes`, waits for
-// the copy ON THE HOST, then publishes `seq` in *flag (pinned host memory; streams wait for it with hipStreamWaitValue32).
-// `wait` (optional): the copy may only start once *wait >= wait_val -- a word in pinned host memory that a stream of the proof writes
-// (hipStreamWriteValue32) when it is done with the destination buffer (the double-buffered randomness rows of stage 2)
-// `segs` (optional, instead of dst / src / bytes): several pieces under one arrival word; a piece without a source is zero-filled on
-// the device (rows a sparse randomness matrix does not ship)
-struct UploadSeg { uint8_t* dst; const uint8_t* src; size_t bytes; };
-struct UploadJob { uint8_t* dst; const uint8_t* src; size_t bytes; volatile uint32_t* flag; uint32_t seq; std::atomic<int>* failed;
-                   const volatile uint32_t* wait = nullptr; uint32_t wait_val = 0; const std::atomic<int>* abort = nullptr;
-                   int prio = 0;        // 1: a proof is waiting for it NOW (randomness rows) -- ahead of the prefetch of a next trace's witness rows
-                   std::shared_ptr<std::vector<UploadSeg>> segs; };
-extern "C" bool lig_internal_uploader_available(lig_ctx* c);          // false: no stream memory operations on this device (callers fall back to stream copies)
-extern "C" void lig_internal_uploader_submit(int device, const std::vector<UploadJob>& jobs, std::atomic<int>* pending);   // *pending += jobs, -1 per finished job
-std::string lig_internal_uploader_state(int device);                  // diagnostics: queue length, the copy in progress and for how long
 
 // (outside the anonymous namespace: these types appear in functions shared between translation units)
 // the derived rows of a packed matrix, ascending, and their copy on the device: what launch_expand_rows takes for rows [b, e)

@@ -17,6 +17,12 @@ struct PadRun { size_t first, count; uint64_t pos; };
 enum : uint8_t { RK_INIT = 4, RK_BIT = 5, RK_EQX = 6, RK_EQY = 7, RK_BQX = 8, RK_BQY = 9, RK_BQZ = 10 };
 inline bool has_code_check(uint8_t kind) { return kind != RK_EQX && kind != RK_EQY; }      // nonbatch_context.hpp:811-825
 
+// the kinds alone, as lig_linear_check and the linear entry points take them
+inline std::vector<uint8_t> kinds_of(const std::vector<RowDesc>& rows) {
+    std::vector<uint8_t> kinds(rows.size());
+    for (size_t r = 0; r < rows.size(); r++) kinds[r] = rows[r].kind;
+    return kinds;
+}
 // quadratic-test terms in hook order (one quadratic-stream draw each): (x, y, z) row indices; y = 0xFFFFFFFF marks the
 // equality term r * (x - z) (prover_kernels.hip k_quad_rows)
 inline std::vector<uint32_t> quad_terms(const std::vector<RowDesc>& rows) {

@@ -1,8 +1,8 @@
 // shard.hip -- one trace sharded over the GPUs of a node (lig_shard_*).
 #include "prover_common.hpp"
+#include "upload.hpp"
 #include <unistd.h>
 #include <functional>
-#include <thread>
 
 // =====================================================================================================================
 // One trace sharded over the GPUs of a node (BASELINE.json configs[3]).
@@ -54,11 +54,12 @@ struct lig_shard {
     size_t h_proof_cap = 0;
     hipEvent_t ev_enc[2] = {nullptr, nullptr}, ev_comm[2] = {nullptr, nullptr}, ev_hash[2] = {nullptr, nullptr};
     // caller rows in host memory (lig_shard_rows_*): uploaded by the library's uploader thread, as in lig_rows_* (prover.hip).  Flag words
-    // in pinned host memory: [round c: local rows of my c-th chunk arrived | round c: randomness rows arrived | ... consumed]
-    volatile uint32_t* up_flag = nullptr; uint32_t* up_flag_dev = nullptr;
-    uint32_t up_seq = 0, rand_seq = 0;
+    // in pinned host memory (lig::shard_flags): [round c: local rows of my c-th chunk arrived | round c: randomness rows arrived | ... consumed]
+    FlagPage flags;
+    UploadLane up;                             // one lane for the local rows and their randomness rows; the latter count in rand_seq
+    uint32_t rand_seq = 0;
     bool rows_by_thread = false;               // the local rows of the trace being committed are arriving through the uploader
-    std::atomic<int> up_pending{0}, up_failed{0}, up_abort{0};
+    std::atomic<int> up_abort{0};
     // narrow row format (lig_rows_job.elem_bytes): packed byte offset of every LOCAL row (+1 entry) and its width, on the device; the
     // staging buffer host rows are copied to (device rows are expanded from where they are)
     bool narrow = false;
@@ -73,9 +74,6 @@ struct lig_shard {
     bool exchange_even_alone = false;          // LIG_SHARD_FORCE_EXCHANGE: run pack + all-to-all with world == 1 too (tests)
     size_t chunk_rows(size_t g) const { return g < G ? gb[g + 1] - gb[g] : 0; }
 };
-
-static int shard_up_flags(lig_shard* S);
-static void shard_up_drain(lig_shard* S);
 
 namespace lig {
 // The column slices of `rows` codewords, one block of cap_rows x ncol per destination rank h.  Inside a row of a block the
@@ -291,13 +289,15 @@ static bool shard_quiesce(lig_shard* S, double seconds) {
 static constexpr double SHARD_QUIESCE_S = 20.0;
 static const char* const SHARD_POISONED_MSG = "; the streams still hold work queued behind the failed collective: the shard is poisoned (rows and randomness rows of this call "
                                               "must stay alive; destroy the shard and do not reuse the context)";
+// a failed call: the uploader thread is done with the caller's rows and the streams have drained -- or the shard is poisoned and says so
+static void shard_settle(lig_shard* S) { S->up.drain(); if (!shard_quiesce(S, SHARD_QUIESCE_S)) S->c->err += SHARD_POISONED_MSG; }
 
 void lig_shard_destroy(lig_shard* S) {
     if (!S) return;
     (void)hipSetDevice(S->c->device);
     if (!S->poisoned) (void)shard_quiesce(S, SHARD_QUIESCE_S);
     S->up_abort.store(1, std::memory_order_release);
-    while (S->up_pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();       // the uploader thread is done with our buffers
+    S->up.drain();                             // the uploader thread is done with our buffers
     if (S->poisoned) {
         // kernels behind a collective that never completed are still queued: they may run (and touch these buffers) whenever the queue is
         // released.  The device and pinned buffers, the events and the flag page outlive the shard; only the host object goes.  (The
@@ -306,7 +306,7 @@ void lig_shard_destroy(lig_shard* S) {
         delete S;
         return;
     }
-    if (S->up_flag) (void)hipHostFree((void*)S->up_flag);
+    S->flags.release();
     lig_internal_linear_destroy(S->linear);
     (void)hipFree(S->rands_lin);
     // the send buffers below are about to be freed.  forget() may be a host collective (comm_ipc): a shard that fails before its
@@ -407,8 +407,8 @@ static std::string shard_debug(lig_shard* S, const char* stage, uint32_t rseq) {
     std::string o = std::string("[lig_shard] rank ") + std::to_string(S->rank) + " in " + stage + ": " +
                     (w ? std::string("the calling thread has been waiting for '") + w + "' for " + std::to_string(now - S->dbg_wait_since_ms.load(std::memory_order_acquire)) + " ms"
                        : std::string("the calling thread is enqueueing"));
-    o += "; rows upload seq " + std::to_string(S->up_seq) + ", randomness seq " + std::to_string(rseq) + ", pending " + std::to_string(S->up_pending.load()) + ", flag words [arrived rows | arrived rands | consumed]:";
-    if (S->up_flag && S->rounds) for (size_t i = 0; i < 3 * S->rounds && i < 24; i++) o += (i % S->rounds == 0 ? " | " : " ") + std::to_string(S->up_flag[i]);
+    o += "; rows upload seq " + std::to_string(S->up.seq) + ", randomness seq " + std::to_string(rseq) + ", pending " + std::to_string(S->up.pending.load()) + ", flag words [arrived rows | arrived rands | consumed]:";
+    if (S->flags.host && S->rounds) for (size_t i = 0; i < 3 * S->rounds && i < 24; i++) o += (i % S->rounds == 0 ? " | " : " ") + std::to_string(S->flags.host[i]);
     else o += " none";
     return o + "; " + lig_internal_uploader_state(c->device);
 }
@@ -457,7 +457,7 @@ static int shard_stage1(lig_shard* S, lig_proof_info* info) {
         const size_t lb = S->lrow0[cidx], nb = S->lrow0[cidx + 1] - lb;
         fr* sendb = S->send + (size_t)pb * CAP * n; fr* recvb = S->recv + (size_t)pb * CAP * n;
         if (S->rows_by_thread) {                              // my c-th chunk has arrived from the host
-            HIP_TRY(c, hipStreamWaitValue32(s, S->up_flag_dev + cidx, S->up_seq, hipStreamWaitValueGte, 0xffffffffu));
+            HIP_TRY(c, hipStreamWaitValue32(s, S->flags.dev + cidx, S->up.seq, hipStreamWaitValueGte, 0xffffffffu));
             draw_pads(lb, lb + nb);
         }
         if (nb) TRY(lig_internal_encode_rows(c, S->msgs + lb * (size_t)k, S->cw + lb * k3, nb, lig::ENC_PLANAR, s));
@@ -509,7 +509,7 @@ static int shard_stage1(lig_shard* S, lig_proof_info* info) {
     TRY(drain(s, "stage 1 (exchange, column hash, leaves)"));
     if (S->rows_by_thread) {                                  // every round has been waited for: the caller's rows are no longer read
         S->rows_by_thread = false;
-        if (const int e = S->up_failed.exchange(0)) FAIL(c, LIG_E_HIP, std::string("rows upload failed: ") + hipGetErrorString((hipError_t)e));
+        if (const int e = S->up.take_error()) FAIL(c, LIG_E_HIP, std::string("rows upload failed: ") + hipGetErrorString((hipError_t)e));
     }
     stage1_seed(info->root, S->hdr.ih, info->stage1_seed);
     return LIG_OK;
@@ -552,20 +552,14 @@ static int shard_stage23(lig_shard* S, const ShardRands& rs, const uint8_t* cons
     // consumption are words in pinned host memory, no copy or event of the transfer in a queue of the proof)
     // (default off in the sharded entry, see shard_rows_load: event-chained copies on the side stream instead)
     const bool rands_by_thread = rs.host && lig::knobs().shard_uploader && lig::knobs().upload_mode == 2 && lig::knobs().rands_upload_mode == 2 && lig_internal_uploader_available(c) && S->rounds;
-    const size_t rflag0 = S->rounds, uflag0 = 2 * S->rounds;
+    const lig::FlagLayout fl = lig::shard_flags(S->rounds);
     if (rands_by_thread) {
-        TRY(shard_up_flags(S));
+        TRY(S->flags.ensure(c, fl.words));
         rseq = ++S->rand_seq;
         S->up_abort.store(0, std::memory_order_release);
-        std::vector<UploadJob> jobs;
-        for (size_t cidx = 0; cidx < S->rounds; cidx++) {
-            const size_t lb = S->lrow0[cidx], nb = S->lrow0[cidx + 1] - lb;
-            UploadJob j{(uint8_t*)rand_buf(cidx), rs.host + lb * (size_t)k * 32, nb * (size_t)k * 32, S->up_flag + rflag0 + cidx, rseq, &S->up_failed};
-            if (cidx >= 2) { j.wait = S->up_flag + uflag0 + cidx - 2; j.wait_val = rseq; }
-            j.abort = &S->up_abort; j.prio = 1;
-            jobs.push_back(j);
-        }
-        lig_internal_uploader_submit(c->device, jobs, &S->up_pending);
+        std::vector<lig::UploadChunk> chunks;
+        for (size_t cidx = 0; cidx < S->rounds; cidx++) chunks.push_back({(uint8_t*)rand_buf(cidx), rs.host + S->lrow0[cidx] * (size_t)k * 32, (S->lrow0[cidx + 1] - S->lrow0[cidx]) * (size_t)k * 32});
+        lig_internal_uploader_submit(c->device, lig::chunk_jobs(chunks, S->flags.host + fl.rands, rseq, &S->up.failed, S->flags.host + fl.consumed, &S->up_abort, 1), &S->up.pending);
     }
     auto form_rand_chunk = [&](size_t cidx) -> int {           // on the side stream
         const size_t lb = S->lrow0[cidx], nb = S->lrow0[cidx + 1] - lb;
@@ -601,7 +595,7 @@ static int shard_stage23(lig_shard* S, const ShardRands& rs, const uint8_t* cons
         const size_t lb = S->lrow0[cidx], nb = S->lrow0[cidx + 1] - lb;
         fr* rb = rand_buf(cidx);
         if (cidx + 1 < S->rounds) TRY(form_rand_chunk(cidx + 1));
-        if (rands_by_thread) HIP_TRY(c, hipStreamWaitValue32(s, S->up_flag_dev + rflag0 + cidx, rseq, hipStreamWaitValueGte, 0xffffffffu));
+        if (rands_by_thread) HIP_TRY(c, hipStreamWaitValue32(s, S->flags.dev + fl.rands + cidx, rseq, hipStreamWaitValueGte, 0xffffffffu));
         else HIP_TRY(c, hipStreamWaitEvent(s, S->ev_enc[cidx & 1], 0));
         if (nb) {
             if (c->fast) {      // as in lig_synth_prove: coset-2 values times the codewords' coset-2 plane inside the encoder's output kernel
@@ -612,7 +606,7 @@ static int shard_stage23(lig_shard* S, const ShardRands& rs, const uint8_t* cons
             }
             if (!fused_rlc) lig::launch_rlc_accumulate29(s, S->msgs + lb * (size_t)k, k, 1, rb, k, nb, k, S->coef_dev + lb, p_code, p_linH, lig_tune::GROUP / 4);
         }
-        if (rands_by_thread) HIP_TRY(c, hipStreamWriteValue32(s, S->up_flag_dev + uflag0 + cidx, rseq, 0));      // consumed: its half of the buffer is free
+        if (rands_by_thread) HIP_TRY(c, hipStreamWriteValue32(s, S->flags.dev + fl.consumed + cidx, rseq, 0));      // consumed: its half of the buffer is free
         else HIP_TRY(c, hipEventRecord(S->ev_comm[cidx & 1], s));
     }
     lig::launch_rlc_combine(s, tmp, p_code, pg, k);
@@ -764,22 +758,12 @@ int lig_shard_rows_plan(const uint8_t* kinds, size_t n_rows, uint32_t world, uin
     return LIG_OK;
 }
 
-static int shard_up_flags(lig_shard* S) {
-    lig_ctx* c = S->c;
-    if (S->up_flag) return LIG_OK;
-    const size_t bytes = ((3 * S->rounds + 8) * 4 + 4095) & ~(size_t)4095;
-    HIP_TRY(c, hipHostMalloc((void**)&S->up_flag, bytes, hipHostMallocDefault));
-    std::memset((void*)S->up_flag, 0, bytes);
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&S->up_flag_dev, (void*)S->up_flag, 0));
-    return LIG_OK;
-}
-static void shard_up_drain(lig_shard* S) { while (S->up_pending.load(std::memory_order_acquire) > 0) std::this_thread::yield(); }
 // local rows of a rows job -> S->msgs.  Device rows: one copy on the main stream.  Host rows: round by round through the uploader
 // thread -- lig_shard_rows_commit encodes my c-th chunk as soon as it has arrived (the caller's memory must stay valid until then).
 static int shard_rows_load(lig_shard* S, const void* local_msgs, bool on_device) {
     lig_ctx* c = S->c;
     if (S->Rl && !local_msgs) FAIL(c, LIG_E_ARG, "sharded rows job: null local rows");
-    shard_up_drain(S);                                 // an upload nobody committed
+    S->up.drain();                                     // an upload nobody committed
     HIP_TRY(c, hipStreamSynchronize(c->stream));      // the previous trace is done with S->msgs
     S->committed = false;
     S->rows_by_thread = false;
@@ -806,15 +790,12 @@ static int shard_rows_load(lig_shard* S, const void* local_msgs, bool on_device)
     // hipStreamWaitValue32 sometimes never completes (profiles/r05_rows_entry_hang.md: 15 % of the runs, the GPUTEST hang of round 4).
     // LIG_SHARD_UPLOADER=1 restores the round-4 path (reproduction / a node where every rank has its own GPU).
     if (!on_device && lig::knobs().shard_uploader && lig::knobs().upload_mode == 2 && lig_internal_uploader_available(c)) {
-        TRY(shard_up_flags(S));
-        S->up_seq++;
+        TRY(S->flags.ensure(c, lig::shard_flags(S->rounds).words));
+        S->up.seq++;
         S->up_abort.store(0, std::memory_order_release);
-        std::vector<UploadJob> jobs;
-        for (size_t cidx = 0; cidx < S->rounds; cidx++) {
-            const size_t lb = S->lrow0[cidx], nb = S->lrow0[cidx + 1] - lb;
-            jobs.push_back(UploadJob{(uint8_t*)S->msgs + lb * row_bytes, (const uint8_t*)local_msgs + lb * row_bytes, nb * row_bytes, S->up_flag + cidx, S->up_seq, &S->up_failed});
-        }
-        lig_internal_uploader_submit(c->device, jobs, &S->up_pending);
+        std::vector<lig::UploadChunk> chunks;
+        for (size_t cidx = 0; cidx < S->rounds; cidx++) chunks.push_back({(uint8_t*)S->msgs + S->lrow0[cidx] * row_bytes, (const uint8_t*)local_msgs + S->lrow0[cidx] * row_bytes, (S->lrow0[cidx + 1] - S->lrow0[cidx]) * row_bytes});
+        lig_internal_uploader_submit(c->device, lig::chunk_jobs(chunks, S->flags.host, S->up.seq, &S->up.failed), &S->up.pending);
         S->rows_by_thread = true;
         return LIG_OK;
     }
@@ -881,11 +862,8 @@ int lig_shard_rows_commit(lig_shard* S, uint8_t root[32], uint8_t stage1_seed[32
     {
         const int rc = shard_stage1(S, &S->info1);
         if (rc != LIG_OK) {               // the caller is told it may free its rows
-            const std::string why = c->err;
-            shard_up_drain(S);
-            const bool quiet = shard_quiesce(S, SHARD_QUIESCE_S);
+            shard_settle(S);
             S->rows_by_thread = false;
-            c->err = quiet ? why : why + SHARD_POISONED_MSG;
             return rc;
         }
     }
@@ -917,16 +895,13 @@ int lig_shard_rows_prove(lig_shard* S, const void* local_rands, int rands_on_dev
     {
         const int rc = shard_stage23(S, rs, const_sum, proof, proof_len, info);
         if (rc != LIG_OK) {               // randomness-row copies the uploader thread still holds read the caller's memory: drop them, wait
-            const std::string why = c->err;
             S->up_abort.store(1, std::memory_order_release);
-            shard_up_drain(S);
-            const bool quiet = shard_quiesce(S, SHARD_QUIESCE_S);
-            c->err = quiet ? why : why + SHARD_POISONED_MSG;
+            shard_settle(S);
             return rc;
         }
         if (rs.host) {
-            shard_up_drain(S);
-            if (const int e = S->up_failed.exchange(0)) FAIL(c, LIG_E_HIP, std::string("randomness rows upload failed: ") + hipGetErrorString((hipError_t)e));
+            S->up.drain();
+            if (const int e = S->up.take_error()) FAIL(c, LIG_E_HIP, std::string("randomness rows upload failed: ") + hipGetErrorString((hipError_t)e));
         }
     }
     info->ms_total = info->ms_stage1 + ms_since(t_begin);
@@ -948,10 +923,8 @@ int lig_shard_rows_set_linear(lig_shard* S, const lig_linear_system* sys) {
         return LIG_OK;
     }
     if (S->dense_rands) FAIL(c, LIG_E_ARG, "lig_shard_rows_set_linear: the job has dense_rands_per_row");
-    std::vector<uint8_t> kinds(S->R);
-    for (size_t r = 0; r < S->R; r++) kinds[r] = S->rows[r].kind;
     lig_linear* L = nullptr;
-    TRY(lig_internal_linear_create_shard(c, sys, kinds.data(), S->R, S->grow, S->rank, S->world, &L));      // lig_linear_check first: nothing is launched for a system it rejects
+    TRY(lig_internal_linear_create_shard(c, sys, kinds_of(S->rows).data(), S->R, S->grow, S->rank, S->world, &L));      // lig_linear_check first: nothing is launched for a system it rejects
     if (!S->rands_lin) {
         const hipError_t e = hipMalloc((void**)&S->rands_lin, (S->Rl ? S->Rl : 1) * (size_t)c->k * 32);
         if (e != hipSuccess) { (void)hipGetLastError(); lig_internal_linear_destroy(L); FAIL(c, LIG_E_NOMEM, std::string("lig_shard_rows_set_linear: randomness matrix: ") + hipGetErrorString(e)); }
