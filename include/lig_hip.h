@@ -281,7 +281,7 @@ typedef struct {
     const uint8_t *kinds;            /* one byte per row (host memory) */
     const void *msgs;                /* rows x k elements, row-major */
     int32_t  msgs_on_device;         /* 0: host memory (uploaded inside the timed path), 1: device memory */
-    int32_t  reserved;
+    int32_t  reserved;               /* 0, or LIG_ROWS_JOB_WIDE: this struct has the member wide_per_row (below) and the library may read it */
     uint8_t  encoding_seed[32];
     uint8_t  program_hash[32];
     int64_t  generated_at;
@@ -310,7 +310,29 @@ typedef struct {
      * lig_rows_restart takes the same packed layout, as do lig_shard_rows_begin / _restart (there: one byte per row of the
      * whole trace, `msgs` = this rank's rows only, packed back to back in commit order). */
     const uint8_t *elem_bytes;
+    /* optional (NULL: none); one entry per row of the job (of the WHOLE trace on the sharded entry): MIXED rows, narrow rows that
+     * carry a few wide slots.  wide_per_row[r] = c > 0: the packed bytes of row r are the narrow row exactly as above (already a
+     * multiple of 4 bytes), followed by c RECORDS of 36 bytes: a uint32_t column and the 8 little-endian uint32_t limbs of a
+     * canonical field element.  After expansion slot `column` of the row holds the record's value; whatever the narrow part
+     * carries at that column is ignored (the caller writes 0 there).  Within a row the columns are strictly ascending and < l.
+     * Only on a row of width LIG_ELEM_BIT, 1, 2, 4 or 8 (whose own rules are unchanged), c <= l; c > 0 on a full-width or
+     * LIG_ELEM_PRODUCT row, with elem_bytes == NULL, or c > l is LIG_E_ARG, decided on the host before anything is launched.
+     * A LIG_ELEM_PRODUCT row whose QX / QY operand rows are mixed sees the records: operand slot i is the record's value where a
+     * record names column i.  The counts belong to the shape: lig_rows_restart / lig_shard_rows_restart take rows in the same
+     * layout with the same counts; the columns and values inside the records may differ from trace to trace.
+     * HOST rows: the records are read before any copy starts (36 c bytes per mixed row); a column >= l or out of order is
+     * LIG_E_ARG from lig_rows_begin / _restart / lig_shard_rows_begin / _restart and nothing is launched.  DEVICE rows: a record
+     * whose column is >= l is not written and raises a flag word on the device: lig_rows_commit then returns LIG_E_ARG (the
+     * trace stays usable: lig_rows_restart with good rows, then commit), lig_shard_rows_begin / _restart return it themselves,
+     * before any collective is queued.  Duplicate or unordered columns in device rows are NOT detected: the slots they name
+     * (and, in a derived row, the products of those slots) hold an unspecified one of the records' values -- never a write
+     * outside the row.  lig_rows_verify_begin ignores the member, as it ignores msgs.
+     * The member was appended to the struct: a caller compiled before it existed passes a struct that ENDS at elem_bytes (and
+     * reserved = 0, as it always had to).  So the library reads wide_per_row only from a job whose `reserved` has the bit
+     * LIG_ROWS_JOB_WIDE; without the bit the job is read exactly as before and nothing past elem_bytes is touched. */
+    const uint32_t *wide_per_row;
 } lig_rows_job;
+enum { LIG_WIDE_RECORD_BYTES = 36, LIG_ROWS_JOB_WIDE = 1 };
 int lig_rows_begin(lig_ctx *ctx, const lig_rows_job *job, lig_trace **out);
 int lig_rows_commit(lig_trace *trace, uint8_t root[32], uint8_t stage1_seed[32]);
 /* const_sum == NULL: the constant is taken to be -sum_r <row_r, rand_r> (returned in info->const_sum) -- for statements that

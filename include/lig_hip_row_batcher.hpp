@@ -51,6 +51,11 @@ struct hip_proof_meta {
     // (LIG_ELEM_BIT / elem_bytes) -- on one GPU and on every rank of a sharded trace (shard_over).  Off: 8 bytes per slot on one
     // GPU, full rows when sharded.
     bool narrowest = false;
+    // With narrow_rows and narrowest: MIXED rows (lig_rows_job.wide_per_row).  The OR of a row's slots no longer decides: every linear /
+    // x / y / z row is shipped in the base width -- bits, 1, 2, 4 or 8 bytes -- for which the narrow row plus one 36-byte record per
+    // data slot that does not fit is the fewest bytes (the narrower base on a tie), at full width only where that is not more bytes.
+    // A bit row with a few machine words among its slots stays a bit row.  Without the other two options it has no effect.
+    bool wide_slots = false;
     // With narrow_rows: the z row of every triple recorded by quadratic_callback is NOT shipped (LIG_ELEM_PRODUCT): the library forms
     // x * y mod p on the device from the x and y rows it received, on one GPU and on every rank of a sharded trace, and draws the
     // row's pads.  The z the guest handed over is ignored: the prover's valid_quad says nothing about such a triple -- a guest whose z
@@ -255,16 +260,19 @@ public:
         shipped_ = kinds_.size() * (size_t)k_ * 32;
         if (sharded_) { commit_sharded(job, root, stage1_seed); return; }
         std::vector<uint8_t> widths;
+        std::vector<uint32_t> wide;
         if (meta_.narrow_rows) {
             // packed IN PLACE: a narrow row shrinks to l x (its width) bytes, rows only ever move towards the front of the staging
             const size_t R = kinds_.size();
-            if (plan_widths(widths, true)) {
+            if (plan_widths(widths, true, wide)) {
                 uint8_t* out = reinterpret_cast<uint8_t*>(rows_.row(0));
                 for (size_t r = 0; r < R; r++) {
                     if (widths[r] != 32) kinds_[r] |= LIG_ROW_DRAW_PAD;
-                    out = pack_row(rows_.row(r), widths[r], out);
+                    out = pack_row(rows_.row(r), widths[r], out, wide.empty() ? 0 : wide[r]);
                 }
                 job.elem_bytes = widths.data();
+                job.wide_per_row = wide.empty() ? nullptr : wide.data();
+                job.reserved = LIG_ROWS_JOB_WIDE;
                 shipped_ = out - reinterpret_cast<uint8_t*>(rows_.row(0));
             }
         }
@@ -273,7 +281,7 @@ public:
             else { lig_trace_destroy(trace_); trace_ = nullptr; linear_on_trace_ = values_on_trace_ = false; }
         }
         if (!trace_) check(lig_rows_begin(ctx_, &job, &trace_), "lig_rows_begin");
-        shape_kinds_ = kinds_; shape_widths_ = widths; shape_meta_ = meta_;
+        shape_kinds_ = kinds_; shape_widths_ = widths; shape_wide_ = wide; shape_meta_ = meta_;
         apply_linear();                                   // (a trace that was restarted keeps the structure it has)
         check(lig_rows_commit(trace_, root, stage1_seed), "lig_rows_commit");
         for (auto& kd : kinds_) kd &= 0x7f;               // (pass 2 compares plain kinds)
@@ -332,7 +340,9 @@ private:
         if (std::memcmp(meta_.encoding_seed, shape_meta_.encoding_seed, 32) || std::memcmp(meta_.program_hash, shape_meta_.program_hash, 32) ||
             meta_.generated_at != shape_meta_.generated_at || meta_.version != shape_meta_.version || meta_.public_args != shape_meta_.public_args) return false;
         const std::vector<uint8_t> w = job.elem_bytes ? std::vector<uint8_t>(job.elem_bytes, job.elem_bytes + kinds_.size()) : std::vector<uint8_t>();
-        return w == shape_widths_ || (w.empty() && shape_widths_.empty());
+        if (!(w == shape_widths_ || (w.empty() && shape_widths_.empty()))) return false;
+        // (the record counts of mixed rows belong to the shape as the widths do)
+        return (job.wide_per_row ? std::vector<uint32_t>(job.wide_per_row, job.wide_per_row + kinds_.size()) : std::vector<uint32_t>()) == shape_wide_;
     }
     void begin_pass2(size_t local_rows) {
         rands_.reserve(local_rows ? local_rows : 1, 0);
@@ -374,17 +384,20 @@ private:
         // narrowest: the widths of ALL rows (every rank sees the same rows), this rank's rows packed in place behind the compaction
         // (derive_products without narrowest: the derived z rows leave the matrix, every other row stays full)
         std::vector<uint8_t> widths;
+        std::vector<uint32_t> wide;
         if (meta_.narrow_rows && (meta_.narrowest || meta_.derive_products)) {
-            if (plan_widths(widths, meta_.narrowest)) {
+            if (plan_widths(widths, meta_.narrowest, wide)) {
                 for (size_t r = 0; r < R; r++) if (widths[r] != 32) kinds_[r] |= LIG_ROW_DRAW_PAD;
                 job.elem_bytes = widths.data();
+                job.wide_per_row = wide.empty() ? nullptr : wide.data();
+                job.reserved = LIG_ROWS_JOB_WIDE;
             }
         }
         uint8_t* out = reinterpret_cast<uint8_t*>(rows_.row(0));
         // this rank's rows, compacted IN PLACE to the front of the staging (commit order is kept, rows only move forward)
         for (uint64_t g = rank_; g < rounds * world_; g += world_)
             for (uint64_t r = b[g]; r < b[g + 1]; r++) {
-                if (job.elem_bytes) out = pack_row(rows_.row(r), widths[r], out);
+                if (job.elem_bytes) out = pack_row(rows_.row(r), widths[r], out, wide.empty() ? 0 : wide[r]);
                 else if (n_local_ != r) std::memmove(rows_.row(n_local_), rows_.row(r), words * 8);
                 local_of_[r] = n_local_++;
             }
@@ -395,7 +408,7 @@ private:
             else { lig_shard_destroy(shard_); shard_ = nullptr; linear_on_trace_ = false; }
         }
         if (!shard_) check(lig_shard_rows_begin(ctx_, &job, rank_, world_, &comm_, &shard_), "lig_shard_rows_begin");
-        shape_kinds_ = kinds_; shape_widths_ = job.elem_bytes ? widths : std::vector<uint8_t>(); shape_meta_ = meta_;
+        shape_kinds_ = kinds_; shape_widths_ = job.elem_bytes ? widths : std::vector<uint8_t>(); shape_wide_ = wide; shape_meta_ = meta_;
         apply_linear();                                   // this rank's share of the system, under the commit
         check(lig_shard_rows_commit(shard_, root, stage1_seed), "lig_shard_rows_commit");
         for (auto& kd : kinds_) kd &= 0x7f;               // (pass 2 compares plain kinds)
@@ -404,16 +417,48 @@ private:
         std::memset(rands_.row(0), 0, (rand_rows ? rand_rows : 1) * words * 8);     // batch rows and rows without a callback keep zero rows
     }
     // widths of all rows: a derived z row (derive_products) LIG_ELEM_PRODUCT, every other row ship_width() or, with narrow_others off,
-    // 32; false = every row is full width (the plain format)
-    bool plan_widths(std::vector<uint8_t>& widths, bool narrow_others) const {
+    // 32; false = every row is full width (the plain format).  wide_slots (with narrowest): mixed_width() chooses instead of
+    // ship_width(), `wide` = the records of every row -- left EMPTY when no row has any (and always without the option)
+    bool plan_widths(std::vector<uint8_t>& widths, bool narrow_others, std::vector<uint32_t>& wide) const {
         const size_t R = kinds_.size();
+        const bool mixed = narrow_others && meta_.narrowest && meta_.wide_slots;
         widths.assign(R ? R : 1, 32);
-        bool any = false;
+        wide.clear();
+        if (mixed) wide.assign(R ? R : 1, 0);
+        bool any = false, any_wide = false;
         for (size_t r = 0; r < R; r++) {
-            widths[r] = meta_.derive_products && kinds_[r] == LIG_ROW_QZ ? (uint8_t)LIG_ELEM_PRODUCT : narrow_others ? ship_width(r) : 32;
+            widths[r] = meta_.derive_products && kinds_[r] == LIG_ROW_QZ ? (uint8_t)LIG_ELEM_PRODUCT : !narrow_others ? 32 : mixed ? mixed_width(r, &wide[r]) : ship_width(r);
             any = any || widths[r] != 32;
+            any_wide = any_wide || (mixed && wide[r]);
         }
+        if (!any_wide) wide.clear();
         return any;
+    }
+    // the smallest base index (0 bits, 1 .. 4 = 1, 2, 4, 8 bytes; 5 = none) slot `v` (4 u64) fits
+    static unsigned slot_class(const uint64_t* v) {
+        if (v[1] | v[2] | v[3]) return 5;
+        return v[0] <= 1 ? 0 : v[0] <= 0xff ? 1 : v[0] <= 0xffff ? 2 : v[0] <= 0xffffffffu ? 3 : 4;
+    }
+    size_t narrow_bytes(uint8_t w) const { return w == LIG_ELEM_BIT ? ((size_t)l_ + 31) / 32 * 4 : ((size_t)l_ * w + 3) / 4 * 4; }
+    // wide_slots: the base width of row r of the staging and its record count -- the base whose narrow row + 36 bytes per data slot
+    // that does not fit it is the fewest bytes, the narrower base on a tie; 32 (no records) for batch rows and where the full row is
+    // not more bytes (as mixed_widths of the Python binding)
+    uint8_t mixed_width(size_t r, uint32_t* records) const {
+        *records = 0;
+        if (kinds_[r] > LIG_ROW_QZ) return 32;
+        const uint64_t* rw = const_cast<hip_row_staging&>(rows_).row(r);
+        size_t n_class[6] = {0, 0, 0, 0, 0, 0};
+        for (uint32_t i = 0; i < l_; i++) n_class[slot_class(rw + 4 * i)]++;
+        static const uint8_t base[5] = {LIG_ELEM_BIT, 1, 2, 4, 8};
+        size_t best = (size_t)k_ * 32, misfit = l_;
+        uint8_t w = 32;
+        for (unsigned b = 0; b < 5; b++) {
+            misfit -= n_class[b];                         // slots of a class above b
+            const size_t cost = narrow_bytes(base[b]) + misfit * LIG_WIDE_RECORD_BYTES;
+            if (cost < best) { best = cost; w = base[b]; *records = (uint32_t)misfit; }
+        }
+        if (w == 32) *records = 0;
+        return w;
     }
     // the width row r of the staging is shipped in: 32 for batch rows and rows whose data slots need more than 8 bytes; else 8,
     // or with `narrowest` the smallest of bits / 1 / 2 / 4 / 8 bytes that holds every data slot (the OR of the slots decides)
@@ -428,12 +473,31 @@ private:
     }
     // row `rw` (k x 4 u64) in the packed layout of width w written at `out` <= rw (the same staging: the write never overtakes
     // the read); returns the next row's start -- narrow rows take l x w bytes (bits: ceil(l / 8)) zero-padded to a multiple of 4,
-    // derived rows nothing
-    uint8_t* pack_row(const uint64_t* rw, uint8_t w, uint8_t* out) const {
+    // derived rows nothing.  records > 0 (a mixed row): the slots that do not fit w are 0 in the narrow part and follow it as
+    // {uint32 column, 32 bytes}, ascending -- collected before the narrow part is written over them; narrow part + records stay below
+    // k x 32 bytes (mixed_width), so the next row of the staging is not reached
+    uint8_t* pack_row(const uint64_t* rw, uint8_t w, uint8_t* out, uint32_t records = 0) const {
         if (w == LIG_ELEM_PRODUCT) return out;            // a derived row: nothing is shipped
         if (w == 32) {
             if ((const void*)out != (const void*)rw) std::memmove(out, rw, (size_t)k_ * 32);
             return out + (size_t)k_ * 32;
+        }
+        if (records) {
+            const unsigned b = w == LIG_ELEM_BIT ? 0 : w == 1 ? 1 : w == 2 ? 2 : w == 4 ? 3 : 4;
+            std::vector<uint8_t> rec((size_t)records * LIG_WIDE_RECORD_BYTES);
+            std::vector<uint32_t> cols;
+            for (uint32_t i = 0; i < l_; i++)
+                if (slot_class(rw + 4 * i) > b) {
+                    std::memcpy(rec.data() + cols.size() * LIG_WIDE_RECORD_BYTES, &i, 4);
+                    std::memcpy(rec.data() + cols.size() * LIG_WIDE_RECORD_BYTES + 4, rw + 4 * i, 32);
+                    cols.push_back(i);
+                }
+            if (cols.size() != records) throw std::logic_error("hip_row_batcher: a mixed row changed between planning and packing");
+            uint64_t* w_rw = const_cast<uint64_t*>(rw);   // (the staging is ours: the slots that travel as records are 0 in the narrow part)
+            for (uint32_t i : cols) w_rw[4 * i] = 0;
+            uint8_t* end = pack_row(rw, w, out, 0);
+            std::memcpy(end, rec.data(), rec.size());
+            return end + rec.size();
         }
         size_t bytes = 0;
         if (w == LIG_ELEM_BIT) {
@@ -500,6 +564,7 @@ private:
     std::vector<uint8_t> present_;
     uint64_t enc_pos_ = 0;                                // encoding-stream position (elements) of the next row's pad
     std::vector<uint8_t> kinds_, shape_kinds_, shape_widths_;
+    std::vector<uint32_t> shape_wide_;                    // record counts of the mixed rows of the last commit (empty: none)
     hip_row_staging rows_, rands_;
     lig_trace* trace_ = nullptr;
     hip_linear_system_copy linear_;

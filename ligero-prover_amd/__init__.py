@@ -49,6 +49,8 @@ ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8,
 ROW_DRAW_PAD = 0x80
 ELEM_BIT = 0x81            # lig_rows_job.elem_bytes: the row's data slots are bits (LIG_ELEM_BIT)
 ELEM_PRODUCT = 0x82        # ... the QZ row of a triple is not shipped: the library forms x * y mod p on the device (LIG_ELEM_PRODUCT)
+ROWS_JOB_WIDE = 1          # lig_rows_job.reserved: the struct has wide_per_row (LIG_ROWS_JOB_WIDE)
+WIDE_RECORD_BYTES = 36     # lig_rows_job.wide_per_row: a record of a mixed row, uint32 column + 8 uint32 limbs (LIG_WIDE_RECORD_BYTES)
 ARG_I64, ARG_STR, ARG_HEX = 0, 1, 2
 COEF_ONE, COEF_NEG_ONE = 0xFFFFFFFF, 0xFFFFFFFE      # lig_lin_term.coef values that need no table entry (LIG_COEF_ONE / LIG_COEF_NEG_ONE)
 
@@ -87,7 +89,7 @@ class RowsJob(C.Structure):
                 ("reserved", C.c_int32), ("encoding_seed", C.c_uint8 * 32), ("program_hash", C.c_uint8 * 32),
                 ("generated_at", C.c_int64), ("version", C.c_char * 16),
                 ("public_args", C.c_void_p), ("public_arg_lens", C.c_void_p), ("n_public_args", C.c_uint64),
-                ("dense_rands_per_row", C.c_void_p), ("elem_bytes", C.c_void_p)]
+                ("dense_rands_per_row", C.c_void_p), ("elem_bytes", C.c_void_p), ("wide_per_row", C.c_void_p)]
 
     def set_public_args(self, args):
         _attach_public_args(self, args)
@@ -485,6 +487,89 @@ def narrowest_widths(rows, kinds, l, derive_products=False):
     return out
 
 
+def narrow_row_bytes(w, l, k):
+    """packed bytes of one row of width w without records: 0 / 32 all k slots; ELEM_BIT, 1, 2, 4, 8 the l data slots rounded up to a
+    multiple of 4; ELEM_PRODUCT nothing"""
+    w = int(w)
+    if w in (0, 32):
+        return 32 * k
+    if w == ELEM_PRODUCT:
+        return 0
+    if w == ELEM_BIT:
+        return (l + 31) // 32 * 4
+    if w in (1, 2, 4, 8):
+        return (l * w + 3) // 4 * 4
+    raise ValueError("no such width %d" % w)
+
+
+_MIXED_BASES = ((ELEM_BIT, 1), (1, 8), (2, 16), (4, 32), (8, 64))       # base width, bits a slot may have to fit it
+
+
+def _slot_bits(d):
+    """(l, 8) uint32 -> the bit length of every slot"""
+    d = np.asarray(d, dtype=np.uint32)
+    top = np.zeros(len(d), dtype=np.int64)
+    for j in range(8):                           # the highest non-zero limb decides
+        nz = d[:, j] != 0
+        top[nz] = 32 * j + np.floor(np.log2(d[nz, j].astype(np.float64))).astype(np.int64) + 1
+    return top
+
+
+def mixed_widths(rows, kinds, l, derive_products=False):
+    """-> (widths, wide_per_row) for pack_rows_mixed / elem_bytes + wide_per_row: every LINEAR / QX / QY / QZ row of rows (R, k, 8) as
+    the cheapest MIXED row -- a base width b of ELEM_BIT, 1, 2, 4, 8 costs narrow_row_bytes(b) + 36 bytes per data slot that does
+    not fit b; on a tie the narrower base -- or at full width (32) where that is not more bytes than the cheapest mixed form; every
+    other row kind is 32 with no records.  derive_products: every QZ row is ELEM_PRODUCT instead, as narrowest_widths does"""
+    rows = np.asarray(rows)
+    kinds = np.asarray(kinds, dtype=np.uint8) & 0x7F
+    k = rows.shape[1] if len(kinds) else 0
+    widths = np.full(len(kinds), 32, dtype=np.uint8)
+    wide = np.zeros(len(kinds), dtype=np.uint32)
+    for r in range(len(kinds)):
+        if kinds[r] > 3:
+            continue
+        if derive_products and kinds[r] == 3:
+            widths[r] = ELEM_PRODUCT
+            continue
+        bits = _slot_bits(rows[r, :l])
+        best = None
+        for b, fit in _MIXED_BASES:
+            c = int((bits > fit).sum())
+            cost = narrow_row_bytes(b, l, k) + WIDE_RECORD_BYTES * c
+            if best is None or cost < best[0]:
+                best = (cost, b, c)
+        if 32 * k <= best[0]:
+            continue
+        widths[r], wide[r] = best[1], best[2]
+    return widths, wide
+
+
+def pack_rows_mixed(rows, widths, wide_per_row, l):
+    """pack_rows for MIXED rows (lig_rows_job.wide_per_row): row r with wide_per_row[r] = c > 0 is its narrow row of width widths[r] with
+    0 in the slots that do not fit, followed by c records -- uint32 column, 8 uint32 limbs -- of exactly those slots, ascending; the
+    row must have exactly c such data slots.  With all counts 0 this is pack_rows"""
+    rows = np.asarray(rows)
+    parts = []
+    for r, w in enumerate(widths):
+        w, c = int(w), int(wide_per_row[r])
+        if not c:
+            parts.append(pack_rows(rows[r:r + 1], [w], l).tobytes())
+            continue
+        fit = dict(_MIXED_BASES).get(w)
+        if fit is None:
+            raise ValueError("row %d: records on a row of width %d" % (r, w))
+        cols = np.nonzero(_slot_bits(rows[r, :l]) > fit)[0]
+        if len(cols) != c:
+            raise ValueError("row %d: %d slots do not fit its width, wide_per_row says %d" % (r, len(cols), c))
+        base = np.array(rows[r:r + 1], dtype=np.uint32)
+        base[0, cols] = 0
+        rec = np.zeros((c, 9), dtype=np.uint32)
+        rec[:, 0] = cols
+        rec[:, 1:] = rows[r, cols]
+        parts.append(pack_rows(base, [w], l).tobytes() + rec.tobytes())
+    return np.frombuffer(b"".join(parts), dtype=np.uint8).copy()
+
+
 def shard_rows_plan(kinds, world):
     """-> (rounds, boundaries): the block-cyclic deal of a rows job's committed rows over `world` ranks (host only):
     global chunk g = rows [b[g], b[g+1]) belongs to rank g mod world"""
@@ -692,7 +777,7 @@ class Context:
 
     # ---- one trace sharded over ranks, rows supplied by the caller (lig_shard_rows_*)
     def shard_rows_begin(self, kinds_all, local_msgs, rank, world, comm, on_device=False, encoding_seed=None, generated_at=0,
-                         public_args=None, dense_rands_per_row=None, elem_bytes=None):
+                         public_args=None, dense_rands_per_row=None, elem_bytes=None, wide_per_row=None):
         """kinds_all: the kinds of ALL committed rows; local_msgs: this rank's rows (lig_shard_rows_plan), (rows_local, k, 8) uint32;
         with elem_bytes (one width per row of the WHOLE trace): this rank's rows packed back to back (pack_rows of the local rows)"""
         kinds = np.ascontiguousarray(kinds_all, dtype=np.uint8)
@@ -704,6 +789,11 @@ class Context:
             eb = np.ascontiguousarray(elem_bytes, dtype=np.uint8)
             job.elem_bytes = eb.ctypes.data if len(eb) else None
             keep += (eb,)
+        if wide_per_row is not None:              # mixed rows: one record count per row of the WHOLE trace
+            wp = np.ascontiguousarray(wide_per_row, dtype=np.uint32)
+            job.wide_per_row = wp.ctypes.data if len(wp) else None
+            job.reserved = ROWS_JOB_WIDE                 # this struct has the member
+            keep += (wp,)
         if on_device:
             job.msgs = local_msgs.value if hasattr(local_msgs, "value") else int(local_msgs)
         elif elem_bytes is not None:              # narrow format: the packed byte string
@@ -816,7 +906,7 @@ class Context:
 
     # ---- the same prover over rows supplied by the caller (lig_rows_*)
     def rows_begin(self, kinds, msgs, on_device=False, encoding_seed=None, generated_at=0, public_args=None, program_hash=None,
-                   dense_rands_per_row=None, elem_bytes=None):
+                   dense_rands_per_row=None, elem_bytes=None, wide_per_row=None):
         """kinds: uint8 array (ROW_KINDS | ROW_DRAW_PAD); msgs: device pointer (on_device) or a (rows, k, 8) uint32 host array.
         -> (trace, keepalive); keep `keepalive` referenced until rows_commit has returned"""
         kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
@@ -835,6 +925,11 @@ class Context:
             eb = np.ascontiguousarray(elem_bytes, dtype=np.uint8)
             job.elem_bytes = eb.ctypes.data if len(eb) else None
             keep = keep + (eb,)
+        if wide_per_row is not None:              # mixed rows (pack_rows_mixed): one record count per row
+            wp = np.ascontiguousarray(wide_per_row, dtype=np.uint32)
+            job.wide_per_row = wp.ctypes.data if len(wp) else None
+            job.reserved = ROWS_JOB_WIDE                 # this struct has the member
+            keep = keep + (wp,)
         job.msgs_on_device = int(bool(on_device))
         es = bytes(range(32)) if encoding_seed is None else bytes(encoding_seed)
         ph = bytes(32) if program_hash is None else bytes(program_hash)

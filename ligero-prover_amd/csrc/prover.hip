@@ -51,6 +51,8 @@ struct lig_trace {
     std::vector<uint64_t> src_off;
     uint64_t* src_off_dev = nullptr; uint8_t* widths_dev = nullptr; uint8_t* packed_dev = nullptr;
     ProductRows prod;                   // derived rows (LIG_ELEM_PRODUCT): formed next to the expansion from the packed x and y rows
+    WideRows wide;                      // mixed rows (lig_rows_job.wide_per_row): their records are written behind the expansion
+    uint32_t* h_wide_flag = nullptr;    // pinned: the flag word of the records of DEVICE rows, read by lig_rows_commit with the root
     lig_proof_info info1;               // stage-1 results kept between lig_rows_commit and lig_rows_prove
     size_t R = 0, RB = 0, n_init = 0;   // all rows, leading rows committed by the batch program, of those: init rows
     fr* msgs = nullptr;                 // R x k witness matrix (pads are re-drawn by every prove)
@@ -318,7 +320,7 @@ static int prove_stage1(lig_trace* T, lig_proof_info* info, const std::function<
             if (T->up_by_thread) HIP_TRY(c, hipStreamWaitValue32(s_enc, T->flags.dev + ci, T->up.seq, hipStreamWaitValueGte, 0xffffffffu));
             else HIP_TRY(c, hipStreamWaitEvent(s_enc, T->ev_up[ci], 0));                   // this chunk's rows have arrived
             // (a derived row whose x / y rows belong to the previous chunk reads them from the staging area: that chunk's arrival was waited for earlier on this stream)
-            if (T->narrow) lig::launch_expand_rows(s_enc, T->packed_dev, T->src_off_dev, T->widths_dev, b, nb, l, k, T->msgs, T->prod.first(b), T->prod.count(b, b + nb));
+            if (T->narrow) lig::launch_expand_rows(s_enc, T->packed_dev, T->src_off_dev, T->widths_dev, b, nb, l, k, T->msgs, T->prod.first(b), T->prod.count(b, b + nb), T->wide.args(b, b + nb));
             for (; pr_i < T->pad_runs.size() && T->pad_runs[pr_i].first < b + nb; pr_i++) {      // runs never straddle chunks (split in begin)
                 const PadRun& pr = T->pad_runs[pr_i];
                 lig::launch_rng_fill_rows(s_enc, c->rk_dev, pr.pos, T->msgs + pr.first * (size_t)k, pr.count, pad, k, l, 1, pad);
@@ -386,7 +388,11 @@ static int prove_stage1(lig_trace* T, lig_proof_info* info, const std::function<
     lig::launch_sha_final(s, T->sha_state, n, absorbed, leaf_level, k);      // plane-major instances -> leaves in column order, written in place
     TRY(lig_merkle_build(c, leaf_level, n, T->nodes));
     TRY(lig_internal_download(c, T->h_nodes, T->nodes, 32, s));              // the root now ...
+    // (mixed DEVICE rows: the host has not seen their records -- rows_load expanded them on this stream -- so the flag word comes with the root)
+    const bool wide_flag = !streamed && T->wide.any();
+    if (wide_flag) HIP_TRY(c, hipMemcpyAsync(T->h_wide_flag, T->wide.flag_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(s));
+    if (wide_flag && *T->h_wide_flag) FAIL(c, LIG_E_ARG, "lig_rows_commit: a wide slot of the device rows names a column >= l (lig_rows_job.wide_per_row); lig_rows_restart with good rows");
     if (streamed && T->up_by_thread) {
         // every chunk has been waited for by now; a copy the uploader thread could not make leaves garbage rows behind
         if (const int e = T->up.take_error()) {
@@ -714,6 +720,7 @@ void lig_trace_destroy(lig_trace* T) {
     for (hipEvent_t e : T->ev_up) (void)hipEventDestroy(e);
     T->flags.release();
     (void)hipFree(T->src_off_dev); (void)hipFree(T->widths_dev); (void)hipFree(T->packed_dev); (void)hipFree(T->prod.dev);
+    T->wide.release(); (void)hipHostFree(T->h_wide_flag);
     (void)hipHostFree(T->h_proof); (void)hipHostFree(T->h_enc); (void)hipHostFree(T->h_nodes); (void)hipHostFree(T->h_small);
     delete T;
 }
@@ -792,7 +799,8 @@ static int rows_load(lig_ctx* c, lig_trace* T, const void* msgs, bool on_device)
         T->alt_pending = true;
     }
     if (on_device) {
-        if (T->narrow) lig::launch_expand_rows(c->stream, (const uint8_t*)msgs, T->src_off_dev, T->widths_dev, 0, R, c->l, k, dst, T->prod.dev, T->prod.rows.size());
+        if (T->wide.any()) HIP_TRY(c, hipMemsetAsync(T->wide.flag_dev, 0, sizeof(uint32_t), c->stream));      // raised by a record with a column >= l: lig_rows_commit
+        if (T->narrow) lig::launch_expand_rows(c->stream, (const uint8_t*)msgs, T->src_off_dev, T->widths_dev, 0, R, c->l, k, dst, T->prod.dev, T->prod.rows.size(), T->wide.args(0, R));
         else HIP_TRY(c, hipMemcpyAsync(dst, msgs, R * (size_t)k * 32, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(c, hipGetLastError());
         return LIG_OK;
@@ -829,16 +837,20 @@ static int rows_begin_impl(lig_ctx* c, const lig_rows_job* job, lig_trace* T) {
     T->dense_rands = job->dense_rands_per_row != nullptr;
     T->mask_pos = pos[R];
     lig::NarrowPlan np;
-    if (job->elem_bytes) {            // the narrow row format; every row is local
+    if (job->elem_bytes || lig::job_wide_per_row(*job)) {            // the narrow row format; every row is local
         std::vector<size_t> all(R);
         for (size_t r = 0; r < R; r++) all[r] = r;
-        if (const char* why = lig::plan_narrow_rows(job->elem_bytes, T->rows, draw, l, k, all, np)) FAIL(c, LIG_E_ARG, std::string("rows job: ") + why);
+        if (const char* why = lig::plan_narrow_rows(job->elem_bytes, T->rows, draw, l, k, all, np, lig::job_wide_per_row(*job))) FAIL(c, LIG_E_ARG, std::string("rows job: ") + why);
+        // mixed host rows: their records are read here, before anything is allocated, copied or launched
+        if (!job->msgs_on_device && !np.mixed_rows.empty())
+            if (const char* why = lig::wide_records_refusal((const uint8_t*)job->msgs, np.src_off, np.mixed_rows, np.wide, l)) FAIL(c, LIG_E_ARG, std::string("rows job: ") + why);
     }
     T->narrow = np.packed;
     TRY(trace_alloc(c, T));
     if (T->narrow) {
-        TRY(lig_internal_upload_narrow_plan(c, np, &T->src_off_dev, &T->widths_dev, &T->prod));
+        TRY(lig_internal_upload_narrow_plan(c, np, &T->src_off_dev, &T->widths_dev, &T->prod, &T->wide));
         T->src_off = std::move(np.src_off);
+        if (T->wide.any()) HIP_TRY(c, hipHostMalloc((void**)&T->h_wide_flag, sizeof(uint32_t)));
         if (!job->msgs_on_device) HIP_TRY(c, hipMalloc((void**)&T->packed_dev, T->src_off[R] ? T->src_off[R] : 16));
     }
     // pad runs: consecutive flagged rows whose stream positions are consecutive, never straddling a stage-1 chunk
@@ -872,6 +884,8 @@ int lig_rows_restart(lig_trace* T, const void* msgs, int msgs_on_device) {
     if (T->R && !msgs) FAIL(c, LIG_E_ARG, "lig_rows_restart: null rows");
     if (T->leak) FAIL(c, LIG_E_STATE, "lig_rows_restart: a transfer into this trace's buffers never completed (lig_upload_health): destroy the trace");
     if (T->loaded && T->host_msgs) { T->up.drain(); if (c->stream3) HIP_TRY(c, hipStreamSynchronize(c->stream3)); }      // an upload nobody committed: let it finish first
+    if (!msgs_on_device && T->wide.any())                 // mixed host rows: the records are read before any copy starts
+        if (const char* why = lig::wide_records_refusal((const uint8_t*)msgs, T->src_off, T->wide.mixed.rows, T->wide.wide, c->l)) FAIL(c, LIG_E_ARG, std::string("lig_rows_restart: ") + why);
     if (!T->committed) T->diag_ok = false;                // the rows go straight into the matrix: the window of lig_rows_diagnose ends
     return rows_load(c, T, msgs, msgs_on_device != 0);
 }

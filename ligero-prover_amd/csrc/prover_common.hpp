@@ -47,8 +47,13 @@ void launch_copy_from_host(hipStream_t s, uint8_t* dst_dev, const uint8_t* src_m
 // packed + off_dev[r], width widths_dev[r] -- into out + r * k, full width; slots l..k-1 of a narrow row are zeroed.
 // prod_rows_dev[0 .. n_prod): the derived rows (LIG_ELEM_PRODUCT) among them, ascending row indices -- formed from the packed
 // sources of the two rows in front of each (which may lie before first_row: they only have to be in `packed`)
+// wd: the mixed rows (lig_rows_job.wide_per_row) among them -- mixed_rows_dev[0 .. n_mixed) ascending row indices, wide_dev[r] = the
+// records of row r (every row of the matrix; NULL: the matrix has no mixed row), max_records = the largest count, flag_dev = one
+// word that a record with a column >= l raises.  n_mixed == 0: nothing more is launched than without the member.
+struct WideArgs { const uint32_t* mixed_rows_dev = nullptr; size_t n_mixed = 0; const uint32_t* wide_dev = nullptr; uint32_t max_records = 0; uint32_t* flag_dev = nullptr; };
 void launch_expand_rows(hipStream_t s, const uint8_t* packed, const uint64_t* off_dev, const uint8_t* widths_dev, size_t first_row,
-                        size_t rows, uint32_t l, uint32_t k, fr* out, const uint32_t* prod_rows_dev = nullptr, size_t n_prod = 0);
+                        size_t rows, uint32_t l, uint32_t k, fr* out, const uint32_t* prod_rows_dev = nullptr, size_t n_prod = 0,
+                        const WideArgs& wd = WideArgs());
 }  // namespace lig
 
 // (outside the anonymous namespace: these types appear in functions shared between translation units)
@@ -59,8 +64,24 @@ struct ProductRows {
     const uint32_t* first(size_t b) const { return dev + (std::lower_bound(rows.begin(), rows.end(), (uint32_t)b) - rows.begin()); }
     size_t count(size_t b, size_t e) const { return std::lower_bound(rows.begin(), rows.end(), (uint32_t)e) - std::lower_bound(rows.begin(), rows.end(), (uint32_t)b); }
 };
+// the mixed rows of a packed matrix (lig_rows_job.wide_per_row), ascending, with the records of every row (`wide`: empty when no row
+// is mixed), their copies on the device and the flag word of k_expand_wide: what launch_expand_rows takes for rows [b, e)
+struct WideRows {
+    ProductRows mixed;
+    std::vector<uint32_t> wide;
+    uint32_t* wide_dev = nullptr; uint32_t* flag_dev = nullptr;
+    uint32_t max_records = 0;
+    bool any() const { return !mixed.rows.empty(); }
+    lig::WideArgs args(size_t b, size_t e) const {
+        lig::WideArgs a;
+        if (!any()) return a;
+        a.mixed_rows_dev = mixed.first(b); a.n_mixed = mixed.count(b, e); a.wide_dev = wide_dev; a.max_records = max_records; a.flag_dev = flag_dev;
+        return a;
+    }
+    void release() { (void)hipFree(mixed.dev); (void)hipFree(wide_dev); (void)hipFree(flag_dev); mixed.dev = wide_dev = flag_dev = nullptr; }
+};
 // a packed plan (rows_plan.hpp) -> what launch_expand_rows reads on the device (expand.hip; synchronous copies, the caller frees)
-int lig_internal_upload_narrow_plan(lig_ctx* c, const lig::NarrowPlan& plan, uint64_t** src_off_dev, uint8_t** widths_dev, ProductRows* prod);
+int lig_internal_upload_narrow_plan(lig_ctx* c, const lig::NarrowPlan& plan, uint64_t** src_off_dev, uint8_t** widths_dev, ProductRows* prod, WideRows* wide);
 // what a trace or a shard keeps of its job's header; ih = instance_hash of the public arguments
 struct JobHeader {
     uint8_t encoding_seed[32] = {0}, program_hash[32] = {0}, ih[32] = {0};

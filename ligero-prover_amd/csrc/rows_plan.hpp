@@ -4,6 +4,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "../../include/lig_hip.h"
@@ -99,31 +100,74 @@ inline const char* narrow_row_refusal(const uint8_t* elem_bytes, size_t r, uint8
     return nullptr;
 }
 
+// the record counts of a rows job: the member is read only from a struct that says it has it (lig_hip.h, LIG_ROWS_JOB_WIDE: a caller
+// built before the member existed passes a shorter struct)
+inline const uint32_t* job_wide_per_row(const lig_rows_job& job) { return (job.reserved & LIG_ROWS_JOB_WIDE) ? job.wide_per_row : nullptr; }
+// wide_per_row[r] of a rows job (mixed rows: a narrow row followed by c records of LIG_WIDE_RECORD_BYTES) checked against the row's
+// width (elem_bytes == NULL: every row is full width).  nullptr = accepted.
+inline const char* wide_row_refusal(const uint8_t* elem_bytes, const uint32_t* wide, size_t r, uint32_t l) {
+    if (!wide || !wide[r]) return nullptr;
+    const uint8_t w = elem_bytes ? elem_bytes[r] : 32;
+    if (w != LIG_ELEM_BIT && w != 1 && w != 2 && w != 4 && w != 8) return "wide_per_row is only accepted on a row of width LIG_ELEM_BIT, 1, 2, 4 or 8";
+    if (wide[r] > l) return "wide_per_row: more records than the row has data slots";
+    return nullptr;
+}
+
 // The narrow row format (lig_rows_job.elem_bytes) of the rows a device holds.  `local` = the global row of every local row, commit
 // order: all rows on one GPU, the rows a rank was dealt on a shard (the deal never splits a triple: the x and y of a derived local
 // row lr are local rows lr - 2, lr - 1).  Every row of the job is checked, whoever holds it; packed = some row of the JOB is not
 // full width (a derived row alone counts) -- false: the plain path, the rest is left empty.
+// Mixed rows (lig_rows_job.wide_per_row, one count per row of the JOB; nullptr: none): the c records of a local row lr are the last
+// 36 c bytes of its packed range, [src_off[lr + 1] - 36 c, src_off[lr + 1]).
 struct NarrowPlan {
     bool packed = false;
     std::vector<uint8_t> widths;          // per local row (one entry at least: nothing of size 0 goes to the device)
-    std::vector<uint64_t> src_off;        // packed byte offset of every local row (+1 entry = all the bytes this device is given)
+    std::vector<uint64_t> src_off;        // packed byte offset of every local row (+1 entry = all the bytes this device is given), records included
     std::vector<uint32_t> prod_rows;      // local indices of the derived rows (LIG_ELEM_PRODUCT), ascending
+    std::vector<uint32_t> wide;           // records per local row; EMPTY when no local row is mixed
+    std::vector<uint32_t> mixed_rows;     // local indices of the mixed rows, ascending
 };
 inline const char* plan_narrow_rows(const uint8_t* elem_bytes, const std::vector<RowDesc>& rows, const std::vector<uint8_t>& draw, uint32_t l,
-                                    uint32_t k, const std::vector<size_t>& local, NarrowPlan& out) {
+                                    uint32_t k, const std::vector<size_t>& local, NarrowPlan& out, const uint32_t* wide_per_row = nullptr) {
     out = NarrowPlan{};
     for (size_t r = 0; r < rows.size(); r++) {
-        if (const char* why = narrow_row_refusal(elem_bytes, r, rows[r].kind, draw[r] != 0, l, k)) return why;
-        out.packed = out.packed || (elem_bytes[r] != 0 && elem_bytes[r] != 32);
+        if (elem_bytes) {
+            if (const char* why = narrow_row_refusal(elem_bytes, r, rows[r].kind, draw[r] != 0, l, k)) return why;
+            out.packed = out.packed || (elem_bytes[r] != 0 && elem_bytes[r] != 32);
+        }
+        if (const char* why = wide_row_refusal(elem_bytes, wide_per_row, r, l)) return why;
     }
     if (!out.packed) return nullptr;
     out.widths.assign(local.empty() ? 1 : local.size(), 32);
     out.src_off.assign(local.size() + 1, 0);
     for (size_t lr = 0; lr < local.size(); lr++) {
         const uint8_t w = elem_bytes[local[lr]] ? elem_bytes[local[lr]] : 32;
+        const uint32_t c = wide_per_row ? wide_per_row[local[lr]] : 0;
         out.widths[lr] = w;
-        out.src_off[lr + 1] = out.src_off[lr] + narrow_row_bytes(w, l, k);
+        out.src_off[lr + 1] = out.src_off[lr] + narrow_row_bytes(w, l, k) + (uint64_t)c * LIG_WIDE_RECORD_BYTES;
         if (w == LIG_ELEM_PRODUCT) out.prod_rows.push_back((uint32_t)lr);
+        if (c) out.mixed_rows.push_back((uint32_t)lr);
+    }
+    if (!out.mixed_rows.empty()) {
+        out.wide.assign(local.size(), 0);
+        for (const uint32_t lr : out.mixed_rows) out.wide[lr] = wide_per_row[local[lr]];
+    }
+    return nullptr;
+}
+// The records of mixed HOST rows, read before any copy starts: `packed` = the rows of the plan back to back (src_off), mixed_rows /
+// wide as in the plan.  nullptr = every column is < l and the columns of every row are strictly ascending.
+inline const char* wide_records_refusal(const uint8_t* packed, const std::vector<uint64_t>& src_off, const std::vector<uint32_t>& mixed_rows,
+                                        const std::vector<uint32_t>& wide, uint32_t l) {
+    for (const uint32_t lr : mixed_rows) {
+        const uint8_t* rec = packed + src_off[lr + 1] - (uint64_t)wide[lr] * LIG_WIDE_RECORD_BYTES;
+        uint32_t prev = 0;
+        for (uint32_t j = 0; j < wide[lr]; j++, rec += LIG_WIDE_RECORD_BYTES) {
+            uint32_t col;
+            std::memcpy(&col, rec, 4);
+            if (col >= l) return "a wide slot names a column >= l";
+            if (j && col <= prev) return "the wide slots of a row are not in strictly ascending column order";
+            prev = col;
+        }
     }
     return nullptr;
 }

@@ -66,6 +66,7 @@ struct lig_shard {
     std::vector<uint64_t> src_off;
     uint64_t* src_off_dev = nullptr; uint8_t* widths_dev = nullptr; uint8_t* packed_dev = nullptr;
     ProductRows prod;                          // derived LOCAL rows (LIG_ELEM_PRODUCT)
+    WideRows wide;                             // mixed LOCAL rows (lig_rows_job.wide_per_row)
     // sparse linear system (lig_shard_rows_set_linear): this rank's share of it, regrouped by local slot (linear.hip), and the local rows x k
     // randomness matrix it is formed into per proof; both survive lig_shard_rows_restart
     lig_linear* linear = nullptr;
@@ -316,7 +317,7 @@ void lig_shard_destroy(lig_shard* S) {
     for (void* p : {(void*)S->msgs, (void*)S->cw, (void*)S->maskcw, (void*)S->send, (void*)S->recv, (void*)S->randb, (void*)S->rhalf, (void*)S->acc,
                     (void*)S->parts, (void*)S->accp, (void*)S->accg, (void*)S->dots, (void*)S->smp, (void*)S->smpg, (void*)S->sha_state,
                     (void*)S->leaves_slice, (void*)S->leaves, (void*)S->nodes, (void*)S->tri_dev, (void*)S->coef_dev, (void*)S->src_off_dev,
-                    (void*)S->widths_dev, (void*)S->packed_dev, (void*)S->prod.dev})
+                    (void*)S->widths_dev, (void*)S->packed_dev, (void*)S->prod.dev, (void*)S->wide.mixed.dev, (void*)S->wide.wide_dev, (void*)S->wide.flag_dev})
         (void)hipFree(p);
     for (int i = 0; i < 2; i++)
         for (hipEvent_t e : {S->ev_enc[i], S->ev_comm[i], S->ev_hash[i]}) if (e) (void)hipEventDestroy(e);
@@ -763,6 +764,8 @@ int lig_shard_rows_plan(const uint8_t* kinds, size_t n_rows, uint32_t world, uin
 static int shard_rows_load(lig_shard* S, const void* local_msgs, bool on_device) {
     lig_ctx* c = S->c;
     if (S->Rl && !local_msgs) FAIL(c, LIG_E_ARG, "sharded rows job: null local rows");
+    if (!on_device && S->wide.any())                   // mixed host rows: the records are read before any copy starts
+        if (const char* why = lig::wide_records_refusal((const uint8_t*)local_msgs, S->src_off, S->wide.mixed.rows, S->wide.wide, c->l)) FAIL(c, LIG_E_ARG, std::string("sharded rows job: ") + why);
     S->up.drain();                                     // an upload nobody committed
     HIP_TRY(c, hipStreamSynchronize(c->stream));      // the previous trace is done with S->msgs
     S->committed = false;
@@ -779,9 +782,15 @@ static int shard_rows_load(lig_shard* S, const void* local_msgs, bool on_device)
             if (S->src_off[S->Rl]) HIP_TRY(c, hipMemcpyAsync(S->packed_dev, local_msgs, S->src_off[S->Rl], hipMemcpyHostToDevice, c->stream));
             src = S->packed_dev;
         }
-        lig::launch_expand_rows(c->stream, src, S->src_off_dev, S->widths_dev, 0, S->Rl, c->l, c->k, S->msgs, S->prod.dev, S->prod.rows.size());
+        const bool wide_flag = on_device && S->wide.any();      // the host has not seen the records of device rows: k_expand_wide raises a word
+        if (wide_flag) HIP_TRY(c, hipMemsetAsync(S->wide.flag_dev, 0, sizeof(uint32_t), c->stream));
+        lig::launch_expand_rows(c->stream, src, S->src_off_dev, S->widths_dev, 0, S->Rl, c->l, c->k, S->msgs, S->prod.dev, S->prod.rows.size(), S->wide.args(0, S->Rl));
         HIP_TRY(c, hipGetLastError());
+        uint32_t raised = 0;
+        if (wide_flag) HIP_TRY(c, hipMemcpyAsync(&raised, S->wide.flag_dev, sizeof raised, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's memory is no longer referenced
+        // (refused here, before any collective is queued: no peer is left waiting)
+        if (raised) FAIL(c, LIG_E_ARG, "sharded rows job: a wide slot of the device rows names a column >= l (lig_rows_job.wide_per_row)");
         return LIG_OK;
     }
     // Host rows are copied HERE, synchronously (as in round 3).  Round 4 had moved them onto the library's uploader thread with a stream
@@ -823,13 +832,13 @@ int lig_shard_rows_begin(lig_ctx* c, const lig_rows_job* job, uint32_t rank, uin
     S->lin_pos.assign(R + 1, 0); S->wit_pos.assign(R + 1, 0);
     for (size_t r = 0; r < R; r++) S->lin_pos[r + 1] = S->lin_pos[r] + S->rows[r].data;
     int rc = shard_alloc(c, rank, world, S);
-    if (rc == LIG_OK && job->elem_bytes) {
+    if (rc == LIG_OK && (job->elem_bytes || lig::job_wide_per_row(*job))) {
         // the narrow row format: every row of the job is checked as lig_rows_begin does, the plan is of the local rows; the staging
         // buffer of host rows is allocated by the first load from host memory (device rows are expanded where they are)
         lig::NarrowPlan np;
-        if (const char* why = lig::plan_narrow_rows(job->elem_bytes, S->rows, S->draw, l, k, S->grow, np)) { c->err = std::string("sharded rows job: ") + why; rc = LIG_E_ARG; }
+        if (const char* why = lig::plan_narrow_rows(job->elem_bytes, S->rows, S->draw, l, k, S->grow, np, lig::job_wide_per_row(*job))) { c->err = std::string("sharded rows job: ") + why; rc = LIG_E_ARG; }
         else if ((S->narrow = np.packed)) {
-            rc = lig_internal_upload_narrow_plan(c, np, &S->src_off_dev, &S->widths_dev, &S->prod);
+            rc = lig_internal_upload_narrow_plan(c, np, &S->src_off_dev, &S->widths_dev, &S->prod, &S->wide);
             S->src_off = std::move(np.src_off);
         }
     }
