@@ -499,8 +499,8 @@ int  lig_linear_program_form(lig_ctx *ctx, const lig_linear_program *p, const ui
  * the call and freed before it returns: this is not the proving path.  Its work is enqueued on the context stream alone, but freeing
  * the scratch waits for the whole device: while the rows of a lig_rows_restart are still arriving, the call returns after them.
  * info->ms_total is the whole call, the host pass of lig_linear_check over sys (one step per term) included.
- * lig_shard_rows_* is NOT covered: a rank holds only the rows it was dealt and a constraint may span ranks.  There is no verifier
- * side: the verifier has no witness. */
+ * The sharded entry has its own call, lig_shard_rows_diagnose below (a rank holds only the rows it was dealt and a constraint may span
+ * ranks).  There is no verifier side: the verifier has no witness. */
 typedef struct { uint32_t constraint, reserved; uint8_t residual[32]; } lig_diag_linear;          /* 40 bytes */
 typedef struct { uint32_t row_x, row_y, row_z, column; uint8_t residual[32]; } lig_diag_quad;     /* 48 bytes */
 typedef struct {
@@ -632,6 +632,36 @@ int lig_shard_rows_linear_stats(const lig_shard *shard, uint64_t *local_terms, u
  * GPU is touched.  LIG_E_ARG: world == 0, rank >= world, a system lig_linear_check rejects. */
 int lig_linear_shard_count(const lig_linear_system *sys, const uint8_t *kinds, uint64_t rows, uint32_t l, uint32_t rank, uint32_t world,
                            uint64_t *local_terms, uint64_t *needed_constraints);
+
+/* lig_rows_diagnose on a rows shard (csrc/diagnose.hip, csrc/shard.hip).  COLLECTIVE: every rank calls it with the same `sys` -- the system
+ * of the WHOLE trace, global slots, as lig_shard_rows_set_linear takes it -- and the same caps.  EVERY RANK RETURNS THE SAME BYTES, and
+ * they are exactly what lig_rows_diagnose returns for the whole trace on one GPU: lig_diag_linear records in ascending constraint number,
+ * lig_diag_quad records in ascending (term in commit order, column) with GLOBAL row numbers, counts that cover all violations, a cap of
+ * 0 for counts only.  sys == NULL: the quadratic part only.  sys->coefs is used as passed; the system set with
+ * lig_shard_rows_set_linear is neither read nor written.
+ * HOW: linear constraints go in slices of LIG_DIAG_SLICE constraints (default 2^22).  Per slice every rank sums a * w over the terms
+ * whose row it holds (a rank without rows: zeros), ONE all-to-all sends the partials of sub-block h of the slice to rank h, which adds
+ * the W partials, subtracts b_c and keeps its first lin_cap violations; counts and records are all-gathered in blocks of a fixed size and
+ * merged on the host of every rank.  A quadratic term never spans ranks (the deal does not split a triple or a pair): each rank
+ * evaluates its own, keeps its first quad_cap violations with the terms' global ordinals, and the blocks are all-gathered and merged by
+ * (ordinal, column).  Arithmetic is exact and no atomic decides an order or a count: the same bytes on every run.  Whether a collective
+ * is issued, how many and of which size depends on the sizes in sys, the caps, world and the slice size alone -- never on what a rank
+ * holds.  world == 1: no collective at all (unless LIG_SHARD_FORCE_EXCHANGE is set), the call is lig_rows_diagnose.
+ * WHEN: from the return of lig_shard_rows_commit until the next lig_shard_rows_restart, before or after lig_shard_rows_prove; the
+ * envelope of a diagnosed shard is byte-identical to that of one that was not.
+ * ERRORS, all decided on the host, identically on every rank, before any launch and any collective: LIG_E_ARG for a system
+ * lig_linear_check rejects, a NULL array with a cap > 0, a short info->struct_bytes; LIG_E_STATE before the commit, for a shard not made
+ * by lig_shard_rows_begin, for a poisoned shard.  FAILURE of a peer or of the communicator: as every lig_shard_* call (bounded polls,
+ * lig_comm.failed after the streams have drained, lig_comm.abort after LIG_COMM_TIMEOUT_S, poisoning).
+ * SCRATCH is allocated inside the call and freed before it returns (lig_comm.forget runs first; every send buffer is an allocation of
+ * its own); the work runs on the context's main stream.  With S = min(LIG_DIAG_SLICE, n_constraints) rounded to a multiple of W, B = S / W
+ * and T = the quadratic terms of the whole trace, a rank allocates at most
+ *     64 S + 40 B + 8 (B + 1)  +  (W + 1) (16 + 40 min(lin_cap, n_constraints))  +  (W + 1) (16 + 52 min(quad_cap, T l))  bytes
+ * plus what lig_rows_diagnose allocates whatever the witness: the uploaded system (8 n_terms + 8 n_constraints + 8 n_rhs + 32 n_coefs),
+ * 4 bytes per row of the trace, 40 bytes per item of a quadratic slice (2^20 items) and the scan's temporary storage.
+ * Not done: skipping the exchange for constraints whose terms all lie on one rank (it would make the schedule depend on the data). */
+int lig_shard_rows_diagnose(lig_shard *shard, const lig_linear_system *sys, lig_diag_linear *lin_out, uint64_t lin_cap,
+                            lig_diag_quad *quad_out, uint64_t quad_cap, lig_diag_info *info);
 
 /* sizeof of the public structs as this build of the library sees them, in the order {lig_batch_op, lig_synth_job, lig_proof_info,
  * lig_verify_info, lig_rows_job, lig_comm}: a binding in another language (ctypes, cgo, JNI) checks its own layouts against these at

@@ -310,14 +310,19 @@ public:
     // set_linear_values, if one was set -- after commit(), before or after prove(), until the next commit().  A batcher that was
     // given a prepared program (set_linear_program) or no system has no term list to evaluate: the quadratic part only.  Upstream
     // the same witness would have tripped the asserts of constrain_equal / constrain_bit while the guest ran
-    // (witness_manager.hpp:418-431).  Not for a sharded batcher (a constraint may span ranks).
+    // (witness_manager.hpp:418-431).  With shard_over(): lig_shard_rows_diagnose, a COLLECTIVE call -- every rank calls it with the same
+    // caps and gets the output of the unsharded batcher, global row numbers included (a constraint may span ranks: the ranks' partial
+    // sums are reduced across them).
     void diagnose(lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
-        if (sharded_) throw std::logic_error("hip_row_batcher::diagnose: not for a sharded batcher");
-        if (pass_ == 1 || !trace_) throw std::logic_error("hip_row_batcher::diagnose before commit");
+        if (pass_ == 1 || !(sharded_ ? (bool)shard_ : (bool)trace_)) throw std::logic_error("hip_row_batcher::diagnose before commit");
         if (!info) throw std::invalid_argument("hip_row_batcher::diagnose: null info");
         lig_linear_system sys = *linear_.get();
         if (values_set_) { sys.coefs = values_.data(); sys.n_coefs = values_.size() / 32; }
         info->struct_bytes = sizeof(lig_diag_info);
+        if (sharded_) {
+            check(lig_shard_rows_diagnose(shard_, linear_.is_set() ? &sys : nullptr, lin_out, lin_cap, quad_out, quad_cap, info), "lig_shard_rows_diagnose");
+            return;
+        }
         check(lig_rows_diagnose(trace_, linear_.is_set() ? &sys : nullptr, lin_out, lin_cap, quad_out, quad_cap, info), "lig_rows_diagnose");
     }
     // the next proof with this batcher: staging and (for the same row kinds) every device buffer of the trace are kept

@@ -39,7 +39,7 @@ EXPORTS = [
     "lig_abi_sizes", "lig_shard_rows_plan", "lig_shard_rows_begin", "lig_shard_rows_restart", "lig_shard_rows_commit", "lig_shard_rows_prove",
     "lig_upload_health", "lig_profile_read_launches",
     "lig_linear_check", "lig_linear_form", "lig_rows_set_linear", "lig_rows_verify_set_linear",
-    "lig_shard_rows_set_linear", "lig_shard_rows_linear_stats", "lig_linear_shard_count",
+    "lig_shard_rows_set_linear", "lig_shard_rows_linear_stats", "lig_linear_shard_count", "lig_shard_rows_diagnose",
     "lig_linear_prepare", "lig_linear_program_release", "lig_linear_program_bytes", "lig_rows_attach_linear", "lig_rows_verify_attach_linear",
     "lig_rows_set_linear_values", "lig_rows_verify_set_linear_values", "lig_linear_program_form",
     "lig_rows_diagnose",
@@ -363,6 +363,7 @@ def load_library():
     L.lig_rows_verify_set_linear_values.argtypes = [vp, vp, u64]
     L.lig_linear_program_form.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.lig_rows_diagnose.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, u64, C.POINTER(DiagInfo)]
+    L.lig_shard_rows_diagnose.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, u64, C.POINTER(DiagInfo)]
     return L
 
 
@@ -1090,6 +1091,16 @@ class Context:
         lin, quad = np.zeros(lin_cap, dtype=DIAG_LINEAR), np.zeros(quad_cap, dtype=DIAG_QUAD)
         self.check(self.L.lig_rows_diagnose(trace, C.byref(system) if system is not None else None, _hptr(lin) if lin_cap else None, lin_cap,
                                             _hptr(quad) if quad_cap else None, quad_cap, C.byref(info)))
+        return info, lin[:info.n_linear_reported], quad[:info.n_quad_reported]
+
+    def shard_rows_diagnose(self, shard, system=None, lin_cap=1024, quad_cap=1024):
+        """lig_shard_rows_diagnose: rows_diagnose on a rows shard.  Collective: every rank passes the same `system` (of the WHOLE trace) and
+        the same caps, and every rank gets what rows_diagnose gives for the whole trace on one GPU (global row numbers)"""
+        info = DiagInfo()
+        info.struct_bytes = C.sizeof(DiagInfo)
+        lin, quad = np.zeros(lin_cap, dtype=DIAG_LINEAR), np.zeros(quad_cap, dtype=DIAG_QUAD)
+        self.check(self.L.lig_shard_rows_diagnose(shard, C.byref(system) if system is not None else None, _hptr(lin) if lin_cap else None, lin_cap,
+                                                  _hptr(quad) if quad_cap else None, quad_cap, C.byref(info)))
         return info, lin[:info.n_linear_reported], quad[:info.n_quad_reported]
 
     def vtrace_destroy(self, vtrace):

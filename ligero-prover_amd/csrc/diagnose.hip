@@ -8,6 +8,11 @@
 //                      coefficient first (Montgomery copy of the table: one product per such term), subtracts b_c
 //   k_diag_lin_heavy   one workgroup per constraint with more terms: lanes stride the segment, fixed LDS tree (lin_block_sum)
 //   k_diag_quad        one lane per (quadratic term, column < l): x * y - z, b * b - b for a bit row, x - z for an equality pair
+// and, for one rank of a sharded rows job (lig_shard_rows_diagnose: the rank holds only the rows it was dealt, a constraint may span ranks):
+//   k_diag_lin_part, k_diag_lin_part_heavy   the same two walks over a slice of the constraints, through the rank's global -> local row
+//                      table: a * w of the terms whose row the rank holds, the others skipped; a canonical PARTIAL per constraint, no b_c, no flag
+//   k_diag_reduce      the owner of a sub-block of the slice adds the W partials it received, subtracts b_c, writes residual and flag
+// (exact arithmetic mod p: no result depends on an order).
 // Every lane writes its canonical residual and a 32-bit flag; the flags go through an exclusive scan (rocPRIM) and the first `cap`
 // violated items are scattered into a record array in ascending order -- no atomic decides an order or a count, the output is the same
 // bytes on every run.  The quadratic items (terms x l) are processed in slices of a fixed scratch budget; the running count and the
@@ -33,10 +38,16 @@ static __device__ __forceinline__ fr diag_one() {
     o.v[0] = 1;
     return o;
 }
-// acc (canonical) += coef * w[slot] for one term
+// where the row a term names lies in `msgs`: the whole matrix (one GPU), or a rank's share through its global -> local row table
+// (LIN_NOT_LOCAL: another rank holds that row)
+struct DiagAllRows { __device__ __forceinline__ uint32_t operator()(uint32_t row) const { return row; } };
+struct DiagLocalRows { const uint32_t* __restrict__ local_of; __device__ __forceinline__ uint32_t operator()(uint32_t row) const { return local_of[row]; } };
+// acc (canonical) += coef * w[slot] for one term (unchanged for a term whose row is not in `msgs`)
+template <class Rows>
 static __device__ __forceinline__ fr diag_accumulate(const fr& acc, const lig_lin_term tm, const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip,
-                                                     const fr* __restrict__ coef_mont) {
-    const uint32_t row = diag_div(tm.slot, l_recip), col = tm.slot - row * l;
+                                                     const fr* __restrict__ coef_mont, const Rows rows) {
+    const uint32_t grow = diag_div(tm.slot, l_recip), col = tm.slot - grow * l, row = rows(grow);
+    if (row == LIN_NOT_LOCAL) return acc;
     const fr w = fr_load(msgs + (size_t)row * k + col);
     if (tm.coef == LIG_COEF_ONE) return fr_add(acc, w);
     if (tm.coef == LIG_COEF_NEG_ONE) return fr_sub(acc, w);
@@ -48,13 +59,29 @@ static __device__ __forceinline__ fr diag_coef_value(uint32_t coef, const fr* __
     if (coef == LIG_COEF_NEG_ONE) return fr_neg(diag_one());
     return fr_montmul(fr_load(coef_mont + coef), diag_one());             // (a R) * 1 / R = a
 }
-// acc - b_c -> residual and flag of constraint c; rhs_index[c] = 1 + the position of c in the right-hand-side list, 0: b_c = 0
-static __device__ __forceinline__ void diag_finish(uint32_t c, fr acc, const uint32_t* __restrict__ rhs_index, const uint32_t* __restrict__ rhs_coef,
+// the two walks over the terms [b, e) of one constraint: one lane; or the lanes of a workgroup striding the segment, then the fixed tree
+// (valid in thread 0; reached by all lanes of the workgroup)
+template <class Rows>
+static __device__ __forceinline__ fr diag_sum_lane(uint32_t b, uint32_t e, const lig_lin_term* __restrict__ terms, const fr* __restrict__ msgs, uint32_t l, uint32_t k,
+                                                   uint64_t l_recip, const fr* __restrict__ coef_mont, const Rows rows) {
+    fr acc = fr_zero();
+    for (uint32_t t = b; t < e; t++) acc = diag_accumulate(acc, terms[t], msgs, l, k, l_recip, coef_mont, rows);
+    return acc;
+}
+template <class Rows>
+static __device__ __forceinline__ fr diag_sum_block(uint32_t b, uint32_t e, const lig_lin_term* __restrict__ terms, const fr* __restrict__ msgs, uint32_t l, uint32_t k,
+                                                    uint64_t l_recip, const fr* __restrict__ coef_mont, const Rows rows, fr* sh) {
+    fr acc = fr_zero();
+    for (uint32_t t = b + threadIdx.x; t < e; t += LIN_WG) acc = diag_accumulate(acc, terms[t], msgs, l, k, l_recip, coef_mont, rows);
+    return lin_block_sum(acc, sh);
+}
+// acc - b_c -> residual and flag of constraint c, stored at index `at`; rhs_index[c] = 1 + the position of c in the right-hand-side list, 0: b_c = 0
+static __device__ __forceinline__ void diag_finish(uint32_t c, uint32_t at, fr acc, const uint32_t* __restrict__ rhs_index, const uint32_t* __restrict__ rhs_coef,
                                                    const fr* __restrict__ coef_mont, fr* __restrict__ res, uint32_t* __restrict__ flag) {
     const uint32_t ri = rhs_index[c];
     if (ri) acc = fr_sub(acc, diag_coef_value(rhs_coef[ri - 1], coef_mont));
-    fr_store(res + c, acc);
-    flag[c] = fr_is_zero(acc) ? 0u : 1u;
+    fr_store(res + at, acc);
+    flag[at] = fr_is_zero(acc) ? 0u : 1u;
 }
 
 // rhs_constraint is strictly ascending: every entry of rhs_index is written at most once
@@ -68,9 +95,7 @@ __global__ void __launch_bounds__(LIN_WG) k_diag_lin(const uint32_t* __restrict_
     for (uint64_t c = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; c < n_constraints; c += (uint64_t)gridDim.x * LIN_WG) {
         const uint32_t b = term_begin[c], e = term_begin[c + 1];
         if (e - b > HEAVY_MIN) continue;                                  // k_diag_lin_heavy
-        fr acc = fr_zero();
-        for (uint32_t t = b; t < e; t++) acc = diag_accumulate(acc, terms[t], msgs, l, k, l_recip, coef_mont);
-        diag_finish((uint32_t)c, acc, rhs_index, rhs_coef, coef_mont, res, flag);
+        diag_finish((uint32_t)c, (uint32_t)c, diag_sum_lane(b, e, terms, msgs, l, k, l_recip, coef_mont, DiagAllRows{}), rhs_index, rhs_coef, coef_mont, res, flag);
     }
 }
 // workgroup -> heavy constraint heavy[blockIdx.x + i * gridDim.x]
@@ -81,11 +106,46 @@ __global__ void __launch_bounds__(LIN_WG) k_diag_lin_heavy(const uint32_t* __res
     __shared__ fr sh[LIN_WG];
     for (uint32_t h = blockIdx.x; h < n_heavy; h += gridDim.x) {          // (uniform over the workgroup: the barriers of lin_block_sum are reached by all lanes)
         const uint32_t c = heavy[h], b = term_begin[c], e = term_begin[c + 1];
-        fr acc = fr_zero();
-        for (uint32_t t = b + threadIdx.x; t < e; t += LIN_WG) acc = diag_accumulate(acc, terms[t], msgs, l, k, l_recip, coef_mont);
-        acc = lin_block_sum(acc, sh);
-        if (threadIdx.x == 0) diag_finish(c, acc, rhs_index, rhs_coef, coef_mont, res, flag);
+        const fr acc = diag_sum_block(b, e, terms, msgs, l, k, l_recip, coef_mont, DiagAllRows{}, sh);
+        if (threadIdx.x == 0) diag_finish(c, c, acc, rhs_index, rhs_coef, coef_mont, res, flag);
         __syncthreads();                                                  // sh is reused by the next constraint
+    }
+}
+// One rank of a sharded rows job, constraints [c0, c0 + n) of the system of the WHOLE trace: part[c - c0] = the sum of a * w over the terms whose
+// row this rank holds (local_of: global row -> local row of `msgs`, LIN_NOT_LOCAL for the rows of other ranks) -- zero for a constraint
+// none of whose terms is here, and for every constraint on a rank without rows.  No b_c, no flag: k_diag_reduce on the owner.
+__global__ void __launch_bounds__(LIN_WG) k_diag_lin_part(const uint32_t* __restrict__ term_begin, const lig_lin_term* __restrict__ terms, uint32_t c0, uint32_t n,
+                                                          const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip, const fr* __restrict__ coef_mont,
+                                                          const uint32_t* __restrict__ local_of, fr* __restrict__ part) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t b = term_begin[c0 + i], e = term_begin[c0 + i + 1];
+        if (e - b > HEAVY_MIN) continue;                                  // k_diag_lin_part_heavy
+        fr_store(part + i, diag_sum_lane(b, e, terms, msgs, l, k, l_recip, coef_mont, DiagLocalRows{local_of}));
+    }
+}
+// workgroup -> heavy constraint heavy[blockIdx.x + i * gridDim.x]; heavy[0 .. n_heavy) are the heavy constraints of the slice, all >= c0
+__global__ void __launch_bounds__(LIN_WG) k_diag_lin_part_heavy(const uint32_t* __restrict__ heavy, uint32_t n_heavy, const uint32_t* __restrict__ term_begin,
+                                                                const lig_lin_term* __restrict__ terms, uint32_t c0, const fr* __restrict__ msgs, uint32_t l, uint32_t k,
+                                                                uint64_t l_recip, const fr* __restrict__ coef_mont, const uint32_t* __restrict__ local_of,
+                                                                fr* __restrict__ part) {
+    __shared__ fr sh[LIN_WG];
+    for (uint32_t h = blockIdx.x; h < n_heavy; h += gridDim.x) {          // (uniform over the workgroup, as in k_diag_lin_heavy)
+        const uint32_t c = heavy[h], b = term_begin[c], e = term_begin[c + 1];
+        const fr acc = diag_sum_block(b, e, terms, msgs, l, k, l_recip, coef_mont, DiagLocalRows{local_of}, sh);
+        if (threadIdx.x == 0) fr_store(part + (c - c0), acc);
+        __syncthreads();
+    }
+}
+// The owner of constraints [first, first + n_valid): recv = W blocks of B partials, block g from rank g, entry i of every block = constraint
+// first + i.  res[i] = their sum - b_c, flag[i]; entries [n_valid, B) (beyond the end of the system) get flag 0.
+__global__ void __launch_bounds__(LIN_WG) k_diag_reduce(const fr* __restrict__ recv, uint32_t W, uint32_t B, uint32_t n_valid, uint32_t first,
+                                                        const uint32_t* __restrict__ rhs_index, const uint32_t* __restrict__ rhs_coef, const fr* __restrict__ coef_mont,
+                                                        fr* __restrict__ res, uint32_t* __restrict__ flag) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < B; i += (uint64_t)gridDim.x * LIN_WG) {
+        if (i >= n_valid) { flag[i] = 0u; continue; }
+        fr acc = fr_load(recv + i);
+        for (uint32_t g = 1; g < W; g++) acc = fr_add(acc, fr_load(recv + (size_t)g * B + i));
+        diag_finish(first + (uint32_t)i, (uint32_t)i, acc, rhs_index, rhs_coef, coef_mont, res, flag);
     }
 }
 // item i of the slice = (term first_term + i / l, column i % l); tri = (x, y, z) rows per term, y = 0xFFFFFFFF: the equality term x - z
@@ -101,27 +161,32 @@ __global__ void __launch_bounds__(LIN_WG) k_diag_quad(const uint32_t* __restrict
         flag[i] = fr_is_zero(r) ? 0u : 1u;
     }
 }
-// the violated items with a position below `cap` -> records, in ascending order (pos = exclusive scan of flag)
+// the violated items with a position below `cap` -> records, in ascending order (pos = exclusive scan of flag); item c = constraint first + c
 __global__ void __launch_bounds__(LIN_WG) k_diag_scatter_lin(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos, const fr* __restrict__ res,
-                                                             uint32_t n, uint32_t cap, lig_diag_linear* __restrict__ out) {
+                                                             uint32_t n, uint32_t first, uint32_t cap, lig_diag_linear* __restrict__ out) {
     for (uint64_t c = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; c < n; c += (uint64_t)gridDim.x * LIN_WG) {
         if (!flag[c] || pos[c] >= cap) continue;
         lig_diag_linear rec;
-        rec.constraint = (uint32_t)c; rec.reserved = 0;
+        rec.constraint = first + (uint32_t)c; rec.reserved = 0;
         const fr r = fr_load(res + c);
         for (int w = 0; w < 8; w++) for (int b = 0; b < 4; b++) rec.residual[4 * w + b] = (uint8_t)(r.v[w] >> (8 * b));
         out[pos[c]] = rec;
     }
 }
+// grow (NULL: the rows of `tri` are the job's): local -> global row of a rank's share; ord / ord_out (NULL: none): the global ordinal of every
+// local term, written next to its records
 __global__ void __launch_bounds__(LIN_WG) k_diag_scatter_quad(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos, const fr* __restrict__ res,
                                                               const uint32_t* __restrict__ tri, uint32_t first_term, uint32_t n_items, uint32_t l, uint64_t l_recip,
-                                                              uint32_t cap, lig_diag_quad* __restrict__ out) {
+                                                              uint32_t cap, lig_diag_quad* __restrict__ out, const uint32_t* __restrict__ grow,
+                                                              const uint32_t* __restrict__ ord, uint32_t* __restrict__ ord_out) {
     for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n_items; i += (uint64_t)gridDim.x * LIN_WG) {
         if (!flag[i] || pos[i] >= cap) continue;
         const uint32_t t = diag_div((uint32_t)i, l_recip);
         const uint32_t* q = tri + 3 * (size_t)(first_term + t);
         lig_diag_quad rec;
         rec.row_x = q[0]; rec.row_y = q[1]; rec.row_z = q[2]; rec.column = (uint32_t)i - t * l;
+        if (grow) { rec.row_x = grow[rec.row_x]; if (rec.row_y != 0xFFFFFFFFu) rec.row_y = grow[rec.row_y]; rec.row_z = grow[rec.row_z]; }
+        if (ord_out) ord_out[pos[i]] = ord[first_term + t];
         const fr r = fr_load(res + i);
         for (int w = 0; w < 8; w++) for (int b = 0; b < 4; b++) rec.residual[4 * w + b] = (uint8_t)(r.v[w] >> (8 * b));
         out[pos[i]] = rec;
@@ -132,6 +197,7 @@ __global__ void __launch_bounds__(LIN_WG) k_diag_scatter_quad(const uint32_t* __
 namespace {
 uint64_t diag_reciprocal(uint32_t d) { return d <= 1 ? ~0ull : ~0ull / d + 1; }       // floor(2^64 / d) + 1 (d = 1 is never used: l >= 2)
 uint32_t diag_grid(uint64_t items) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + lig::LIN_WG - 1) / lig::LIN_WG, 1), lig::DIAG_MAX_BLOCKS); }
+using DiagWait = std::function<int()>;      // "the main stream has drained": the way a proof waits (one GPU), or the bounded poll of a shard
 
 // device scratch of one call: freed (after the main stream has drained) when the call returns, whatever way.  hipFree waits for
 // every stream of the device, a prefetch of the next trace included.
@@ -143,6 +209,7 @@ struct DiagScratch {
         if (!bufs.empty()) (void)lig_internal_wait_stream(c->stream);
         for (void* p : bufs) (void)hipFree(p);
     }
+    void abandon() { bufs.clear(); }       // a poisoned shard: kernels that never drained may still touch the buffers, they outlive the call
     int alloc(void** p, size_t bytes) {
         *p = nullptr;
         const hipError_t e = hipMalloc(p, bytes ? bytes : 16);
@@ -153,8 +220,7 @@ struct DiagScratch {
 };
 
 // flag[0 .. n] (flag[n] = 0) -> pos[0 .. n] = exclusive scan; *count = pos[n] = the number of set flags.  Blocks until it is known.
-int diag_scan(lig_ctx* c, DiagScratch& sc, const uint32_t* flag, uint32_t* pos, size_t n, void** scan_tmp, size_t* scan_cap,
-              uint32_t* count) {
+int diag_scan(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, const uint32_t* flag, uint32_t* pos, size_t n, void** scan_tmp, size_t* scan_cap, uint32_t* count) {
     hipStream_t s = c->stream;
     size_t need = 0;
     HIP_TRY(c, rocprim::exclusive_scan(nullptr, need, flag, pos, 0u, n + 1, rocprim::plus<uint32_t>(), s));
@@ -162,7 +228,92 @@ int diag_scan(lig_ctx* c, DiagScratch& sc, const uint32_t* flag, uint32_t* pos, 
     need = *scan_cap;
     HIP_TRY(c, rocprim::exclusive_scan(*scan_tmp, need, flag, pos, 0u, n + 1, rocprim::plus<uint32_t>(), s));
     HIP_TRY(c, hipMemcpyAsync(count, pos + n, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, lig_internal_wait_stream(s));
+    return wait();
+}
+
+// the caller's system on the device: the constraint-major term list as passed, a scratch copy of its table in Montgomery form (the table
+// of an attached program is neither read nor written), rhs_index, the constraints with more than HEAVY_MIN terms (ascending)
+struct DiagSystem {
+    uint32_t NC = 0;
+    std::vector<uint32_t> heavy;
+    uint32_t *tb = nullptr, *rhs_coef = nullptr, *rhs_index = nullptr, *heavy_dev = nullptr;
+    lig_lin_term* terms = nullptr;
+    fr* coef = nullptr;
+};
+int diag_upload_system(lig_ctx* c, DiagScratch& sc, const lig_linear_system* sys, DiagSystem& d) {
+    hipStream_t s = c->stream;
+    const uint32_t NC = d.NC = (uint32_t)sys->n_constraints, NT = (uint32_t)sys->n_terms, NR = (uint32_t)sys->n_rhs;
+    for (uint32_t cn = 0; cn < NC; cn++) if (sys->term_begin[cn + 1] - sys->term_begin[cn] > lig::HEAVY_MIN) d.heavy.push_back(cn);
+    uint32_t* d_rhs_c = nullptr;
+    TRY(sc.alloc((void**)&d.tb, ((size_t)NC + 1) * 4));
+    TRY(sc.alloc((void**)&d.terms, (size_t)NT * sizeof(lig_lin_term)));
+    TRY(sc.alloc((void**)&d_rhs_c, (size_t)NR * 4));
+    TRY(sc.alloc((void**)&d.rhs_coef, (size_t)NR * 4));
+    TRY(sc.alloc((void**)&d.rhs_index, (size_t)NC * 4));
+    TRY(sc.alloc((void**)&d.heavy_dev, d.heavy.size() * 4));
+    TRY(sc.alloc((void**)&d.coef, (size_t)sys->n_coefs * 32));
+    HIP_TRY(c, hipMemcpyAsync(d.tb, sys->term_begin, ((size_t)NC + 1) * 4, hipMemcpyHostToDevice, s));
+    if (NT) HIP_TRY(c, hipMemcpyAsync(d.terms, sys->terms, (size_t)NT * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
+    if (NR) {
+        HIP_TRY(c, hipMemcpyAsync(d_rhs_c, sys->rhs_constraint, (size_t)NR * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d.rhs_coef, sys->rhs_coef, (size_t)NR * 4, hipMemcpyHostToDevice, s));
+    }
+    if (!d.heavy.empty()) HIP_TRY(c, hipMemcpyAsync(d.heavy_dev, d.heavy.data(), d.heavy.size() * 4, hipMemcpyHostToDevice, s));
+    if (sys->n_coefs) HIP_TRY(c, hipMemcpyAsync(d.coef, sys->coefs, (size_t)sys->n_coefs * 32, hipMemcpyHostToDevice, s));
+    lig::launch_lin_coefs_mont(s, d.coef, sys->n_coefs);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemsetAsync(d.rhs_index, 0, (size_t)NC * 4, s));
+    if (NR) {
+        hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, d_rhs_c, NR, d.rhs_index);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return LIG_OK;
+}
+
+// The quadratic terms tri_dev[0 .. n_terms) over `msgs`, in slices of at most DIAG_QUAD_ITEMS items; the running count and the output offset
+// are carried on the host.  The first `cap` records go to host_out slice by slice (one GPU), or -- host_out == NULL -- stay on the device in
+// dev_out[0 .. cap) with the terms' ordinals in ord_out (a rank of a shard: rows through grow_dev, ordinals from ord_dev).
+int diag_quad_pass(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, void** scan_tmp, size_t* scan_cap, const fr* msgs, const uint32_t* tri_dev, uint64_t n_terms,
+                   uint64_t cap, lig_diag_quad* host_out, lig_diag_quad* dev_out, const uint32_t* grow_dev, const uint32_t* ord_dev, uint32_t* ord_out,
+                   uint64_t* bad_total_out, uint64_t* reported_out) {
+    hipStream_t s = c->stream;
+    const uint32_t l = c->l, k = c->k;
+    const uint64_t l_recip = diag_reciprocal(l);
+    const uint64_t per = std::max<uint64_t>(lig::DIAG_QUAD_ITEMS / l, 1);        // terms per slice: per * l < 2^32 (l < 2^32, and per = 1 beyond the budget)
+    const uint64_t slice_items = std::min(per, n_terms) * l;
+    uint32_t *d_flag = nullptr, *d_pos = nullptr; fr* d_res = nullptr;
+    TRY(sc.alloc((void**)&d_res, (size_t)slice_items * 32));
+    TRY(sc.alloc((void**)&d_flag, ((size_t)slice_items + 1) * 4));
+    TRY(sc.alloc((void**)&d_pos, ((size_t)slice_items + 1) * 4));
+    if (host_out || !dev_out) {
+        const uint64_t out_cap = std::min<uint64_t>(cap, slice_items);
+        if (out_cap) TRY(sc.alloc((void**)&dev_out, (size_t)out_cap * sizeof(lig_diag_quad)));
+    }
+    uint64_t bad_total = 0, reported = 0;
+    for (uint64_t t0 = 0; t0 < n_terms; t0 += per) {
+        const uint32_t items = (uint32_t)(std::min(per, n_terms - t0) * l);
+        HIP_TRY(c, hipMemsetAsync(d_flag + items, 0, 4, s));
+        hipLaunchKernelGGL(lig::k_diag_quad, dim3(diag_grid(items)), dim3(lig::LIN_WG), 0, s, tri_dev, (uint32_t)t0, items, msgs, l, k, l_recip, d_res, d_flag);
+        HIP_TRY(c, hipGetLastError());
+        uint32_t bad = 0;
+        TRY(diag_scan(c, sc, wait, d_flag, d_pos, items, scan_tmp, scan_cap, &bad));
+        if (bad > items) FAIL(c, LIG_E_STATE, "lig_rows_diagnose: counted more violated items than the slice holds");
+        bad_total += bad;
+        const uint32_t rep = (uint32_t)std::min<uint64_t>(bad, cap - reported);
+        if (rep) {
+            const uint64_t at = host_out ? 0 : reported;
+            hipLaunchKernelGGL(lig::k_diag_scatter_quad, dim3(diag_grid(items)), dim3(lig::LIN_WG), 0, s, d_flag, d_pos, d_res, tri_dev, (uint32_t)t0, items, l, l_recip,
+                               rep, dev_out + at, grow_dev, ord_dev, ord_out ? ord_out + at : nullptr);
+            HIP_TRY(c, hipGetLastError());
+            if (host_out) {
+                HIP_TRY(c, hipMemcpyAsync(host_out + reported, dev_out, (size_t)rep * sizeof(lig_diag_quad), hipMemcpyDeviceToHost, s));
+                TRY(wait());
+            }
+            reported += rep;
+        }
+    }
+    *bad_total_out = bad_total;
+    *reported_out = reported;
     return LIG_OK;
 }
 }  // namespace
@@ -176,96 +327,228 @@ int lig_internal_rows_diagnose(lig_ctx* c, const fr* msgs, uint64_t rows, const 
     const uint64_t l_recip = diag_reciprocal(l);
     DiagScratch sc(c);
     void* scan_tmp = nullptr; size_t scan_cap = 0;
+    const DiagWait wait = [c, s]() -> int { HIP_TRY(c, lig_internal_wait_stream(s)); return LIG_OK; };
 
     // ---------------------------------------------------------------- linear constraints
     if (sys && sys->n_constraints) {
-        const uint32_t NC = (uint32_t)sys->n_constraints, NT = (uint32_t)sys->n_terms, NR = (uint32_t)sys->n_rhs;
-        std::vector<uint32_t> heavy;                                      // constraints with more than HEAVY_MIN terms, ascending
-        for (uint32_t cn = 0; cn < NC; cn++) if (sys->term_begin[cn + 1] - sys->term_begin[cn] > lig::HEAVY_MIN) heavy.push_back(cn);
-        uint32_t *d_tb = nullptr, *d_rhs_c = nullptr, *d_rhs_coef = nullptr, *d_rhs_index = nullptr, *d_heavy = nullptr, *d_flag = nullptr, *d_pos = nullptr;
-        lig_lin_term* d_terms = nullptr; fr *d_coef = nullptr, *d_res = nullptr;
-        TRY(sc.alloc((void**)&d_tb, ((size_t)NC + 1) * 4));
-        TRY(sc.alloc((void**)&d_terms, (size_t)NT * sizeof(lig_lin_term)));
-        TRY(sc.alloc((void**)&d_rhs_c, (size_t)NR * 4));
-        TRY(sc.alloc((void**)&d_rhs_coef, (size_t)NR * 4));
-        TRY(sc.alloc((void**)&d_rhs_index, (size_t)NC * 4));
-        TRY(sc.alloc((void**)&d_heavy, heavy.size() * 4));
-        TRY(sc.alloc((void**)&d_coef, (size_t)sys->n_coefs * 32));
+        DiagSystem d;
+        TRY(diag_upload_system(c, sc, sys, d));
+        const uint32_t NC = d.NC;
+        uint32_t *d_flag = nullptr, *d_pos = nullptr; fr* d_res = nullptr;
         TRY(sc.alloc((void**)&d_res, (size_t)NC * 32));
         TRY(sc.alloc((void**)&d_flag, ((size_t)NC + 1) * 4));
         TRY(sc.alloc((void**)&d_pos, ((size_t)NC + 1) * 4));
-        HIP_TRY(c, hipMemcpyAsync(d_tb, sys->term_begin, ((size_t)NC + 1) * 4, hipMemcpyHostToDevice, s));
-        if (NT) HIP_TRY(c, hipMemcpyAsync(d_terms, sys->terms, (size_t)NT * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
-        if (NR) {
-            HIP_TRY(c, hipMemcpyAsync(d_rhs_c, sys->rhs_constraint, (size_t)NR * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(d_rhs_coef, sys->rhs_coef, (size_t)NR * 4, hipMemcpyHostToDevice, s));
-        }
-        if (!heavy.empty()) HIP_TRY(c, hipMemcpyAsync(d_heavy, heavy.data(), heavy.size() * 4, hipMemcpyHostToDevice, s));
-        // a scratch copy of the caller's table in Montgomery form: the table of an attached program is neither read nor written
-        if (sys->n_coefs) HIP_TRY(c, hipMemcpyAsync(d_coef, sys->coefs, (size_t)sys->n_coefs * 32, hipMemcpyHostToDevice, s));
-        lig::launch_lin_coefs_mont(s, d_coef, sys->n_coefs);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemsetAsync(d_rhs_index, 0, (size_t)NC * 4, s));
         HIP_TRY(c, hipMemsetAsync(d_flag, 0, ((size_t)NC + 1) * 4, s));
-        if (NR) {
-            hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, d_rhs_c, NR, d_rhs_index);
-            HIP_TRY(c, hipGetLastError());
-        }
-        hipLaunchKernelGGL(lig::k_diag_lin, dim3(diag_grid(NC)), dim3(lig::LIN_WG), 0, s, d_tb, d_terms, NC, msgs, l, k, l_recip, d_coef, d_rhs_index, d_rhs_coef, d_res, d_flag);
+        hipLaunchKernelGGL(lig::k_diag_lin, dim3(diag_grid(NC)), dim3(lig::LIN_WG), 0, s, d.tb, d.terms, NC, msgs, l, k, l_recip, d.coef, d.rhs_index, d.rhs_coef, d_res, d_flag);
         HIP_TRY(c, hipGetLastError());
-        if (!heavy.empty()) {
-            hipLaunchKernelGGL(lig::k_diag_lin_heavy, dim3(std::min<uint32_t>((uint32_t)heavy.size(), lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d_heavy,
-                               (uint32_t)heavy.size(), d_tb, d_terms, msgs, l, k, l_recip, d_coef, d_rhs_index, d_rhs_coef, d_res, d_flag);
+        if (!d.heavy.empty()) {
+            hipLaunchKernelGGL(lig::k_diag_lin_heavy, dim3(std::min<uint32_t>((uint32_t)d.heavy.size(), lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d.heavy_dev,
+                               (uint32_t)d.heavy.size(), d.tb, d.terms, msgs, l, k, l_recip, d.coef, d.rhs_index, d.rhs_coef, d_res, d_flag);
             HIP_TRY(c, hipGetLastError());
         }
         uint32_t bad = 0;
-        TRY(diag_scan(c, sc, d_flag, d_pos, NC, &scan_tmp, &scan_cap, &bad));
+        TRY(diag_scan(c, sc, wait, d_flag, d_pos, NC, &scan_tmp, &scan_cap, &bad));
         if (bad > NC) FAIL(c, LIG_E_STATE, "lig_rows_diagnose: counted more violated constraints than the system holds");
         info->n_linear_bad = bad;
         const uint32_t rep = (uint32_t)std::min<uint64_t>(bad, lin_cap);
         if (rep) {
             lig_diag_linear* d_out = nullptr;
             TRY(sc.alloc((void**)&d_out, (size_t)rep * sizeof(lig_diag_linear)));
-            hipLaunchKernelGGL(lig::k_diag_scatter_lin, dim3(diag_grid(NC)), dim3(lig::LIN_WG), 0, s, d_flag, d_pos, d_res, NC, rep, d_out);
+            hipLaunchKernelGGL(lig::k_diag_scatter_lin, dim3(diag_grid(NC)), dim3(lig::LIN_WG), 0, s, d_flag, d_pos, d_res, NC, 0u, rep, d_out);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipMemcpyAsync(lin_out, d_out, (size_t)rep * sizeof(lig_diag_linear), hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, lig_internal_wait_stream(s));
+            TRY(wait());
         }
         info->n_linear_reported = rep;
     }
 
-    // ---------------------------------------------------------------- quadratic terms, in slices of at most DIAG_QUAD_ITEMS items
-    if (n_quad_terms && rows) {
-        const uint64_t per = std::max<uint64_t>(lig::DIAG_QUAD_ITEMS / l, 1);        // terms per slice: per * l < 2^32 (l < 2^32, and per = 1 beyond the budget)
-        const uint64_t slice_items = std::min(per, n_quad_terms) * l;
-        uint32_t *d_flag = nullptr, *d_pos = nullptr; fr* d_res = nullptr; lig_diag_quad* d_out = nullptr;
-        TRY(sc.alloc((void**)&d_res, (size_t)slice_items * 32));
-        TRY(sc.alloc((void**)&d_flag, ((size_t)slice_items + 1) * 4));
-        TRY(sc.alloc((void**)&d_pos, ((size_t)slice_items + 1) * 4));
-        const uint64_t out_cap = std::min<uint64_t>(quad_cap, slice_items);
-        if (out_cap) TRY(sc.alloc((void**)&d_out, (size_t)out_cap * sizeof(lig_diag_quad)));
-        uint64_t bad_total = 0, reported = 0;
-        for (uint64_t t0 = 0; t0 < n_quad_terms; t0 += per) {
-            const uint32_t items = (uint32_t)(std::min(per, n_quad_terms - t0) * l);
-            HIP_TRY(c, hipMemsetAsync(d_flag + items, 0, 4, s));
-            hipLaunchKernelGGL(lig::k_diag_quad, dim3(diag_grid(items)), dim3(lig::LIN_WG), 0, s, tri_dev, (uint32_t)t0, items, msgs, l, k, l_recip, d_res, d_flag);
-            HIP_TRY(c, hipGetLastError());
-            uint32_t bad = 0;
-            TRY(diag_scan(c, sc, d_flag, d_pos, items, &scan_tmp, &scan_cap, &bad));
-            if (bad > items) FAIL(c, LIG_E_STATE, "lig_rows_diagnose: counted more violated items than the slice holds");
-            bad_total += bad;
-            const uint32_t rep = (uint32_t)std::min<uint64_t>(bad, quad_cap - reported);
-            if (rep) {
-                hipLaunchKernelGGL(lig::k_diag_scatter_quad, dim3(diag_grid(items)), dim3(lig::LIN_WG), 0, s, d_flag, d_pos, d_res, tri_dev, (uint32_t)t0, items, l, l_recip,
-                                   rep, d_out);
-                HIP_TRY(c, hipGetLastError());
-                HIP_TRY(c, hipMemcpyAsync(quad_out + reported, d_out, (size_t)rep * sizeof(lig_diag_quad), hipMemcpyDeviceToHost, s));
-                HIP_TRY(c, lig_internal_wait_stream(s));
-                reported += rep;
-            }
-        }
-        info->n_quad_bad = bad_total;
-        info->n_quad_reported = reported;
-    }
+    // ---------------------------------------------------------------- quadratic terms
+    if (n_quad_terms && rows)
+        TRY(diag_quad_pass(c, sc, wait, &scan_tmp, &scan_cap, msgs, tri_dev, n_quad_terms, quad_cap, quad_out, nullptr, nullptr, nullptr, nullptr, &info->n_quad_bad,
+                           &info->n_quad_reported));
     return LIG_OK;
+}
+
+// One rank of a sharded rows job (lig_shard_rows_diagnose, lig_hip.h; v: prover_common.hpp).  Collective: whether a collective is issued,
+// how many and of which size depends on sys' sizes, the caps, the world size and the slice knob alone -- never on what this rank holds.
+//   linear     constraints in slices of W * B; sub-block h of a slice (B contiguous constraints) is owned by rank h.  Per slice: partials of
+//              the whole slice (k_diag_lin_part*), ONE all-to-all of B x 32 bytes per pair, k_diag_reduce on the owner's sub-block, scan,
+//              scatter behind the owner's earlier records (at most lin_cap of them are kept).  Then one all-gather of
+//              [count, kept | lin_cap' records] and a merge into ascending constraint order on the host of every rank.
+//   quadratic  every term is local to one rank: the one-GPU pass over the local terms, global rows through `grow`, at most quad_cap records
+//              kept with the terms' global ordinals; one all-gather of [count, kept | records | ordinals], merged by (ordinal, column).
+// Every send buffer is an allocation of its own; v.forget runs before any of them is freed.
+int lig_internal_shard_diagnose(lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out,
+                                uint64_t quad_cap, lig_diag_info* info) {
+    hipStream_t s = c->stream;
+    const uint32_t l = c->l, k = c->k, W = v.world;
+    const uint64_t l_recip = diag_reciprocal(l);
+    DiagScratch sc(c);
+    void* scan_tmp = nullptr; size_t scan_cap = 0;
+    bool used_comm = false;
+    const DiagWait wait = [&v]() -> int { return v.drain("lig_shard_rows_diagnose"); };
+    // LIG_TRACE: a synchronised split of the call into its phases on stderr
+    const bool trace_on = lig::knobs().trace;
+    enum { PH_PARTIAL, PH_EXCHANGE, PH_REDUCE, PH_RECORDS, PH_QUAD, PH_N };
+    double ph[PH_N] = {0, 0, 0, 0, 0};
+    auto t_mark = clk::now();
+    auto mark = [&](int p) -> int {
+        if (!trace_on) return LIG_OK;
+        TRY(wait());
+        ph[p] += ms_since(t_mark);
+        t_mark = clk::now();
+        return LIG_OK;
+    };
+    std::vector<uint32_t> local_of, grow32, ord32;      // (sources of queued uploads: they live until the call returns)
+    std::vector<uint8_t> gathered;
+    uint64_t header[2] = {0, 0}, qheader[2] = {0, 0};
+
+    auto body = [&]() -> int {
+        // ---------------------------------------------------------------- linear constraints
+        if (sys && sys->n_constraints) {
+            DiagSystem d;
+            TRY(diag_upload_system(c, sc, sys, d));
+            const uint32_t NC = d.NC;
+            local_of.assign(v.rows_global, lig::LIN_NOT_LOCAL);
+            for (size_t lr = 0; lr < v.grow->size(); lr++) local_of[(*v.grow)[lr]] = (uint32_t)lr;
+            uint32_t* d_local = nullptr;
+            TRY(sc.alloc((void**)&d_local, local_of.size() * 4));
+            if (!local_of.empty()) HIP_TRY(c, hipMemcpyAsync(d_local, local_of.data(), local_of.size() * 4, hipMemcpyHostToDevice, s));
+            const uint64_t SL = std::max<uint64_t>(v.slice, 1);
+            const uint32_t B = (uint32_t)(NC <= SL ? ((uint64_t)NC + W - 1) / W : std::max<uint64_t>(SL / W, 1));      // constraints per sub-block
+            const uint64_t SE = (uint64_t)B * W, n_slices = (NC + SE - 1) / SE;                                         // constraints per slice, slices
+            const uint64_t rec_cap = std::min<uint64_t>(lin_cap, n_slices * B);                                          // no owner has more to report
+            const size_t blk = 16 + (size_t)rec_cap * sizeof(lig_diag_linear);
+            fr *d_send = nullptr, *d_recv = nullptr, *d_res = nullptr; uint32_t *d_flag = nullptr, *d_pos = nullptr; uint8_t *d_gsend = nullptr, *d_grecv = nullptr;
+            TRY(sc.alloc((void**)&d_send, (size_t)SE * 32));
+            TRY(sc.alloc((void**)&d_recv, (size_t)SE * 32));
+            TRY(sc.alloc((void**)&d_res, (size_t)B * 32));
+            TRY(sc.alloc((void**)&d_flag, ((size_t)B + 1) * 4));
+            TRY(sc.alloc((void**)&d_pos, ((size_t)B + 1) * 4));
+            TRY(sc.alloc((void**)&d_gsend, blk));
+            TRY(sc.alloc((void**)&d_grecv, (size_t)W * blk));
+            HIP_TRY(c, hipMemsetAsync(d_flag, 0, ((size_t)B + 1) * 4, s));
+            lig_diag_linear* d_rec = reinterpret_cast<lig_diag_linear*>(d_gsend + 16);
+            uint64_t bad_mine = 0, rep_mine = 0;
+            TRY(mark(PH_RECORDS));      // (uploads, table conversion)
+            for (uint64_t j = 0; j < n_slices; j++) {
+                const uint32_t c0 = (uint32_t)(j * SE), n = (uint32_t)std::min<uint64_t>(SE, NC - c0);
+                if (n < SE) HIP_TRY(c, hipMemsetAsync(d_send + n, 0, (size_t)(SE - n) * 32, s));       // beyond the end of the system: zero partials
+                hipLaunchKernelGGL(lig::k_diag_lin_part, dim3(diag_grid(n)), dim3(lig::LIN_WG), 0, s, d.tb, d.terms, c0, n, v.msgs, l, k, l_recip, d.coef, d_local, d_send);
+                HIP_TRY(c, hipGetLastError());
+                const size_t h0 = std::lower_bound(d.heavy.begin(), d.heavy.end(), c0) - d.heavy.begin();
+                const size_t h1 = std::lower_bound(d.heavy.begin(), d.heavy.end(), c0 + n) - d.heavy.begin();
+                if (h1 > h0) {
+                    hipLaunchKernelGGL(lig::k_diag_lin_part_heavy, dim3(std::min<uint32_t>((uint32_t)(h1 - h0), lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d.heavy_dev + h0,
+                                       (uint32_t)(h1 - h0), d.tb, d.terms, c0, v.msgs, l, k, l_recip, d.coef, d_local, d_send);
+                    HIP_TRY(c, hipGetLastError());
+                }
+                TRY(mark(PH_PARTIAL));
+                used_comm = true;
+                TRY(v.all_to_all(d_send, d_recv, (size_t)B * 32, "all_to_all(partial constraint sums)"));
+                TRY(mark(PH_EXCHANGE));
+                const uint64_t first = (uint64_t)c0 + (uint64_t)v.rank * B;                             // my sub-block of this slice
+                const uint32_t n_valid = first < NC ? (uint32_t)std::min<uint64_t>(B, NC - first) : 0u;
+                hipLaunchKernelGGL(lig::k_diag_reduce, dim3(diag_grid(B)), dim3(lig::LIN_WG), 0, s, d_recv, W, B, n_valid, (uint32_t)std::min<uint64_t>(first, NC), d.rhs_index,
+                                   d.rhs_coef, d.coef, d_res, d_flag);
+                HIP_TRY(c, hipGetLastError());
+                TRY(mark(PH_REDUCE));
+                uint32_t bad = 0;
+                TRY(diag_scan(c, sc, wait, d_flag, d_pos, B, &scan_tmp, &scan_cap, &bad));
+                if (bad > n_valid) FAIL(c, LIG_E_STATE, "lig_shard_rows_diagnose: counted more violated constraints than the sub-block holds");
+                bad_mine += bad;
+                const uint32_t rep = (uint32_t)std::min<uint64_t>(bad, rec_cap - rep_mine);
+                if (rep) {
+                    hipLaunchKernelGGL(lig::k_diag_scatter_lin, dim3(diag_grid(B)), dim3(lig::LIN_WG), 0, s, d_flag, d_pos, d_res, B, (uint32_t)first, rep, d_rec + rep_mine);
+                    HIP_TRY(c, hipGetLastError());
+                    rep_mine += rep;
+                }
+                TRY(mark(PH_RECORDS));
+            }
+            header[0] = bad_mine; header[1] = rep_mine;
+            HIP_TRY(c, hipMemcpyAsync(d_gsend, header, 16, hipMemcpyHostToDevice, s));
+            TRY(v.all_gather(d_gsend, d_grecv, blk, "all_gather(violated constraints)"));
+            gathered.resize((size_t)W * blk);
+            HIP_TRY(c, hipMemcpyAsync(gathered.data(), d_grecv, gathered.size(), hipMemcpyDeviceToHost, s));
+            TRY(wait());
+            // every rank: W ascending lists -> ascending constraint order, cut at lin_cap
+            std::vector<lig_diag_linear> all;
+            uint64_t bad_total = 0;
+            for (uint32_t g = 0; g < W; g++) {
+                uint64_t hd[2];
+                std::memcpy(hd, gathered.data() + (size_t)g * blk, 16);
+                if (hd[1] > rec_cap || hd[1] > hd[0] || hd[0] > n_slices * B) FAIL(c, LIG_E_STATE, "lig_shard_rows_diagnose: a rank's record block is malformed");
+                bad_total += hd[0];
+                const size_t at = all.size();
+                all.resize(at + hd[1]);
+                if (hd[1]) std::memcpy(all.data() + at, gathered.data() + (size_t)g * blk + 16, hd[1] * sizeof(lig_diag_linear));
+            }
+            std::stable_sort(all.begin(), all.end(), [](const lig_diag_linear& a, const lig_diag_linear& b) { return a.constraint < b.constraint; });
+            const uint64_t rep = std::min<uint64_t>(all.size(), lin_cap);
+            if (rep) std::memcpy(lin_out, all.data(), rep * sizeof(lig_diag_linear));
+            info->n_linear_bad = bad_total;
+            info->n_linear_reported = rep;
+            TRY(mark(PH_RECORDS));
+        }
+
+        // ---------------------------------------------------------------- quadratic terms: every term is local to one rank
+        if (v.n_terms_global) {
+            const uint64_t NTl = v.triple_ord->size();
+            const uint64_t rec_cap = std::min<uint64_t>(quad_cap, v.n_terms_global * l);
+            const size_t blk = 16 + (size_t)rec_cap * (sizeof(lig_diag_quad) + 4);                     // [count, kept | records | ordinals]
+            uint8_t *d_gsend = nullptr, *d_grecv = nullptr; uint32_t *d_grow = nullptr, *d_ord = nullptr;
+            TRY(sc.alloc((void**)&d_gsend, blk));
+            TRY(sc.alloc((void**)&d_grecv, (size_t)W * blk));
+            lig_diag_quad* d_rec = reinterpret_cast<lig_diag_quad*>(d_gsend + 16);
+            uint32_t* d_rec_ord = reinterpret_cast<uint32_t*>(d_gsend + 16 + (size_t)rec_cap * sizeof(lig_diag_quad));
+            uint64_t bad_mine = 0, rep_mine = 0;
+            if (NTl) {
+                grow32.assign(v.grow->begin(), v.grow->end());
+                ord32.assign(v.triple_ord->begin(), v.triple_ord->end());
+                TRY(sc.alloc((void**)&d_grow, grow32.size() * 4));
+                TRY(sc.alloc((void**)&d_ord, ord32.size() * 4));
+                HIP_TRY(c, hipMemcpyAsync(d_grow, grow32.data(), grow32.size() * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(c, hipMemcpyAsync(d_ord, ord32.data(), ord32.size() * 4, hipMemcpyHostToDevice, s));
+                TRY(diag_quad_pass(c, sc, wait, &scan_tmp, &scan_cap, v.msgs, v.tri_dev, NTl, rec_cap, nullptr, d_rec, d_grow, d_ord, d_rec_ord, &bad_mine, &rep_mine));
+            }
+            qheader[0] = bad_mine; qheader[1] = rep_mine;
+            HIP_TRY(c, hipMemcpyAsync(d_gsend, qheader, 16, hipMemcpyHostToDevice, s));
+            used_comm = true;
+            TRY(v.all_gather(d_gsend, d_grecv, blk, "all_gather(violated quadratic terms)"));
+            gathered.resize((size_t)W * blk);
+            HIP_TRY(c, hipMemcpyAsync(gathered.data(), d_grecv, gathered.size(), hipMemcpyDeviceToHost, s));
+            TRY(wait());
+            struct Item { uint32_t ord; lig_diag_quad rec; };
+            std::vector<Item> all;
+            uint64_t bad_total = 0;
+            for (uint32_t g = 0; g < W; g++) {
+                const uint8_t* b = gathered.data() + (size_t)g * blk;
+                uint64_t hd[2];
+                std::memcpy(hd, b, 16);
+                if (hd[1] > rec_cap || hd[1] > hd[0] || hd[0] > v.n_terms_global * l) FAIL(c, LIG_E_STATE, "lig_shard_rows_diagnose: a rank's record block is malformed");
+                bad_total += hd[0];
+                for (uint64_t i = 0; i < hd[1]; i++) {
+                    Item it;
+                    std::memcpy(&it.rec, b + 16 + i * sizeof(lig_diag_quad), sizeof(lig_diag_quad));
+                    std::memcpy(&it.ord, b + 16 + (size_t)rec_cap * sizeof(lig_diag_quad) + i * 4, 4);
+                    all.push_back(it);
+                }
+            }
+            std::stable_sort(all.begin(), all.end(), [](const Item& a, const Item& b) { return a.ord != b.ord ? a.ord < b.ord : a.rec.column < b.rec.column; });
+            const uint64_t rep = std::min<uint64_t>(all.size(), quad_cap);
+            for (uint64_t i = 0; i < rep; i++) quad_out[i] = all[i].rec;
+            info->n_quad_bad = bad_total;
+            info->n_quad_reported = rep;
+            TRY(mark(PH_QUAD));
+        }
+        return LIG_OK;
+    };
+    const int rc = body();
+    if (rc != LIG_OK && v.settle_failed()) { sc.abandon(); return rc; }      // poisoned: the scratch outlives the call
+    if (rc == LIG_OK) (void)wait();
+    if (used_comm) v.forget();                                                // before any send buffer is freed (lig_comm.forget)
+    if (trace_on && rc == LIG_OK)
+        std::fprintf(stderr, "[lig_trace] shard_diagnose rank %u: partial %.3f exchange %.3f reduce %.3f records %.3f quadratic %.3f ms\n", v.rank, ph[PH_PARTIAL],
+                     ph[PH_EXCHANGE], ph[PH_REDUCE], ph[PH_RECORDS], ph[PH_QUAD]);
+    return rc;
 }

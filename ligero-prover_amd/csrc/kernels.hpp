@@ -41,6 +41,7 @@ struct Knobs {
     int      spin_wait_ms = 50;        // LIG_SPIN_WAIT_MS   polling gives way to the blocking wait after this long
     bool     d2h_kernel = true;        // LIG_D2H_KERNEL=0   proof downloads by hipMemcpyAsync instead of copy kernels
     bool     shard_force_exchange = false;   // LIG_SHARD_FORCE_EXCHANGE  pack + all-to-all with one rank too (tests)
+    uint64_t diag_slice = 1ull << 22;  // LIG_DIAG_SLICE     lig_shard_rows_diagnose: linear constraints per slice of the cross-rank reduction (scratch: 64 B per constraint of a slice)
     bool     zres = false;             // LIG_ZRES=1         stage 1 keeps the encoder's Z tiles instead of codeword planes: K3 inside the column hash (round 6 A/B)
     bool     trace = false;            // LIG_TRACE          synchronised phase timeline on stderr
     int      fault_comm = 0;           // LIG_FAULT_COMM     tests: 1 = the stream-ordered all-to-all of the library's communicators

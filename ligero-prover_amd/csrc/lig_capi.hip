@@ -335,6 +335,7 @@ const lig::Knobs& lig::knobs() {
         t.spin_wait_ms = (int)pos("LIG_SPIN_WAIT_MS", 50);
         t.shard_force_exchange = std::getenv("LIG_SHARD_FORCE_EXCHANGE") != nullptr;
         t.trace = std::getenv("LIG_TRACE") != nullptr;
+        t.diag_slice = (uint64_t)pos("LIG_DIAG_SLICE", 1l << 22);
         t.zres = num("LIG_ZRES", 0) != 0;
         t.fault_comm = (int)num("LIG_FAULT_COMM", 0);
         t.ipc_stall_s = (int)pos("LIG_IPC_STALL_S", 120);

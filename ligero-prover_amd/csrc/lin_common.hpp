@@ -7,6 +7,7 @@ namespace lig {
 static constexpr uint32_t LIN_WG = 256;
 static constexpr uint32_t HEAVY_MIN = 2048;       // a segment (the terms of one slot / of one constraint) with more terms than this is summed by whole workgroups
 static constexpr uint32_t COEFS_MAX_BLOCKS = 1024;      // block cap of the grid-stride passes over a table or over constraints
+static constexpr uint32_t LIN_NOT_LOCAL = 0xFFFFFFFFu;  // entry of a rank's global -> local row table: another rank holds that row
 
 // sum of the workgroup's LIN_WG values (fixed tree: the same bytes on every run); valid in thread 0
 static __device__ __forceinline__ fr lin_block_sum(fr v, fr* sh) {

@@ -76,7 +76,6 @@ __global__ void __launch_bounds__(LIN_WG) k_lin_classify(const uint32_t* __restr
 // for the rows of other ranks), renumbered to local slots, and samples only the constraints it NEEDS: those with a kept term and those
 // of its slice of the right-hand sides.  flag[c] = 1 marks them (plain stores of the same value from any number of lanes), an exclusive
 // scan of the flags numbers them in ascending order, and the per-slot entries carry those compact numbers: r is need-list long.
-static constexpr uint32_t LIN_NOT_LOCAL = 0xFFFFFFFFu;
 static __device__ __forceinline__ uint32_t lin_local_slot(uint32_t slot, uint32_t l, const uint32_t* __restrict__ local_of) {
     const uint32_t row = slot / l, lr = local_of[row];
     return lr == LIN_NOT_LOCAL ? LIN_NOT_LOCAL : lr * l + (slot - row * l);

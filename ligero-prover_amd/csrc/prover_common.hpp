@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <utility>
@@ -458,6 +459,26 @@ uint8_t* lig_internal_linear_const_buf(lig_linear* L);
 int lig_internal_rows_diagnose(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* tri_dev, uint64_t n_quad_terms, const lig_linear_system* sys,
                                lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info);
 hipError_t lig_internal_wait_stream(hipStream_t st);
+// lig_shard_rows_diagnose (diagnose.hip): what one rank of a sharded rows job holds, and the shard's collectives and waits (shard.hip).
+// all_to_all / all_gather run on the context's main stream (stream-ordered forms) or after it has drained (host-synchronous callbacks);
+// drain = the bounded wait of every lig_shard_* call; settle_failed = after a failure: drain within bounds, true when the shard is
+// poisoned (the scratch of the call then outlives it); forget = lig_comm.forget.
+struct lig_diag_shard {
+    const fr* msgs = nullptr;                          // the committed LOCAL rows x k
+    const std::vector<size_t>* grow = nullptr;         // global row of every local row
+    uint64_t rows_global = 0;
+    const uint32_t* tri_dev = nullptr;                 // local quadratic terms, local row indices
+    const std::vector<size_t>* triple_ord = nullptr;   // their global ordinals
+    uint64_t n_terms_global = 0;
+    uint32_t rank = 0, world = 1;
+    uint64_t slice = 0;                                // LIG_DIAG_SLICE
+    std::function<int(const void*, void*, size_t, const char*)> all_to_all, all_gather;
+    std::function<int(const char*)> drain;
+    std::function<bool()> settle_failed;
+    std::function<void()> forget;
+};
+int lig_internal_shard_diagnose(lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out,
+                                uint64_t quad_cap, lig_diag_info* info);
 
 // the batch program of a job on the device: committed rows are written to rows_out in program order (prover.hip)
 int lig_run_batch_program(lig_ctx* c, const lig_synth_job& job, fr* rows_out);

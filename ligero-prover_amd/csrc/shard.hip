@@ -40,6 +40,7 @@ struct lig_shard {
     std::vector<uint64_t> enc_pos;             // encoding-stream position of every global row's pads (+1 entry = the masks' position)
     bool from_rows = false;                    // lig_shard_rows_*: the local rows and their randomness rows come from the caller
     bool dense_rands = false, committed = false;
+    bool diag_ok = false;                      // `msgs` holds a committed trace (lig_shard_rows_diagnose): from lig_shard_rows_commit until the next load
     lig_proof_info info1;                      // stage-1 results kept between lig_shard_rows_commit and lig_shard_rows_prove
     JobHeader hdr;
     size_t RB = 0, n_init = 0;                 // leading rows committed by the batch program, of those: init rows
@@ -769,6 +770,7 @@ static int shard_rows_load(lig_shard* S, const void* local_msgs, bool on_device)
     S->up.drain();                                     // an upload nobody committed
     HIP_TRY(c, hipStreamSynchronize(c->stream));      // the previous trace is done with S->msgs
     S->committed = false;
+    S->diag_ok = false;
     S->rows_by_thread = false;
     if (!S->Rl) return LIG_OK;
     const size_t row_bytes = (size_t)c->k * 32;
@@ -878,6 +880,7 @@ int lig_shard_rows_commit(lig_shard* S, uint8_t root[32], uint8_t stage1_seed[32
     }
     S->info1.ms_stage1 = ms_since(t_begin);
     S->committed = true;
+    S->diag_ok = true;
     if (root) std::memcpy(root, S->info1.root, 32);
     if (stage1_seed) std::memcpy(stage1_seed, S->info1.stage1_seed, 32);
     return LIG_OK;
@@ -915,6 +918,50 @@ int lig_shard_rows_prove(lig_shard* S, const void* local_rands, int rands_on_dev
     }
     info->ms_total = info->ms_stage1 + ms_since(t_begin);
     S->committed = false;
+    return LIG_OK;
+}
+
+// Which constraints does the committed witness violate, on a rows shard (diagnose.hip): collective, every rank obtains the bytes of
+// lig_rows_diagnose on the whole trace.  Everything that can be refused is refused here, on the host, identically on every rank, before
+// anything is launched and before any collective.
+int lig_shard_rows_diagnose(lig_shard* S, const lig_linear_system* sys, lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap,
+                            lig_diag_info* info) {
+    if (!S || !info || info->struct_bytes < sizeof(lig_diag_info)) return LIG_E_ARG;
+    if ((lin_cap && !lin_out) || (quad_cap && !quad_out)) return LIG_E_ARG;
+    const auto t_begin = clk::now();
+    SHARD_COMMON;
+    (void)n;
+    CHECK_CTX(c);
+    if (S->poisoned) FAIL(c, LIG_E_STATE, "lig_shard_rows_diagnose: the shard is poisoned (work queued behind a failed collective never drained): destroy it");
+    if (!S->from_rows) FAIL(c, LIG_E_STATE, "lig_shard_rows_diagnose: not a rows shard (lig_shard_rows_begin)");
+    if (!S->diag_ok) FAIL(c, LIG_E_STATE, "lig_shard_rows_diagnose: no committed matrix (between lig_shard_rows_commit and the next lig_shard_rows_restart)");
+    if (sys && lig_linear_check(sys, kinds_of(S->rows).data(), R, l) != LIG_OK) FAIL(c, LIG_E_ARG, "lig_shard_rows_diagnose: linear system rejected by lig_linear_check");
+    const uint32_t struct_bytes = info->struct_bytes;
+    std::memset(info, 0, sizeof *info);
+    info->struct_bytes = struct_bytes;
+    ShardDebugScope dbg(S, "diagnose", nullptr);
+    if (W == 1 && !S->exchange_even_alone) {       // one rank holds every row in commit order: the one-GPU pass, no collective
+        TRY(lig_internal_rows_diagnose(c, S->msgs, R, S->tri_dev, S->triple_ord.size(), sys, lin_out, lin_cap, quad_out, quad_cap, info));
+        info->ms_total = ms_since(t_begin);
+        return LIG_OK;
+    }
+    lig_diag_shard v;
+    v.msgs = S->msgs; v.grow = &S->grow; v.rows_global = R; v.tri_dev = S->tri_dev; v.triple_ord = &S->triple_ord;
+    v.n_terms_global = quad_terms(S->rows).size() / 3;
+    v.rank = S->rank; v.world = W; v.slice = lig::knobs().diag_slice;
+    v.all_to_all = [&](const void* src, void* dst, size_t block_bytes, const char* what) -> int {
+        S->used_comm = true;
+        if (ordered) { if (S->comm.all_to_all_on(S->comm.user, src, dst, block_bytes, s)) return comm_fail(what); return LIG_OK; }
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (S->comm.all_to_all(S->comm.user, src, dst, block_bytes)) return comm_fail(what);
+        return LIG_OK;
+    };
+    v.all_gather = [&](const void* src, void* dst, size_t bytes, const char* what) -> int { return all_gather(src, dst, bytes, s, what); };
+    v.drain = [&](const char* what) -> int { return drain(s, what); };
+    v.settle_failed = [&]() -> bool { shard_settle(S); return S->poisoned; };
+    v.forget = [&] { if (S->comm.forget) S->comm.forget(S->comm.user); };
+    TRY(lig_internal_shard_diagnose(c, v, sys, lin_out, lin_cap, quad_out, quad_cap, info));
+    info->ms_total = ms_since(t_begin);
     return LIG_OK;
 }
 
