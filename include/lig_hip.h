@@ -512,6 +512,26 @@ typedef struct {
 } lig_diag_info;
 int lig_rows_diagnose(lig_trace *trace, const lig_linear_system *sys, lig_diag_linear *lin_out, uint64_t lin_cap,
                       lig_diag_quad *quad_out, uint64_t quad_cap, lig_diag_info *info);
+/* lig_rows_diagnose against the statement ATTACHED to the trace: the one lig_rows_prove(rands = NULL, const_sum = NULL) would prove.  For
+ * the caller of lig_linear_prepare who has released the term list, and for the caller of lig_rows_set_linear_values who would otherwise
+ * have to pass "the table of THIS statement" by hand.
+ *   structure  what lig_rows_set_linear or lig_rows_attach_linear attached.  Nothing attached: LIG_E_STATE.
+ *   values     the coefficient table in force for THIS trace: the one given to lig_rows_set_linear_values if one is set, else the
+ *              program's own.  Two traces attached to one program with different values each get their own answer.
+ *   output     order, counts, caps, record layouts and *info exactly as for lig_rows_diagnose: for the same statement the two calls
+ *              return the same bytes.  The quadratic part is the same pass over the same trace.
+ * The program keeps its terms grouped by slot; the call regroups them by constraint on the device (count, scan, scatter: the prepare run
+ * the other way, csrc/diagnose.hip), reads the right-hand sides and the table where they are, and then runs the passes of
+ * lig_rows_diagnose.  No host pass over the terms, no upload.  WHEN, blocking, streams and scratch as for lig_rows_diagnose (scratch:
+ * 8 n_terms + 8 n_constraints for the regrouped list, on top of the residuals and records); a table lig_rows_set_linear_values is still
+ * converting on the side stream is waited for with an event, not with a device-wide synchronise.  It writes nothing the program or the
+ * attachment owns -- not the sampled elements, not the partial sums, not the constant, not the table -- and the envelope of a trace
+ * diagnosed this way is byte-identical to that of one that was not.  LIG_E_STATE outside the window, for a lig_synth_prepare trace and
+ * when nothing is attached; LIG_E_ARG for a NULL array with a cap > 0, a NULL or too small *info, a NULL trace; all decided on the host
+ * before anything is launched.  info->ms_total is the whole call.
+ * The sharded entry is not covered: lig_shard_rows_diagnose takes the term list, as before. */
+int lig_rows_diagnose_attached(lig_trace *trace, lig_diag_linear *lin_out, uint64_t lin_cap, lig_diag_quad *quad_out, uint64_t quad_cap,
+                               lig_diag_info *info);
 
 /* ==== proof file framing (src/webgpu_prover.cpp:437-457 writes gzip(level 6) of the serialized envelope with
  * Boost.iostreams; src/webgpu_verifier.cpp:249-253 reads it back).  Host-only helpers on zlib: the output is a standard

@@ -308,7 +308,8 @@ public:
     // ---- when valid_linear or valid_quad came out 0 (or before prove(), to save the proof): WHICH constraints does the committed
     // witness violate?  lig_rows_diagnose (lig_hip.h) with the system given to set_linear_system -- with the table of
     // set_linear_values, if one was set -- after commit(), before or after prove(), until the next commit().  A batcher that was
-    // given a prepared program (set_linear_program) or no system has no term list to evaluate: the quadratic part only.  Upstream
+    // given a prepared program (set_linear_program) or no system has no term list to evaluate: the quadratic part only -- the linear
+    // constraints of such a batcher are named by diagnose_attached() below, which needs no term list.  Upstream
     // the same witness would have tripped the asserts of constrain_equal / constrain_bit while the guest ran
     // (witness_manager.hpp:418-431).  With shard_over(): lig_shard_rows_diagnose, a COLLECTIVE call -- every rank calls it with the same
     // caps and gets the output of the unsharded batcher, global row numbers included (a constraint may span ranks: the ranks' partial
@@ -324,6 +325,19 @@ public:
             return;
         }
         check(lig_rows_diagnose(trace_, linear_.is_set() ? &sys : nullptr, lin_out, lin_cap, quad_out, quad_cap, info), "lig_rows_diagnose");
+    }
+    // The same question put to the statement ATTACHED to the trace (lig_rows_diagnose_attached, lig_hip.h): the structure of
+    // set_linear_system or set_linear_program as it lies on the device, with the values of set_linear_values in force if any were set --
+    // exactly what prove(nullptr) proves.  No term list is needed: the caller of set_linear_program may have released its own long ago.
+    // After commit(), before or after prove(), until the next commit(); same output as diagnose().  std::logic_error before commit(),
+    // without a system or program, and with shard_over() (a rank's structure is local: diagnose() there).
+    void diagnose_attached(lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
+        if (sharded_) throw std::logic_error("hip_row_batcher::diagnose_attached: not on a sharded batcher (diagnose)");
+        if (pass_ == 1 || !trace_) throw std::logic_error("hip_row_batcher::diagnose_attached before commit");
+        if (!has_linear() || !linear_on_trace_) throw std::logic_error("hip_row_batcher::diagnose_attached without a linear system or program");
+        if (!info) throw std::invalid_argument("hip_row_batcher::diagnose_attached: null info");
+        info->struct_bytes = sizeof(lig_diag_info);
+        check(lig_rows_diagnose_attached(trace_, lin_out, lin_cap, quad_out, quad_cap, info), "lig_rows_diagnose_attached");
     }
     // the next proof with this batcher: staging and (for the same row kinds) every device buffer of the trace are kept
     void reset(const hip_proof_meta* meta = nullptr) {

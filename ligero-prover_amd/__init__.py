@@ -42,7 +42,7 @@ EXPORTS = [
     "lig_shard_rows_set_linear", "lig_shard_rows_linear_stats", "lig_linear_shard_count", "lig_shard_rows_diagnose",
     "lig_linear_prepare", "lig_linear_program_release", "lig_linear_program_bytes", "lig_rows_attach_linear", "lig_rows_verify_attach_linear",
     "lig_rows_set_linear_values", "lig_rows_verify_set_linear_values", "lig_linear_program_form",
-    "lig_rows_diagnose",
+    "lig_rows_diagnose", "lig_rows_diagnose_attached",
 ]
 
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
@@ -364,6 +364,7 @@ def load_library():
     L.lig_linear_program_form.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.lig_rows_diagnose.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, u64, C.POINTER(DiagInfo)]
     L.lig_shard_rows_diagnose.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, u64, C.POINTER(DiagInfo)]
+    L.lig_rows_diagnose_attached.argtypes = [vp, vp, u64, vp, u64, C.POINTER(DiagInfo)]
     return L
 
 
@@ -1091,6 +1092,16 @@ class Context:
         lin, quad = np.zeros(lin_cap, dtype=DIAG_LINEAR), np.zeros(quad_cap, dtype=DIAG_QUAD)
         self.check(self.L.lig_rows_diagnose(trace, C.byref(system) if system is not None else None, _hptr(lin) if lin_cap else None, lin_cap,
                                             _hptr(quad) if quad_cap else None, quad_cap, C.byref(info)))
+        return info, lin[:info.n_linear_reported], quad[:info.n_quad_reported]
+
+    def rows_diagnose_attached(self, trace, lin_cap=1024, quad_cap=1024):
+        """lig_rows_diagnose_attached: rows_diagnose against the statement attached to the trace (rows_set_linear / rows_attach_linear, with
+        the values of rows_set_linear_values in force): no term list is passed -> the same triple as rows_diagnose"""
+        info = DiagInfo()
+        info.struct_bytes = C.sizeof(DiagInfo)
+        lin, quad = np.zeros(lin_cap, dtype=DIAG_LINEAR), np.zeros(quad_cap, dtype=DIAG_QUAD)
+        self.check(self.L.lig_rows_diagnose_attached(trace, _hptr(lin) if lin_cap else None, lin_cap, _hptr(quad) if quad_cap else None, quad_cap,
+                                                     C.byref(info)))
         return info, lin[:info.n_linear_reported], quad[:info.n_quad_reported]
 
     def shard_rows_diagnose(self, shard, system=None, lin_cap=1024, quad_cap=1024):

@@ -2,10 +2,9 @@
 //
 // The prover's self-check answers with one bit per test (valid_linear, valid_quad), computed from a random combination.  This pass
 // evaluates the statement itself on the committed witness matrix, exactly and without randomness, and returns the violated constraints:
-//   k_diag_lin         one lane per linear constraint with at most HEAVY_MIN terms: walks the caller's constraint-major term list
-//                      (the slot-major regrouping of a lig_linear_program is of no use here: per-constraint sums over it would need
-//                      256-bit atomics), gathers w[slot] (32 bytes, random), adds / subtracts it or multiplies it by a table
-//                      coefficient first (Montgomery copy of the table: one product per such term), subtracts b_c
+//   k_diag_lin         one lane per linear constraint with at most HEAVY_MIN terms: walks a constraint-major term list, gathers w[slot]
+//                      (32 bytes, random), adds / subtracts it or multiplies it by a table coefficient first (table in Montgomery
+//                      form: one product per such term), subtracts b_c
 //   k_diag_lin_heavy   one workgroup per constraint with more terms: lanes stride the segment, fixed LDS tree (lin_block_sum)
 //   k_diag_quad        one lane per (quadratic term, column < l): x * y - z, b * b - b for a bit row, x - z for an equality pair
 // and, for one rank of a sharded rows job (lig_shard_rows_diagnose: the rank holds only the rows it was dealt, a constraint may span ranks):
@@ -13,6 +12,19 @@
 //                      table: a * w of the terms whose row the rank holds, the others skipped; a canonical PARTIAL per constraint, no b_c, no flag
 //   k_diag_reduce      the owner of a sub-block of the slice adds the W partials it received, subtracts b_c, writes residual and flag
 // (exact arithmetic mod p: no result depends on an order).
+// Where the constraint-major list comes from is the only difference between the two one-GPU entries:
+//   lig_rows_diagnose            the caller's lig_linear_system, uploaded, with a scratch copy of its table in Montgomery form
+//   lig_rows_diagnose_attached   the statement ATTACHED to the trace.  Its program keeps the terms slot-major (linear.hip: begin[], ent[] =
+//                      (constraint, coefficient index)); per-constraint sums straight over that would need 256-bit atomics, so it is
+//                      regrouped first -- the prepare of linear.hip run the other way:
+//     k_diag_att_count    one lane per entry: a 32-bit atomic on the counter of its constraint
+//     (rocPRIM exclusive scan of the counters -> cbegin; k_diag_att_classify: the constraints with more than HEAVY_MIN terms, sorted on the host)
+//     k_diag_att_scatter  one lane per entry: its slot by binary search over begin[] (a slot with a very long segment does not serialise
+//                      on one lane), lig_lin_term{slot, coef} to cbegin[c] + atomicAdd(cursor + c, 1)
+//                      The atomics only decide WHERE a term lands inside its constraint's segment; the sum over a segment is exact, so no
+//                      output byte depends on them.  One constraint with very many terms sends that many atomics to one address in the
+//                      scatter: correct, slow, and off the proving path -- left as it is.
+//                      rhs_coef and the Montgomery table in force for the attachment are read where they are: no copy, no conversion.
 // Every lane writes its canonical residual and a 32-bit flag; the flags go through an exclusive scan (rocPRIM) and the first `cap`
 // violated items are scattered into a record array in ascending order -- no atomic decides an order or a count, the output is the same
 // bytes on every run.  The quadratic items (terms x l) are processed in slices of a fixed scratch budget; the running count and the
@@ -82,6 +94,40 @@ static __device__ __forceinline__ void diag_finish(uint32_t c, uint32_t at, fr a
     if (ri) acc = fr_sub(acc, diag_coef_value(rhs_coef[ri - 1], coef_mont));
     fr_store(res + at, acc);
     flag[at] = fr_is_zero(acc) ? 0u : 1u;
+}
+
+// ---- the statement attached to the trace -> constraint-major (file header).  ent[e].x < n_constraints for every entry, the segments of
+// begin[] tile [0, n_terms): the prepare built both from a system lig_linear_check accepted.
+// slot of entry e: the s with begin[s] <= e < begin[s + 1] (slots may be empty); e < n_terms = begin[n_slots]
+static __device__ __forceinline__ uint32_t diag_slot_of(const uint32_t* __restrict__ begin, uint32_t n_slots, uint32_t e) {
+    uint32_t lo = 0, hi = n_slots;                // first index in (0, n_slots] whose entry is > e, minus one (lin_constraint_of, linear.hip)
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (begin[mid + 1] > e) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+__global__ void __launch_bounds__(LIN_WG) k_diag_att_count(const uint2* __restrict__ ent, uint32_t n_terms, uint32_t* __restrict__ count) {
+    for (uint64_t e = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; e < n_terms; e += (uint64_t)gridDim.x * LIN_WG) atomicAdd(count + ent[e].x, 1u);
+}
+// constraints with more than HEAVY_MIN terms, appended in any order: the host sorts the list
+__global__ void __launch_bounds__(LIN_WG) k_diag_att_classify(const uint32_t* __restrict__ count, uint32_t n_constraints, uint32_t* __restrict__ heavy,
+                                                              uint32_t heavy_cap, uint32_t* __restrict__ n_heavy) {
+    for (uint64_t c = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; c < n_constraints; c += (uint64_t)gridDim.x * LIN_WG) {
+        if (count[c] <= HEAVY_MIN) continue;
+        const uint32_t i = atomicAdd(n_heavy, 1u);
+        if (i < heavy_cap) heavy[i] = (uint32_t)c;
+    }
+}
+// cursor[c] counts up to the number of terms of c (the counts cbegin was scanned from): every position lies inside the segment of c
+__global__ void __launch_bounds__(LIN_WG) k_diag_att_scatter(const uint2* __restrict__ ent, uint32_t n_terms, const uint32_t* __restrict__ begin, uint32_t n_slots,
+                                                             const uint32_t* __restrict__ cbegin, uint32_t* __restrict__ cursor, lig_lin_term* __restrict__ terms) {
+    for (uint64_t e = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; e < n_terms; e += (uint64_t)gridDim.x * LIN_WG) {
+        const uint2 en = ent[e];
+        lig_lin_term tm;
+        tm.slot = diag_slot_of(begin, n_slots, (uint32_t)e); tm.coef = en.y;
+        terms[cbegin[en.x] + atomicAdd(cursor + en.x, 1u)] = tm;
+    }
 }
 
 // rhs_constraint is strictly ascending: every entry of rhs_index is written at most once
@@ -231,42 +277,89 @@ int diag_scan(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, const uint32_t*
     return wait();
 }
 
-// the caller's system on the device: the constraint-major term list as passed, a scratch copy of its table in Montgomery form (the table
-// of an attached program is neither read nor written), rhs_index, the constraints with more than HEAVY_MIN terms (ascending)
+// a system on the device, as the linear passes consume it: a constraint-major term list, rhs_index, the constraints with more than HEAVY_MIN
+// terms (ascending), the right-hand-side coefficients and a table in Montgomery form.
+//   diag_upload_system   the caller's system: the term list as passed, a scratch copy of its table (the table of an attached program is
+//                        neither read nor written)
+//   diag_regroup_system  the statement attached to the trace: the term list regrouped in scratch; rhs_coef and coef point INTO the program /
+//                        the attachment, which nothing here writes
 struct DiagSystem {
     uint32_t NC = 0;
     std::vector<uint32_t> heavy;
-    uint32_t *tb = nullptr, *rhs_coef = nullptr, *rhs_index = nullptr, *heavy_dev = nullptr;
+    uint32_t *tb = nullptr, *rhs_index = nullptr, *heavy_dev = nullptr;
+    const uint32_t* rhs_coef = nullptr;
     lig_lin_term* terms = nullptr;
-    fr* coef = nullptr;
+    const fr* coef = nullptr;
 };
 int diag_upload_system(lig_ctx* c, DiagScratch& sc, const lig_linear_system* sys, DiagSystem& d) {
     hipStream_t s = c->stream;
     const uint32_t NC = d.NC = (uint32_t)sys->n_constraints, NT = (uint32_t)sys->n_terms, NR = (uint32_t)sys->n_rhs;
     for (uint32_t cn = 0; cn < NC; cn++) if (sys->term_begin[cn + 1] - sys->term_begin[cn] > lig::HEAVY_MIN) d.heavy.push_back(cn);
-    uint32_t* d_rhs_c = nullptr;
+    uint32_t *d_rhs_c = nullptr, *d_rhs_coef = nullptr; fr* d_coef = nullptr;
     TRY(sc.alloc((void**)&d.tb, ((size_t)NC + 1) * 4));
     TRY(sc.alloc((void**)&d.terms, (size_t)NT * sizeof(lig_lin_term)));
     TRY(sc.alloc((void**)&d_rhs_c, (size_t)NR * 4));
-    TRY(sc.alloc((void**)&d.rhs_coef, (size_t)NR * 4));
+    TRY(sc.alloc((void**)&d_rhs_coef, (size_t)NR * 4));
     TRY(sc.alloc((void**)&d.rhs_index, (size_t)NC * 4));
     TRY(sc.alloc((void**)&d.heavy_dev, d.heavy.size() * 4));
-    TRY(sc.alloc((void**)&d.coef, (size_t)sys->n_coefs * 32));
+    TRY(sc.alloc((void**)&d_coef, (size_t)sys->n_coefs * 32));
+    d.rhs_coef = d_rhs_coef; d.coef = d_coef;
     HIP_TRY(c, hipMemcpyAsync(d.tb, sys->term_begin, ((size_t)NC + 1) * 4, hipMemcpyHostToDevice, s));
     if (NT) HIP_TRY(c, hipMemcpyAsync(d.terms, sys->terms, (size_t)NT * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
     if (NR) {
         HIP_TRY(c, hipMemcpyAsync(d_rhs_c, sys->rhs_constraint, (size_t)NR * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d.rhs_coef, sys->rhs_coef, (size_t)NR * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_rhs_coef, sys->rhs_coef, (size_t)NR * 4, hipMemcpyHostToDevice, s));
     }
     if (!d.heavy.empty()) HIP_TRY(c, hipMemcpyAsync(d.heavy_dev, d.heavy.data(), d.heavy.size() * 4, hipMemcpyHostToDevice, s));
-    if (sys->n_coefs) HIP_TRY(c, hipMemcpyAsync(d.coef, sys->coefs, (size_t)sys->n_coefs * 32, hipMemcpyHostToDevice, s));
-    lig::launch_lin_coefs_mont(s, d.coef, sys->n_coefs);
+    if (sys->n_coefs) HIP_TRY(c, hipMemcpyAsync(d_coef, sys->coefs, (size_t)sys->n_coefs * 32, hipMemcpyHostToDevice, s));
+    lig::launch_lin_coefs_mont(s, d_coef, sys->n_coefs);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemsetAsync(d.rhs_index, 0, (size_t)NC * 4, s));
     if (NR) {
         hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, d_rhs_c, NR, d.rhs_index);
         HIP_TRY(c, hipGetLastError());
     }
+    return LIG_OK;
+}
+// The statement attached to the trace (v: prover_common.hpp, not sharded) -> constraint-major, in scratch: count, scan, scatter (file header).
+// Scratch: cbegin (n_constraints + 1) x 4, counters / cursor (n_constraints + 1) x 4, terms n_terms x 8, rhs_index, the short heavy list.
+// Blocks once, for the scan's total and the number of heavy constraints.
+int diag_regroup_system(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, void** scan_tmp, size_t* scan_cap, const lig_linear_view& v, DiagSystem& d) {
+    hipStream_t s = c->stream;
+    const uint32_t NC = d.NC = (uint32_t)v.n_constraints, NT = (uint32_t)v.n_terms, NR = (uint32_t)v.n_rhs;
+    const uint32_t heavy_cap = NT / (lig::HEAVY_MIN + 1) + 1;
+    uint32_t *d_cursor = nullptr, *d_nheavy = nullptr;
+    TRY(sc.alloc((void**)&d.tb, ((size_t)NC + 1) * 4));
+    TRY(sc.alloc((void**)&d_cursor, ((size_t)NC + 1) * 4));
+    TRY(sc.alloc((void**)&d.terms, (size_t)NT * sizeof(lig_lin_term)));
+    TRY(sc.alloc((void**)&d.rhs_index, (size_t)NC * 4));
+    TRY(sc.alloc((void**)&d.heavy_dev, (size_t)heavy_cap * 4));
+    TRY(sc.alloc((void**)&d_nheavy, 4));
+    d.rhs_coef = v.rhs_coef; d.coef = v.coef;
+    // values set on the side stream (lig_rows_set_linear_values): the passes below read the table once its conversion has finished
+    if (v.coef_ready) HIP_TRY(c, hipStreamWaitEvent(s, v.coef_ready, 0));
+    HIP_TRY(c, hipMemsetAsync(d_cursor, 0, ((size_t)NC + 1) * 4, s));
+    HIP_TRY(c, hipMemsetAsync(d_nheavy, 0, 4, s));
+    if (NT) hipLaunchKernelGGL(lig::k_diag_att_count, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, d_cursor);
+    hipLaunchKernelGGL(lig::k_diag_att_classify, dim3(diag_grid(NC)), dim3(lig::LIN_WG), 0, s, d_cursor, NC, d.heavy_dev, heavy_cap, d_nheavy);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t total = 0, n_heavy = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n_heavy, d_nheavy, 4, hipMemcpyDeviceToHost, s));
+    const int rc = diag_scan(c, sc, wait, d_cursor, d.tb, NC, scan_tmp, scan_cap, &total);
+    if (rc != LIG_OK) { (void)wait(); return rc; }      // (the copy into n_heavy may still be queued)
+    if (total != NT || n_heavy > heavy_cap) FAIL(c, LIG_E_STATE, "lig_rows_diagnose_attached: the attached program's index does not add up to its term count");
+    if (n_heavy) {      // ascending: the same launch geometry whatever order the atomics appended them in
+        d.heavy.resize(n_heavy);
+        HIP_TRY(c, hipMemcpyAsync(d.heavy.data(), d.heavy_dev, (size_t)n_heavy * 4, hipMemcpyDeviceToHost, s));
+        TRY(wait());
+        std::sort(d.heavy.begin(), d.heavy.end());
+        HIP_TRY(c, hipMemcpyAsync(d.heavy_dev, d.heavy.data(), (size_t)n_heavy * 4, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(c, hipMemsetAsync(d_cursor, 0, ((size_t)NC + 1) * 4, s));
+    if (NT) hipLaunchKernelGGL(lig::k_diag_att_scatter, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, v.begin, v.n_slots, d.tb, d_cursor, d.terms);
+    HIP_TRY(c, hipMemsetAsync(d.rhs_index, 0, (size_t)NC * 4, s));
+    if (NR) hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, v.rhs_c, NR, d.rhs_index);
+    HIP_TRY(c, hipGetLastError());
     return LIG_OK;
 }
 
@@ -318,10 +411,13 @@ int diag_quad_pass(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, void** sca
 }
 }  // namespace
 
-// msgs: the committed rows x k witness matrix; tri_dev / n_quad_terms: the quadratic terms of the trace (quad_terms(), rows_plan.hpp); sys (may be NULL) has
-// passed lig_linear_check against the trace's kinds.  Waits with lig_internal_wait_stream (prover.hip: bounded spin, then the blocking wait).
-int lig_internal_rows_diagnose(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* tri_dev, uint64_t n_quad_terms, const lig_linear_system* sys,
-                               lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
+namespace {
+// The two one-GPU entries.  msgs: the committed rows x k witness matrix; tri_dev / n_quad_terms: the quadratic terms of the trace (quad_terms(),
+// rows_plan.hpp).  The linear statement is `sys` (it has passed lig_linear_check against the trace's kinds) or `att` (the view of the trace's
+// attachment), at most one of them: where the DiagSystem comes from is all that differs.  Waits with lig_internal_wait_stream (prover.hip: bounded
+// spin, then the blocking wait).
+int diag_rows(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* tri_dev, uint64_t n_quad_terms, const lig_linear_system* sys, const lig_linear_view* att,
+              lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
     hipStream_t s = c->stream;
     const uint32_t l = c->l, k = c->k;
     const uint64_t l_recip = diag_reciprocal(l);
@@ -330,9 +426,10 @@ int lig_internal_rows_diagnose(lig_ctx* c, const fr* msgs, uint64_t rows, const 
     const DiagWait wait = [c, s]() -> int { HIP_TRY(c, lig_internal_wait_stream(s)); return LIG_OK; };
 
     // ---------------------------------------------------------------- linear constraints
-    if (sys && sys->n_constraints) {
+    if (sys ? sys->n_constraints : att ? att->n_constraints : 0) {
         DiagSystem d;
-        TRY(diag_upload_system(c, sc, sys, d));
+        if (sys) TRY(diag_upload_system(c, sc, sys, d));
+        else TRY(diag_regroup_system(c, sc, wait, &scan_tmp, &scan_cap, *att, d));
         const uint32_t NC = d.NC;
         uint32_t *d_flag = nullptr, *d_pos = nullptr; fr* d_res = nullptr;
         TRY(sc.alloc((void**)&d_res, (size_t)NC * 32));
@@ -367,6 +464,18 @@ int lig_internal_rows_diagnose(lig_ctx* c, const fr* msgs, uint64_t rows, const 
         TRY(diag_quad_pass(c, sc, wait, &scan_tmp, &scan_cap, msgs, tri_dev, n_quad_terms, quad_cap, quad_out, nullptr, nullptr, nullptr, nullptr, &info->n_quad_bad,
                            &info->n_quad_reported));
     return LIG_OK;
+}
+}  // namespace
+
+int lig_internal_rows_diagnose(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* tri_dev, uint64_t n_quad_terms, const lig_linear_system* sys,
+                               lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
+    return diag_rows(c, msgs, rows, tri_dev, n_quad_terms, sys, nullptr, lin_out, lin_cap, quad_out, quad_cap, info);
+}
+int lig_internal_rows_diagnose_attached(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* tri_dev, uint64_t n_quad_terms, const lig_linear* att,
+                                        lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
+    const lig_linear_view v = lig_internal_linear_view(att);
+    if (v.sharded) FAIL(c, LIG_E_STATE, "lig_rows_diagnose_attached: the attached structure is one rank's share of a sharded trace");
+    return diag_rows(c, msgs, rows, tri_dev, n_quad_terms, nullptr, &v, lin_out, lin_cap, quad_out, quad_cap, info);
 }
 
 // One rank of a sharded rows job (lig_shard_rows_diagnose, lig_hip.h; v: prover_common.hpp).  Collective: whether a collective is issued,

@@ -226,6 +226,7 @@ struct lig_linear {
     fr* vals = nullptr;                 // lig_rows_set_linear_values: n_coefs elements, Montgomery form once k_lin_coefs_mont has run
     uint8_t* h_vals = nullptr;          // pinned staging of the canonical table: the caller's memory is free when set_values returns
     hipEvent_t ev_vals = nullptr;       // the copy out of h_vals has finished
+    hipEvent_t ev_mont = nullptr;       // ... and k_lin_coefs_mont behind it: `vals` is in Montgomery form (a reader on another stream waits for it)
 };
 
 static bool lin_coef_ok(uint32_t coef, uint64_t n_coefs) { return coef == LIG_COEF_ONE || coef == LIG_COEF_NEG_ONE || coef < n_coefs; }
@@ -275,6 +276,7 @@ void lig_internal_linear_destroy(lig_linear* L) {
     (void)hipHostFree(L->h_const);
     (void)hipHostFree(L->h_vals);
     if (L->ev_vals) (void)hipEventDestroy(L->ev_vals);
+    if (L->ev_mont) (void)hipEventDestroy(L->ev_mont);
     linear_program_release(L->P);
     delete L;
 }
@@ -500,13 +502,26 @@ int lig_internal_linear_set_values(lig_ctx* c, lig_linear* L, const uint8_t* coe
     if (!L->h_vals) HIP_TRY(c, hipHostMalloc((void**)&L->h_vals, bytes, hipHostMallocDefault));
     if (!L->ev_vals) HIP_TRY(c, hipEventCreateWithFlags(&L->ev_vals, hipEventDisableTiming));
     else HIP_TRY(c, hipEventSynchronize(L->ev_vals));          // the copy of the previous table out of the staging buffer
+    if (!L->ev_mont) HIP_TRY(c, hipEventCreateWithFlags(&L->ev_mont, hipEventDisableTiming));
     std::memcpy(L->h_vals, coefs, bytes);
     HIP_TRY(c, hipMemcpyAsync(L->vals, L->h_vals, bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipEventRecord(L->ev_vals, st));
     lig::launch_lin_coefs_mont(st, L->vals, n_coefs);
     HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(L->ev_mont, st));
     L->coef = L->vals;
     return LIG_OK;
+}
+// what lig_rows_diagnose_attached (diagnose.hip) reads of an attachment; nothing of it is written through the view
+lig_linear_view lig_internal_linear_view(const lig_linear* L) {
+    const lig_linear_program* P = L->P;
+    lig_linear_view v;
+    v.sharded = P->sharded;
+    v.n_constraints = P->n_constraints; v.n_terms = P->n_terms; v.n_rhs = P->n_rhs; v.n_slots = P->n_slots;
+    v.begin = P->begin; v.ent = P->ent; v.rhs_c = P->rhs_c; v.rhs_coef = P->rhs_coef;
+    v.coef = L->coef;
+    v.coef_ready = L->coef == L->vals && L->vals ? L->ev_mont : nullptr;
+    return v;
 }
 
 // this rank's share of a deal: which rows are local, its slice of the right-hand sides.  grow = the global row of every local row.

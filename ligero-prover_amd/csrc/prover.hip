@@ -1069,6 +1069,25 @@ int lig_rows_diagnose(lig_trace* T, const lig_linear_system* sys, lig_diag_linea
     return LIG_OK;
 }
 
+// the same passes over the statement attached to the trace (lig_rows_set_linear / lig_rows_attach_linear, the values in force): nothing of
+// the program or the attachment is written
+int lig_rows_diagnose_attached(lig_trace* T, lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
+    if (!T || !info || info->struct_bytes < sizeof(lig_diag_info)) return LIG_E_ARG;
+    if ((lin_cap && !lin_out) || (quad_cap && !quad_out)) return LIG_E_ARG;
+    const auto t_begin = clk::now();
+    lig_ctx* c = T->c;
+    CHECK_CTX(c);
+    if (!T->from_rows) FAIL(c, LIG_E_STATE, "lig_rows_diagnose_attached: not a rows trace");
+    if (!T->diag_ok) FAIL(c, LIG_E_STATE, "lig_rows_diagnose_attached: no committed matrix (between lig_rows_commit and the next commit, or a lig_rows_restart after lig_rows_prove)");
+    if (!T->linear) FAIL(c, LIG_E_STATE, "lig_rows_diagnose_attached: nothing is attached (lig_rows_set_linear, lig_rows_attach_linear)");
+    const uint32_t struct_bytes = info->struct_bytes;
+    std::memset(info, 0, sizeof *info);
+    info->struct_bytes = struct_bytes;
+    TRY(lig_internal_rows_diagnose_attached(c, T->msgs, T->R, T->tri_dev, T->triples.size() / 3, T->linear, lin_out, lin_cap, quad_out, quad_cap, info));
+    info->ms_total = ms_since(t_begin);
+    return LIG_OK;
+}
+
 int lig_rows_push_rands(lig_trace* T, uint64_t first_row, uint64_t n_rows, const void* host_rows) {
     return lig_rows_push_rands_sparse(T, first_row, n_rows, nullptr, host_rows);
 }

@@ -452,12 +452,30 @@ void lig_internal_linear_shard_count(const lig_linear_system* sys, uint32_t l, c
 void lig_internal_linear_stats(const lig_linear* L, uint64_t* local_terms, uint64_t* sampled);
 const fr* lig_internal_linear_partial_dev(const lig_linear* L);
 uint8_t* lig_internal_linear_const_buf(lig_linear* L);
+// a read-only view of an attachment (lig_rows_diagnose_attached): the slot-major index of its program -- the segment of slot s is
+// ent[begin[s] .. begin[s + 1]), ent = (constraint, coefficient index) --, the right-hand sides, and the Montgomery table IN FORCE for
+// this attachment (the program's, or the values of lig_rows_set_linear_values).  coef_ready: NULL, or the event recorded behind the
+// conversion of those values on the stream they were set on -- a reader on another stream waits for it first.
+struct lig_linear_view {
+    bool sharded = false;                              // one rank's local, compactly numbered structure: not a system of the whole trace
+    uint64_t n_constraints = 0, n_terms = 0, n_rhs = 0;
+    uint32_t n_slots = 0;
+    const uint32_t* begin = nullptr;
+    const uint2* ent = nullptr;
+    const uint32_t *rhs_c = nullptr, *rhs_coef = nullptr;
+    const fr* coef = nullptr;
+    hipEvent_t coef_ready = nullptr;
+};
+lig_linear_view lig_internal_linear_view(const lig_linear* L);
 
 // lig_rows_diagnose (diagnose.hip): the residual of every linear constraint of `sys` (NULL: none; it has passed lig_linear_check) and of every
 // (quadratic term, column < l) over the committed rows x k matrix `msgs`; tri_dev = the trace's quadratic terms, 3 row indices each.
 // Blocking, on the context's main stream; waits the way a proof does (lig_internal_wait_stream, prover.hip).
 int lig_internal_rows_diagnose(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* tri_dev, uint64_t n_quad_terms, const lig_linear_system* sys,
                                lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info);
+// lig_rows_diagnose_attached: the same passes over the statement ATTACHED to the trace (`att`: not sharded), regrouped by constraint on the device
+int lig_internal_rows_diagnose_attached(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* tri_dev, uint64_t n_quad_terms, const lig_linear* att,
+                                        lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info);
 hipError_t lig_internal_wait_stream(hipStream_t st);
 // lig_shard_rows_diagnose (diagnose.hip): what one rank of a sharded rows job holds, and the shard's collectives and waits (shard.hip).
 // all_to_all / all_gather run on the context's main stream (stream-ordered forms) or after it has drained (host-synchronous callbacks);
