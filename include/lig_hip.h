@@ -533,6 +533,60 @@ int lig_rows_diagnose(lig_trace *trace, const lig_linear_system *sys, lig_diag_l
 int lig_rows_diagnose_attached(lig_trace *trace, lig_diag_linear *lin_out, uint64_t lin_cap, lig_diag_quad *quad_out, uint64_t quad_cap,
                                lig_diag_info *info);
 
+/* ---- explain a constraint: its terms, coefficients and witness values  (csrc/diagnose.hip)
+ * lig_rows_diagnose* NAME the violated constraints; these entries SHOW constraints, as the library holds them.  Upstream constrain_equal /
+ * constrain_bit assert with the values in hand (witness_manager.hpp:418-431); a caller who released its term list after
+ * lig_linear_prepare, or whose QZ rows are derived on the device (LIG_ELEM_PRODUCT), or whose rows are mixed (wide_per_row), has neither
+ * the terms nor the witness values any more.
+ *   constraints  n_asked constraint numbers of the statement, strictly ascending, each < n_constraints (else LIG_E_ARG).
+ *   con_out      n_asked records (required when n_asked > 0), record i for asked constraint i:
+ *                  n_terms     ALL its terms, reported or not; 0 for an empty constraint
+ *                  first_term  the index of its first term in the full output order below (may be >= term_cap)
+ *                  rhs         b_c, canonical: the table entry named by rhs_coef, zero when the constraint is not in rhs_constraint
+ *                  residual    sum a * w - b_c over all its terms, canonical: the 32 bytes lig_rows_diagnose writes for the constraint
+ *                              when it is violated, zero when it holds
+ *   terms_out    the first term_cap records of the full order: ascending asked constraint, then ascending slot, then ascending
+ *                coef_index as an unsigned number (LIG_COEF_NEG_ONE, LIG_COEF_ONE come last).  A term the statement holds twice appears
+ *                twice.  coef = the canonical value the index stands for (1, p - 1, or the table entry IN FORCE); value = the canonical
+ *                committed w[slot] -- on a derived row the product the device formed, on a record slot of a mixed row the record's
+ *                value.  Records that compare equal in this order are byte-identical: no output byte depends on an atomic, on
+ *                scheduling, or on which lig_linear_prepare of the same system made the program.  NULL with term_cap = 0 gives the
+ *                counts and con_out only.
+ *   info         n_terms_total = the terms of all asked constraints, n_terms_reported = min(n_terms_total, term_cap); ms_total = the
+ *                whole call.
+ * lig_rows_explain uses `sys` AS PASSED, like lig_rows_diagnose: it goes through lig_linear_check against the trace's kinds first
+ * (LIG_E_ARG; sys == NULL is LIG_E_ARG here), and what is attached to the trace is neither used nor modified.
+ * lig_rows_explain_attached uses what lig_rows_set_linear / lig_rows_attach_linear attached, with the table of
+ * lig_rows_set_linear_values in force if one is set (a conversion still running on the side stream is waited for with its event, not
+ * with a device-wide synchronise); nothing attached: LIG_E_STATE.  For the same statement the two calls return the same bytes.
+ * lig_rows_read_slots: values[i] (32 bytes) = the canonical committed element of slots[i] = row * l + column, over the committed rows
+ * of ANY kind (masks excluded), column < l; any order, repeats allowed; a slot >= rows * l is LIG_E_ARG; n_slots = 0 is LIG_OK and
+ * launches nothing.
+ * WHEN, blocking, streams as for lig_rows_diagnose: inside its window (LIG_E_STATE outside, and for a lig_synth_prepare trace), work
+ * enqueued on the context stream alone, scratch allocated per call and freed before it returns.  Nothing a proof depends on is written
+ * (the envelope of a trace that was explained or read is byte-identical to that of one that was not), nothing the program or the
+ * attachment owns is written.  The attached entry selects the asked terms straight from the program's slot-major index (one mark
+ * pass over its entries, a scan, a collect: no regrouping of the statement, no atomic); the m selected 12-byte items are ordered on the
+ * host.  Scratch, attached: 8 (n_terms + 1) for marks and positions, 4 n_constraints for the right-hand-side index, 4 n_asked; term
+ * list: the uploaded system as for lig_rows_diagnose, 8 n_asked; both: 20 m for the items, 88 n_asked + 84 min(m, term_cap) for the
+ * records.  LIG_E_ARG: a NULL trace, a NULL or too small *info, con_out == NULL or constraints == NULL with n_asked > 0, terms_out ==
+ * NULL with term_cap > 0, slots or values == NULL with n_slots > 0, and the range errors above -- all decided on the host before
+ * anything is launched: an index out of range never reaches a kernel.
+ * Not covered: the sharded entry (a rank's structure is local and compactly numbered: lig_shard_rows_diagnose names the constraints,
+ * the term list is the caller's), and a verifier side (the verifier has no witness). */
+typedef struct { uint32_t constraint, slot, coef_index, reserved; uint8_t coef[32]; uint8_t value[32]; } lig_explain_term;       /* 80 bytes */
+typedef struct { uint32_t constraint, reserved; uint64_t n_terms, first_term; uint8_t rhs[32]; uint8_t residual[32]; } lig_explain_constraint; /* 88 bytes */
+typedef struct {
+    uint32_t struct_bytes, reserved;     /* sizeof(lig_explain_info) as the caller sees it; smaller than the library's: LIG_E_ARG */
+    uint64_t n_terms_total, n_terms_reported;
+    double   ms_total;                   /* wall time of the call */
+} lig_explain_info;
+int lig_rows_explain(lig_trace *trace, const lig_linear_system *sys, const uint32_t *constraints, uint64_t n_asked,
+                     lig_explain_constraint *con_out, lig_explain_term *terms_out, uint64_t term_cap, lig_explain_info *info);
+int lig_rows_explain_attached(lig_trace *trace, const uint32_t *constraints, uint64_t n_asked,
+                              lig_explain_constraint *con_out, lig_explain_term *terms_out, uint64_t term_cap, lig_explain_info *info);
+int lig_rows_read_slots(lig_trace *trace, const uint32_t *slots, uint64_t n_slots, uint8_t *values /* n_slots x 32 */);
+
 /* ==== proof file framing (src/webgpu_prover.cpp:437-457 writes gzip(level 6) of the serialized envelope with
  * Boost.iostreams; src/webgpu_verifier.cpp:249-253 reads it back).  Host-only helpers on zlib: the output is a standard
  * gzip member that any gzip reader (the reference's gzip_decompressor included) accepts; compressed BYTES depend on the

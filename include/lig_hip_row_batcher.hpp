@@ -339,6 +339,42 @@ public:
         info->struct_bytes = sizeof(lig_diag_info);
         check(lig_rows_diagnose_attached(trace_, lin_out, lin_cap, quad_out, quad_cap, info), "lig_rows_diagnose_attached");
     }
+    // ---- diagnose() names the violated constraints; these SHOW constraints: every term with its slot, coefficient index, coefficient
+    // value and the witness value the library committed, the right-hand side and the residual (lig_rows_explain, lig_hip.h).
+    // constraints: n_asked numbers, strictly ascending; con_out: n_asked records; terms_out: the first term_cap term records in
+    // ascending (constraint, slot, coef_index) order (NULL with term_cap = 0: con_out and the counts only).
+    // explain(): the system given to set_linear_system, with the table of set_linear_values if one was set -- as diagnose() does; a
+    // batcher with a prepared program or without a system has no term list: std::logic_error (explain_attached()).
+    // explain_attached(): the statement attached to the trace, as diagnose_attached(): no term list is needed.
+    // Both after commit(), before or after prove(), until the next commit(); the same bytes for the same statement.  std::logic_error
+    // before commit() and with shard_over() (a rank's structure is local and compactly numbered).
+    void explain(const uint32_t* constraints, uint64_t n_asked, lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap,
+                 lig_explain_info* info) {
+        if (sharded_) throw std::logic_error("hip_row_batcher::explain: not on a sharded batcher");
+        if (pass_ == 1 || !trace_) throw std::logic_error("hip_row_batcher::explain before commit");
+        if (!linear_.is_set()) throw std::logic_error("hip_row_batcher::explain without a linear system (explain_attached)");
+        if (!info) throw std::invalid_argument("hip_row_batcher::explain: null info");
+        lig_linear_system sys = *linear_.get();
+        if (values_set_) { sys.coefs = values_.data(); sys.n_coefs = values_.size() / 32; }
+        info->struct_bytes = sizeof(lig_explain_info);
+        check(lig_rows_explain(trace_, &sys, constraints, n_asked, con_out, terms_out, term_cap, info), "lig_rows_explain");
+    }
+    void explain_attached(const uint32_t* constraints, uint64_t n_asked, lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap,
+                          lig_explain_info* info) {
+        if (sharded_) throw std::logic_error("hip_row_batcher::explain_attached: not on a sharded batcher");
+        if (pass_ == 1 || !trace_) throw std::logic_error("hip_row_batcher::explain_attached before commit");
+        if (!has_linear() || !linear_on_trace_) throw std::logic_error("hip_row_batcher::explain_attached without a linear system or program");
+        if (!info) throw std::invalid_argument("hip_row_batcher::explain_attached: null info");
+        info->struct_bytes = sizeof(lig_explain_info);
+        check(lig_rows_explain_attached(trace_, constraints, n_asked, con_out, terms_out, term_cap, info), "lig_rows_explain_attached");
+    }
+    // the committed witness elements of `slots` (row * l + column over the committed rows of any kind: derived and mixed rows as the
+    // device holds them; any order, repeats allowed) -> values, n_slots x 32 canonical bytes (lig_rows_read_slots).  Window as explain().
+    void read_slots(const uint32_t* slots, uint64_t n_slots, uint8_t* values) {
+        if (sharded_) throw std::logic_error("hip_row_batcher::read_slots: not on a sharded batcher");
+        if (pass_ == 1 || !trace_) throw std::logic_error("hip_row_batcher::read_slots before commit");
+        check(lig_rows_read_slots(trace_, slots, n_slots, values), "lig_rows_read_slots");
+    }
     // the next proof with this batcher: staging and (for the same row kinds) every device buffer of the trace are kept
     void reset(const hip_proof_meta* meta = nullptr) {
         if (pass_ == 2) throw std::logic_error("hip_row_batcher::reset between commit and prove");

@@ -43,6 +43,7 @@ EXPORTS = [
     "lig_linear_prepare", "lig_linear_program_release", "lig_linear_program_bytes", "lig_rows_attach_linear", "lig_rows_verify_attach_linear",
     "lig_rows_set_linear_values", "lig_rows_verify_set_linear_values", "lig_linear_program_form",
     "lig_rows_diagnose", "lig_rows_diagnose_attached",
+    "lig_rows_explain", "lig_rows_explain_attached", "lig_rows_read_slots",
 ]
 
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
@@ -215,6 +216,19 @@ DIAG_LINEAR = np.dtype([("constraint", "<u4"), ("reserved", "<u4"), ("residual",
 DIAG_QUAD = np.dtype([("row_x", "<u4"), ("row_y", "<u4"), ("row_z", "<u4"), ("column", "<u4"), ("residual", "u1", (32,))])
 
 
+class ExplainInfo(C.Structure):
+    """lig_explain_info: n_terms_total covers every term of the asked constraints, n_terms_reported what fitted term_cap"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("reserved", C.c_uint32), ("n_terms_total", C.c_uint64), ("n_terms_reported", C.c_uint64),
+                ("ms_total", C.c_double)]
+
+
+# lig_explain_term (80 bytes) / lig_explain_constraint (88 bytes) as numpy records; coef, value, rhs, residual = 32 little-endian bytes, canonical
+EXPLAIN_TERM = np.dtype([("constraint", "<u4"), ("slot", "<u4"), ("coef_index", "<u4"), ("reserved", "<u4"), ("coef", "u1", (32,)),
+                         ("value", "u1", (32,))])
+EXPLAIN_CONSTRAINT = np.dtype([("constraint", "<u4"), ("reserved", "<u4"), ("n_terms", "<u8"), ("first_term", "<u8"), ("rhs", "u1", (32,)),
+                               ("residual", "u1", (32,))])
+
+
 class ProofInfo(C.Structure):
     _fields_ = [("root", C.c_uint8 * 32), ("stage1_seed", C.c_uint8 * 32), ("stage2_seed", C.c_uint8 * 32),
                 ("const_sum", C.c_uint8 * 32), ("rows", C.c_uint64), ("valid_code", C.c_int32),
@@ -365,6 +379,9 @@ def load_library():
     L.lig_rows_diagnose.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, u64, C.POINTER(DiagInfo)]
     L.lig_shard_rows_diagnose.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, u64, C.POINTER(DiagInfo)]
     L.lig_rows_diagnose_attached.argtypes = [vp, vp, u64, vp, u64, C.POINTER(DiagInfo)]
+    L.lig_rows_explain.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
+    L.lig_rows_explain_attached.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
+    L.lig_rows_read_slots.argtypes = [vp, vp, u64, vp]
     return L
 
 
@@ -1103,6 +1120,35 @@ class Context:
         self.check(self.L.lig_rows_diagnose_attached(trace, _hptr(lin) if lin_cap else None, lin_cap, _hptr(quad) if quad_cap else None, quad_cap,
                                                      C.byref(info)))
         return info, lin[:info.n_linear_reported], quad[:info.n_quad_reported]
+
+    def _rows_explain(self, call, head, constraints, term_cap):
+        info = ExplainInfo()
+        info.struct_bytes = C.sizeof(ExplainInfo)
+        asked = np.ascontiguousarray(constraints, dtype=np.uint32)
+        con, terms = np.zeros(len(asked), dtype=EXPLAIN_CONSTRAINT), np.zeros(term_cap, dtype=EXPLAIN_TERM)
+        self.check(call(*head, _hptr(asked) if len(asked) else None, len(asked), _hptr(con) if len(asked) else None,
+                        _hptr(terms) if term_cap else None, term_cap, C.byref(info)))
+        return info, con, terms[:info.n_terms_reported]
+
+    def rows_explain(self, trace, system, constraints, term_cap=4096):
+        """lig_rows_explain: the constraints `constraints` (numbers, strictly ascending) of `system` as the library holds them ->
+        (ExplainInfo, constraint records, term records): numpy record arrays (EXPLAIN_CONSTRAINT: n_terms, first_term, rhs, residual;
+        EXPLAIN_TERM: slot, coef_index, coefficient value, committed witness value), the first term_cap terms in ascending (constraint,
+        slot, coef_index) order; the counts cover all terms"""
+        return self._rows_explain(self.L.lig_rows_explain, (trace, C.byref(system) if system is not None else None), constraints, term_cap)
+
+    def rows_explain_attached(self, trace, constraints, term_cap=4096):
+        """lig_rows_explain_attached: rows_explain against the statement attached to the trace (rows_set_linear / rows_attach_linear, with
+        the values of rows_set_linear_values in force): no term list is passed -> the same triple as rows_explain"""
+        return self._rows_explain(self.L.lig_rows_explain_attached, (trace,), constraints, term_cap)
+
+    def rows_read_slots(self, trace, slots):
+        """lig_rows_read_slots: the committed witness elements of `slots` (row * l + column over the committed rows of any kind; any order,
+        repeats allowed) -> (n, 8) uint32 limbs, canonical"""
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        out = np.zeros((len(sl), 8), dtype=np.uint32)
+        self.check(self.L.lig_rows_read_slots(trace, _hptr(sl) if len(sl) else None, len(sl), _hptr(out) if len(sl) else None))
+        return out
 
     def shard_rows_diagnose(self, shard, system=None, lin_cap=1024, quad_cap=1024):
         """lig_shard_rows_diagnose: rows_diagnose on a rows shard.  Collective: every rank passes the same `system` (of the WHOLE trace) and

@@ -34,7 +34,9 @@
 // main stream only -- the side stream, the uploader and the copy stream may be carrying the prefetch of the next trace.  Freeing the
 // scratch (hipFree) waits for the whole device, though: with a prefetch in flight the call returns after that transfer (lig_hip.h says so).
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
+#include "explain_plan.hpp"
 #include "lin_common.hpp"
 #include "prover_common.hpp"
 
@@ -238,6 +240,106 @@ __global__ void __launch_bounds__(LIN_WG) k_diag_scatter_quad(const uint32_t* __
         out[pos[i]] = rec;
     }
 }
+
+// ---- lig_rows_explain / lig_rows_explain_attached: the asked constraints as the library holds them (terms, coefficient values, committed
+// witness values, b_c, residual), and lig_rows_read_slots.  A term before it is filled in is a 12-byte lig::ExplainItem {index in the
+// asked list, slot, coefficient index} (explain_plan.hpp).  Where the items come from is the only difference between the two entries:
+//   k_explain_mark     (attached) one lane per entry of the program: mark[e] = 1 + the position of its constraint in the asked list (binary
+//                      search over the ascending device copy), 0 when it is not asked
+//   (rocPRIM exclusive scan of mark != 0 -> pos, the total m)
+//   k_explain_collect  (attached) a marked entry writes its item at pos[e]; its slot by binary search over begin[] (diag_slot_of).  No atomic.
+//   k_explain_gather   (term list) one lane per output term: the asked segments of the uploaded constraint-major list, addressed through the
+//                      prefix sums of their lengths (host)
+// The host puts the m items into the output order (explain_order: a total order on the 12 bytes, so the bytes depend neither on the order
+// of the entries inside a slot's segment -- which prepare made the program -- nor on the sort) and uploads them again; then
+//   k_explain_fill     one lane per reported record: coefficient value (diag_coef_value), the 32-byte gather of w[slot], 16-byte stores
+//   k_explain_finish   one workgroup per asked constraint over its segment of the ordered items: diag_sum_block and the fixed tree, b_c as in
+//                      diag_finish; writes the whole 88-byte record
+//   k_read_slots       one lane per slot: gather, store
+// position of c in the ascending list asked[0 .. n), n when it is not there
+static __device__ __forceinline__ uint32_t explain_find(const uint32_t* __restrict__ asked, uint32_t n, uint32_t c) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (asked[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    return lo < n && asked[lo] == c ? lo : n;
+}
+struct ExplainMarked { __host__ __device__ uint32_t operator()(uint32_t mark) const { return mark ? 1u : 0u; } };
+__global__ void __launch_bounds__(LIN_WG) k_explain_mark(const uint2* __restrict__ ent, uint32_t n_terms, const uint32_t* __restrict__ asked, uint32_t n_asked,
+                                                         uint32_t* __restrict__ mark) {
+    for (uint64_t e = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; e < n_terms; e += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t a = explain_find(asked, n_asked, ent[e].x);
+        mark[e] = a < n_asked ? a + 1 : 0u;
+    }
+}
+// pos = the exclusive scan of mark != 0: the marked entries get the positions 0 .. m - 1 in entry order, items has m entries
+__global__ void __launch_bounds__(LIN_WG) k_explain_collect(const uint2* __restrict__ ent, uint32_t n_terms, const uint32_t* __restrict__ begin, uint32_t n_slots,
+                                                            const uint32_t* __restrict__ mark, const uint32_t* __restrict__ pos, ExplainItem* __restrict__ items) {
+    for (uint64_t e = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; e < n_terms; e += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t mk = mark[e];
+        if (!mk) continue;
+        ExplainItem it;
+        it.ask = mk - 1; it.slot = diag_slot_of(begin, n_slots, (uint32_t)e); it.coef = ent[e].y;
+        items[pos[e]] = it;
+    }
+}
+// pre[0 .. n_asked]: prefix sums of the asked constraints' term counts, pre[n_asked] = m; item i belongs to the a with pre[a] <= i < pre[a + 1]
+__global__ void __launch_bounds__(LIN_WG) k_explain_gather(const uint32_t* __restrict__ term_begin, const lig_lin_term* __restrict__ terms,
+                                                           const uint32_t* __restrict__ asked, uint32_t n_asked, const uint32_t* __restrict__ pre, uint32_t m,
+                                                           ExplainItem* __restrict__ items) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < m; i += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t a = diag_slot_of(pre, n_asked, (uint32_t)i);
+        const lig_lin_term tm = terms[term_begin[asked[a]] + ((uint32_t)i - pre[a])];
+        ExplainItem it;
+        it.ask = a; it.slot = tm.slot; it.coef = tm.coef;
+        items[i] = it;
+    }
+}
+static __device__ __forceinline__ fr diag_witness(uint32_t slot, const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip) {
+    const uint32_t row = diag_div(slot, l_recip);
+    return fr_load(msgs + (size_t)row * k + (slot - row * l));
+}
+// record i = the i-th item of the output order: terms[i] with ask[i]; out is 16-byte aligned and a record has 80 bytes
+__global__ void __launch_bounds__(LIN_WG) k_explain_fill(const lig_lin_term* __restrict__ terms, const uint32_t* __restrict__ ask, uint32_t n,
+                                                         const uint32_t* __restrict__ asked, const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip,
+                                                         const fr* __restrict__ coef_mont, lig_explain_term* __restrict__ out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG) {
+        const lig_lin_term tm = terms[i];
+        uint4* o = reinterpret_cast<uint4*>(out + i);
+        o[0] = make_uint4(asked[ask[i]], tm.slot, tm.coef, 0u);
+        fr_store(reinterpret_cast<fr*>(o + 1), diag_coef_value(tm.coef, coef_mont));
+        fr_store(reinterpret_cast<fr*>(o + 3), diag_witness(tm.slot, msgs, l, k, l_recip));
+    }
+}
+// workgroup -> asked constraint blockIdx.x + i * gridDim.x; first[0 .. n_asked]: its items are terms[first[a] .. first[a + 1]).  A record has 88
+// bytes: 8-byte stores.
+__global__ void __launch_bounds__(LIN_WG) k_explain_finish(const uint32_t* __restrict__ first, const lig_lin_term* __restrict__ terms, const uint32_t* __restrict__ asked,
+                                                           uint32_t n_asked, const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip,
+                                                           const fr* __restrict__ coef_mont, const uint32_t* __restrict__ rhs_index,
+                                                           const uint32_t* __restrict__ rhs_coef, lig_explain_constraint* __restrict__ out) {
+    __shared__ fr sh[LIN_WG];
+    for (uint32_t a = blockIdx.x; a < n_asked; a += gridDim.x) {          // (uniform over the workgroup, as in k_diag_lin_heavy)
+        const uint32_t b = first[a], e = first[a + 1];
+        const fr acc = diag_sum_block(b, e, terms, msgs, l, k, l_recip, coef_mont, DiagAllRows{}, sh);
+        if (threadIdx.x == 0) {
+            const uint32_t cn = asked[a], ri = rhs_index[cn];
+            const fr rhs = ri ? diag_coef_value(rhs_coef[ri - 1], coef_mont) : fr_zero();
+            const fr res = fr_sub(acc, rhs);
+            uint2* o = reinterpret_cast<uint2*>(out + a);
+            o[0] = make_uint2(cn, 0u);
+            o[1] = make_uint2(e - b, 0u);
+            o[2] = make_uint2(b, 0u);
+            for (int w = 0; w < 4; w++) { o[3 + w] = make_uint2(rhs.v[2 * w], rhs.v[2 * w + 1]); o[7 + w] = make_uint2(res.v[2 * w], res.v[2 * w + 1]); }
+        }
+        __syncthreads();                                                  // sh is reused by the next constraint
+    }
+}
+__global__ void __launch_bounds__(LIN_WG) k_read_slots(const uint32_t* __restrict__ slots, uint32_t n, const fr* __restrict__ msgs, uint32_t l, uint32_t k,
+                                                       uint64_t l_recip, fr* __restrict__ out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG)
+        fr_store(out + i, diag_witness(slots[i], msgs, l, k, l_recip));
+}
 }  // namespace lig
 
 namespace {
@@ -266,7 +368,8 @@ struct DiagScratch {
 };
 
 // flag[0 .. n] (flag[n] = 0) -> pos[0 .. n] = exclusive scan; *count = pos[n] = the number of set flags.  Blocks until it is known.
-int diag_scan(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, const uint32_t* flag, uint32_t* pos, size_t n, void** scan_tmp, size_t* scan_cap, uint32_t* count) {
+template <class Flags>      // const uint32_t*, or an iterator over them (the marks of k_explain_mark read as 0 / 1)
+int diag_scan(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, Flags flag, uint32_t* pos, size_t n, void** scan_tmp, size_t* scan_cap, uint32_t* count) {
     hipStream_t s = c->stream;
     size_t need = 0;
     HIP_TRY(c, rocprim::exclusive_scan(nullptr, need, flag, pos, 0u, n + 1, rocprim::plus<uint32_t>(), s));
@@ -476,6 +579,134 @@ int lig_internal_rows_diagnose_attached(lig_ctx* c, const fr* msgs, uint64_t row
     const lig_linear_view v = lig_internal_linear_view(att);
     if (v.sharded) FAIL(c, LIG_E_STATE, "lig_rows_diagnose_attached: the attached structure is one rank's share of a sharded trace");
     return diag_rows(c, msgs, rows, tri_dev, n_quad_terms, nullptr, &v, lin_out, lin_cap, quad_out, quad_cap, info);
+}
+
+namespace {
+// The two explain entries (lig_hip.h).  The statement is `sys` (it has passed lig_linear_check against the trace's kinds) or `att` (the view of
+// the trace's attachment, not sharded), exactly one of them; asked[0 .. n_asked) has passed explain_asked_ok against its constraint count and
+// n_asked > 0.  Where the unordered items come from is all that differs (the kernels' header above).  Blocks twice: for the items (ordered on
+// the host), and for the records.
+int explain_rows(lig_ctx* c, const fr* msgs, const lig_linear_system* sys, const lig_linear_view* att, const uint32_t* asked, uint64_t n_asked,
+                 lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info) {
+    hipStream_t s = c->stream;
+    const uint32_t l = c->l, k = c->k, NA = (uint32_t)n_asked;
+    const uint64_t l_recip = diag_reciprocal(l);
+    // (sources and targets of queued copies: declared before the scratch, whose destructor drains the stream)
+    std::vector<lig::ExplainItem> items;
+    std::vector<uint64_t> first;
+    std::vector<uint32_t> pre, first32, ask;
+    std::vector<lig_lin_term> ordered;
+    DiagScratch sc(c);
+    void* scan_tmp = nullptr; size_t scan_cap = 0;
+    const DiagWait wait = [c, s]() -> int { HIP_TRY(c, lig_internal_wait_stream(s)); return LIG_OK; };
+
+    uint32_t* d_asked = nullptr; lig::ExplainItem* d_items = nullptr;
+    TRY(sc.alloc((void**)&d_asked, (size_t)NA * 4));
+    HIP_TRY(c, hipMemcpyAsync(d_asked, asked, (size_t)NA * 4, hipMemcpyHostToDevice, s));
+    DiagSystem d;
+    uint32_t m = 0;
+    if (sys) {
+        TRY(diag_upload_system(c, sc, sys, d));
+        pre.assign((size_t)NA + 1, 0);
+        for (uint32_t a = 0; a < NA; a++) pre[a + 1] = pre[a] + (sys->term_begin[asked[a] + 1] - sys->term_begin[asked[a]]);      // <= n_terms < 2^32: the asked are distinct
+        m = pre[NA];
+        uint32_t* d_pre = nullptr;
+        TRY(sc.alloc((void**)&d_pre, ((size_t)NA + 1) * 4));
+        TRY(sc.alloc((void**)&d_items, (size_t)m * sizeof(lig::ExplainItem)));
+        HIP_TRY(c, hipMemcpyAsync(d_pre, pre.data(), ((size_t)NA + 1) * 4, hipMemcpyHostToDevice, s));
+        if (m) hipLaunchKernelGGL(lig::k_explain_gather, dim3(diag_grid(m)), dim3(lig::LIN_WG), 0, s, d.tb, d.terms, d_asked, NA, d_pre, m, d_items);
+        HIP_TRY(c, hipGetLastError());
+    } else {
+        const lig_linear_view& v = *att;
+        const uint32_t NC = d.NC = (uint32_t)v.n_constraints, NT = (uint32_t)v.n_terms, NR = (uint32_t)v.n_rhs;
+        uint32_t *d_mark = nullptr, *d_pos = nullptr;
+        TRY(sc.alloc((void**)&d_mark, ((size_t)NT + 1) * 4));
+        TRY(sc.alloc((void**)&d_pos, ((size_t)NT + 1) * 4));
+        TRY(sc.alloc((void**)&d.rhs_index, (size_t)NC * 4));
+        d.rhs_coef = v.rhs_coef; d.coef = v.coef;
+        // values set on the side stream (lig_rows_set_linear_values): the table is read once its conversion has finished
+        if (v.coef_ready) HIP_TRY(c, hipStreamWaitEvent(s, v.coef_ready, 0));
+        HIP_TRY(c, hipMemsetAsync(d_mark + NT, 0, 4, s));
+        if (NT) hipLaunchKernelGGL(lig::k_explain_mark, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, d_asked, NA, d_mark);
+        HIP_TRY(c, hipGetLastError());
+        TRY(diag_scan(c, sc, wait, rocprim::make_transform_iterator((const uint32_t*)d_mark, lig::ExplainMarked{}), d_pos, NT, &scan_tmp, &scan_cap, &m));
+        if (m > NT) FAIL(c, LIG_E_STATE, "lig_rows_explain_attached: counted more asked terms than the attached program holds");
+        TRY(sc.alloc((void**)&d_items, (size_t)m * sizeof(lig::ExplainItem)));
+        if (m) hipLaunchKernelGGL(lig::k_explain_collect, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, v.begin, v.n_slots, d_mark, d_pos, d_items);
+        HIP_TRY(c, hipMemsetAsync(d.rhs_index, 0, (size_t)NC * 4, s));
+        if (NR) hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, v.rhs_c, NR, d.rhs_index);
+        HIP_TRY(c, hipGetLastError());
+    }
+    // the m items -> the output order, on the host (explain_plan.hpp)
+    items.resize(m);
+    if (m) HIP_TRY(c, hipMemcpyAsync(items.data(), d_items, (size_t)m * sizeof(lig::ExplainItem), hipMemcpyDeviceToHost, s));
+    TRY(wait());
+    if (!lig::explain_order(items, NA, first)) FAIL(c, LIG_E_STATE, "lig_rows_explain: a collected term names no asked constraint");
+    const uint32_t rep = (uint32_t)std::min<uint64_t>(m, term_cap);
+    ordered.resize(m);
+    ask.resize(rep);
+    first32.assign(first.begin(), first.end());
+    for (uint32_t i = 0; i < m; i++) { ordered[i].slot = items[i].slot; ordered[i].coef = items[i].coef; }
+    for (uint32_t i = 0; i < rep; i++) ask[i] = items[i].ask;
+    lig_lin_term* d_ordered = nullptr; uint32_t *d_ask = nullptr, *d_first = nullptr;
+    lig_explain_constraint* d_con = nullptr; lig_explain_term* d_out = nullptr;
+    TRY(sc.alloc((void**)&d_ordered, (size_t)m * sizeof(lig_lin_term)));
+    TRY(sc.alloc((void**)&d_ask, (size_t)rep * 4));
+    TRY(sc.alloc((void**)&d_first, ((size_t)NA + 1) * 4));
+    TRY(sc.alloc((void**)&d_con, (size_t)NA * sizeof(lig_explain_constraint)));
+    TRY(sc.alloc((void**)&d_out, (size_t)rep * sizeof(lig_explain_term)));
+    if (m) HIP_TRY(c, hipMemcpyAsync(d_ordered, ordered.data(), (size_t)m * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
+    if (rep) HIP_TRY(c, hipMemcpyAsync(d_ask, ask.data(), (size_t)rep * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d_first, first32.data(), ((size_t)NA + 1) * 4, hipMemcpyHostToDevice, s));
+    if (rep) hipLaunchKernelGGL(lig::k_explain_fill, dim3(diag_grid(rep)), dim3(lig::LIN_WG), 0, s, d_ordered, d_ask, rep, d_asked, msgs, l, k, l_recip, d.coef, d_out);
+    hipLaunchKernelGGL(lig::k_explain_finish, dim3(std::min<uint32_t>(NA, lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d_first, d_ordered, d_asked, NA, msgs, l, k,
+                       l_recip, d.coef, d.rhs_index, d.rhs_coef, d_con);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(con_out, d_con, (size_t)NA * sizeof(lig_explain_constraint), hipMemcpyDeviceToHost, s));
+    if (rep) HIP_TRY(c, hipMemcpyAsync(terms_out, d_out, (size_t)rep * sizeof(lig_explain_term), hipMemcpyDeviceToHost, s));
+    TRY(wait());
+    info->n_terms_total = m;
+    info->n_terms_reported = rep;
+    return LIG_OK;
+}
+}  // namespace
+
+int lig_internal_rows_explain(lig_ctx* c, const fr* msgs, const lig_linear_system* sys, const uint32_t* asked, uint64_t n_asked, lig_explain_constraint* con_out,
+                              lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info) {
+    if (!lig::explain_asked_ok(asked, n_asked, sys->n_constraints))
+        FAIL(c, LIG_E_ARG, "lig_rows_explain: the asked constraints must be strictly ascending and below n_constraints");
+    if (!n_asked) return LIG_OK;
+    return explain_rows(c, msgs, sys, nullptr, asked, n_asked, con_out, terms_out, term_cap, info);
+}
+int lig_internal_rows_explain_attached(lig_ctx* c, const fr* msgs, const lig_linear* att, const uint32_t* asked, uint64_t n_asked, lig_explain_constraint* con_out,
+                                       lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info) {
+    const lig_linear_view v = lig_internal_linear_view(att);
+    if (v.sharded) FAIL(c, LIG_E_STATE, "lig_rows_explain_attached: the attached structure is one rank's share of a sharded trace");
+    if (!lig::explain_asked_ok(asked, n_asked, v.n_constraints))
+        FAIL(c, LIG_E_ARG, "lig_rows_explain_attached: the asked constraints must be strictly ascending and below n_constraints");
+    if (!n_asked) return LIG_OK;
+    return explain_rows(c, msgs, nullptr, &v, asked, n_asked, con_out, terms_out, term_cap, info);
+}
+// lig_rows_read_slots: values[i] = the canonical w[slots[i]] of the committed rows x k matrix; every slot < rows * l (checked here, before
+// anything is launched).  In pieces of 2^24 slots.
+int lig_internal_rows_read_slots(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* slots, uint64_t n_slots, uint8_t* values) {
+    if (!lig::explain_slots_ok(slots, n_slots, rows, c->l)) FAIL(c, LIG_E_ARG, "lig_rows_read_slots: a slot is not below rows * l");
+    if (!n_slots) return LIG_OK;
+    hipStream_t s = c->stream;
+    const uint64_t l_recip = diag_reciprocal(c->l), piece = std::min<uint64_t>(n_slots, 1ull << 24);
+    DiagScratch sc(c);
+    uint32_t* d_slots = nullptr; fr* d_val = nullptr;
+    TRY(sc.alloc((void**)&d_slots, (size_t)piece * 4));
+    TRY(sc.alloc((void**)&d_val, (size_t)piece * 32));
+    for (uint64_t at = 0; at < n_slots; at += piece) {
+        const uint32_t n = (uint32_t)std::min(piece, n_slots - at);
+        HIP_TRY(c, hipMemcpyAsync(d_slots, slots + at, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(lig::k_read_slots, dim3(diag_grid(n)), dim3(lig::LIN_WG), 0, s, d_slots, n, msgs, c->l, c->k, l_recip, d_val);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(values + at * 32, d_val, (size_t)n * 32, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, lig_internal_wait_stream(s));
+    }
+    return LIG_OK;
 }
 
 // One rank of a sharded rows job (lig_shard_rows_diagnose, lig_hip.h; v: prover_common.hpp).  Collective: whether a collective is issued,

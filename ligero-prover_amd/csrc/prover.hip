@@ -1088,6 +1088,47 @@ int lig_rows_diagnose_attached(lig_trace* T, lig_diag_linear* lin_out, uint64_t 
     return LIG_OK;
 }
 
+// the asked constraints as the library holds them: terms, coefficient values, committed witness values, b_c, residual (diagnose.hip); the
+// window, blocking and streams of lig_rows_diagnose.  which: the C name, for the messages; att: the attached statement instead of sys
+static int rows_explain(const char* which, bool att, lig_trace* T, const lig_linear_system* sys, const uint32_t* asked, uint64_t n_asked,
+                        lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info) {
+    if (!T || !info || info->struct_bytes < sizeof(lig_explain_info)) return LIG_E_ARG;
+    if ((n_asked && (!con_out || !asked)) || (term_cap && !terms_out)) return LIG_E_ARG;
+    const auto t_begin = clk::now();
+    lig_ctx* c = T->c;
+    CHECK_CTX(c);
+    const std::string w(which);
+    if (!T->from_rows) FAIL(c, LIG_E_STATE, w + ": not a rows trace");
+    if (!T->diag_ok) FAIL(c, LIG_E_STATE, w + ": no committed matrix (between lig_rows_commit and the next commit, or a lig_rows_restart after lig_rows_prove)");
+    if (att && !T->linear) FAIL(c, LIG_E_STATE, w + ": nothing is attached (lig_rows_set_linear, lig_rows_attach_linear)");
+    if (!att && !sys) FAIL(c, LIG_E_ARG, w + ": null linear system");
+    if (!att && lig_linear_check(sys, kinds_of(T->rows).data(), T->R, c->l) != LIG_OK) FAIL(c, LIG_E_ARG, w + ": linear system rejected by lig_linear_check");
+    const uint32_t struct_bytes = info->struct_bytes;
+    std::memset(info, 0, sizeof *info);
+    info->struct_bytes = struct_bytes;
+    if (att) TRY(lig_internal_rows_explain_attached(c, T->msgs, T->linear, asked, n_asked, con_out, terms_out, term_cap, info));
+    else TRY(lig_internal_rows_explain(c, T->msgs, sys, asked, n_asked, con_out, terms_out, term_cap, info));
+    info->ms_total = ms_since(t_begin);
+    return LIG_OK;
+}
+int lig_rows_explain(lig_trace* T, const lig_linear_system* sys, const uint32_t* constraints, uint64_t n_asked, lig_explain_constraint* con_out,
+                     lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info) {
+    return rows_explain("lig_rows_explain", false, T, sys, constraints, n_asked, con_out, terms_out, term_cap, info);
+}
+int lig_rows_explain_attached(lig_trace* T, const uint32_t* constraints, uint64_t n_asked, lig_explain_constraint* con_out, lig_explain_term* terms_out,
+                              uint64_t term_cap, lig_explain_info* info) {
+    return rows_explain("lig_rows_explain_attached", true, T, nullptr, constraints, n_asked, con_out, terms_out, term_cap, info);
+}
+// the committed w[slot] of any row kind, canonical (diagnose.hip); the window, blocking and streams of lig_rows_diagnose
+int lig_rows_read_slots(lig_trace* T, const uint32_t* slots, uint64_t n_slots, uint8_t* values) {
+    if (!T || (n_slots && (!slots || !values))) return LIG_E_ARG;
+    lig_ctx* c = T->c;
+    CHECK_CTX(c);
+    if (!T->from_rows) FAIL(c, LIG_E_STATE, "lig_rows_read_slots: not a rows trace");
+    if (!T->diag_ok) FAIL(c, LIG_E_STATE, "lig_rows_read_slots: no committed matrix (between lig_rows_commit and the next commit, or a lig_rows_restart after lig_rows_prove)");
+    return lig_internal_rows_read_slots(c, T->msgs, T->R, slots, n_slots, values);
+}
+
 int lig_rows_push_rands(lig_trace* T, uint64_t first_row, uint64_t n_rows, const void* host_rows) {
     return lig_rows_push_rands_sparse(T, first_row, n_rows, nullptr, host_rows);
 }

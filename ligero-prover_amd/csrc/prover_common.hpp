@@ -476,6 +476,14 @@ int lig_internal_rows_diagnose(lig_ctx* c, const fr* msgs, uint64_t rows, const 
 // lig_rows_diagnose_attached: the same passes over the statement ATTACHED to the trace (`att`: not sharded), regrouped by constraint on the device
 int lig_internal_rows_diagnose_attached(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* tri_dev, uint64_t n_quad_terms, const lig_linear* att,
                                         lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info);
+// lig_rows_explain / lig_rows_explain_attached / lig_rows_read_slots (diagnose.hip): the asked constraints of `sys` (it has passed
+// lig_linear_check) or of the statement attached (`att`: not sharded) as records over the committed matrix; the asked list and the slots are
+// checked here, on the host, before anything is launched (LIG_E_ARG).  Blocking, main stream only, scratch per call.
+int lig_internal_rows_explain(lig_ctx* c, const fr* msgs, const lig_linear_system* sys, const uint32_t* asked, uint64_t n_asked, lig_explain_constraint* con_out,
+                              lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info);
+int lig_internal_rows_explain_attached(lig_ctx* c, const fr* msgs, const lig_linear* att, const uint32_t* asked, uint64_t n_asked, lig_explain_constraint* con_out,
+                                       lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info);
+int lig_internal_rows_read_slots(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* slots, uint64_t n_slots, uint8_t* values);
 hipError_t lig_internal_wait_stream(hipStream_t st);
 // lig_shard_rows_diagnose (diagnose.hip): what one rank of a sharded rows job holds, and the shard's collectives and waits (shard.hip).
 // all_to_all / all_gather run on the context's main stream (stream-ordered forms) or after it has drained (host-synchronous callbacks);
