@@ -572,8 +572,8 @@ int lig_rows_diagnose_attached(lig_trace *trace, lig_diag_linear *lin_out, uint6
  * records.  LIG_E_ARG: a NULL trace, a NULL or too small *info, con_out == NULL or constraints == NULL with n_asked > 0, terms_out ==
  * NULL with term_cap > 0, slots or values == NULL with n_slots > 0, and the range errors above -- all decided on the host before
  * anything is launched: an index out of range never reaches a kernel.
- * Not covered: the sharded entry (a rank's structure is local and compactly numbered: lig_shard_rows_diagnose names the constraints,
- * the term list is the caller's), and a verifier side (the verifier has no witness). */
+ * The sharded entry has its own calls, lig_shard_rows_explain / lig_shard_rows_read_slots below.  Not covered: a verifier side (the
+ * verifier has no witness). */
 typedef struct { uint32_t constraint, slot, coef_index, reserved; uint8_t coef[32]; uint8_t value[32]; } lig_explain_term;       /* 80 bytes */
 typedef struct { uint32_t constraint, reserved; uint64_t n_terms, first_term; uint8_t rhs[32]; uint8_t residual[32]; } lig_explain_constraint; /* 88 bytes */
 typedef struct {
@@ -736,6 +736,46 @@ int lig_linear_shard_count(const lig_linear_system *sys, const uint8_t *kinds, u
  * Not done: skipping the exchange for constraints whose terms all lie on one rank (it would make the schedule depend on the data). */
 int lig_shard_rows_diagnose(lig_shard *shard, const lig_linear_system *sys, lig_diag_linear *lin_out, uint64_t lin_cap,
                             lig_diag_quad *quad_out, uint64_t quad_cap, lig_diag_info *info);
+
+/* lig_rows_explain / lig_rows_read_slots on a rows shard (csrc/diagnose.hip, csrc/shard.hip).  lig_shard_rows_diagnose hands every rank
+ * a constraint number and 32 residual bytes; a constraint may span ranks and no process holds the witness: the value of a term on a
+ * derived QZ row or on a record slot of a mixed row exists only on the device of the rank that was dealt that row.
+ * COLLECTIVE: every rank passes the same `sys` (the term list of the WHOLE trace with global slots, exactly what
+ * lig_shard_rows_diagnose takes), the same asked list, the same term_cap, the same `slots`.  Slots are global: row * l + column over
+ * the committed rows of the whole trace, of any kind.  EVERY RANK RECEIVES THE SAME BYTES, and they are the bytes of
+ * lig_rows_explain(trace, sys, ...) / lig_rows_read_slots(trace, ...) on a one-GPU trace of the same rows: order, first_term, n_terms,
+ * rhs, residual, coefficient values, value, reserved fields zero, info->n_terms_total and n_terms_reported.  info->ms_total is the
+ * rank's own.
+ * WHEN: the window of lig_shard_rows_diagnose -- from the return of lig_shard_rows_commit until the next lig_shard_rows_restart, before
+ * or after lig_shard_rows_prove; LIG_E_STATE outside it, for a shard not made by lig_shard_rows_begin, for a poisoned shard.  Nothing a
+ * proof depends on is written: the envelope of a shard that was explained or read is byte-identical to that of one that was not.
+ * REFUSALS happen on the host, before any launch and any collective, and are decided identically on every rank, so a refused call
+ * leaves the shard usable and no peer waiting.  LIG_E_ARG: sys == NULL or a sys lig_linear_check rejects; an asked list that is not
+ * strictly ascending or names a constraint >= n_constraints; a slot >= rows * l of the whole trace; a NULL array with a non-zero
+ * count (constraints, con_out with n_asked > 0; terms_out with term_cap > 0; slots, values with n_slots > 0); a NULL or short *info.
+ * n_asked == 0 or n_slots == 0: LIG_OK, no launch, no collective.
+ * world == 1 without LIG_SHARD_FORCE_EXCHANGE: no collective, the call is lig_rows_explain / lig_rows_read_slots on the rank's matrix;
+ * with the knob set the exchange path runs with one rank.
+ * HOW: the asked segments are on the host of every rank already: the m = sum of n_terms items are formed and put into the output order
+ * there (no gather kernel, no copy back, and the system is NOT uploaded: only the m ordered terms, first_term[], the asked list, one
+ * right-hand-side coefficient index per asked constraint and the coefficient table).  The values cross the ranks in pieces of
+ * P = min(m, LIG_DIAG_SLICE) terms (the last piece ragged): a rank writes the canonical w of the terms whose row it holds and zero for
+ * the others (a rank without rows: zeros), ONE all-gather of 32 P bytes per rank and piece (the tail of the last piece zeroed: the size is
+ * fixed), and every rank adds the W received values -- a row has one owner, so exactly one summand is non-zero and the sum is exact and
+ * independent of rank order.  The records are then filled and the residuals summed by the kernels of lig_rows_explain over the value
+ * list (fixed tree, one workgroup per asked constraint, whatever its length).  con_out is complete whatever term_cap is, so all m values
+ * are exchanged.  lig_shard_rows_read_slots runs the same exchange over the slot list in pieces of min(n_slots, LIG_DIAG_SLICE).
+ * Whether a collective is issued, how many and of which size depends on m (or n_slots), world and the piece size alone -- never on
+ * which rows a rank holds.  FAILURE of a peer or of the communicator: as lig_shard_rows_diagnose.
+ * SCRATCH is allocated inside the call and freed before it returns (lig_comm.forget runs first; every send buffer is an allocation of
+ * its own); the work runs on the context's main stream.  explain: 32 P (send) + 32 W P (receive) + 32 m (values) + 8 m (ordered
+ * terms) + 32 n_coefs + 16 n_asked + 4 bytes per row of the trace, and the records, 88 n_asked + 84 min(m, term_cap); read_slots:
+ * 68 P + 32 W P + 4 bytes per row of the trace.
+ * Not done: an attached variant (a rank's attached structure is local and compactly numbered: the term list is the caller's); an
+ * all-to-all, reduce and all-gather instead of the all-gather, which would halve the bytes (the calls are for short lists). */
+int lig_shard_rows_explain(lig_shard *shard, const lig_linear_system *sys, const uint32_t *constraints, uint64_t n_asked,
+                           lig_explain_constraint *con_out, lig_explain_term *terms_out, uint64_t term_cap, lig_explain_info *info);
+int lig_shard_rows_read_slots(lig_shard *shard, const uint32_t *slots, uint64_t n_slots, uint8_t *values /* n_slots x 32 */);
 
 /* sizeof of the public structs as this build of the library sees them, in the order {lig_batch_op, lig_synth_job, lig_proof_info,
  * lig_verify_info, lig_rows_job, lig_comm}: a binding in another language (ctypes, cgo, JNI) checks its own layouts against these at

@@ -347,16 +347,21 @@ public:
     // batcher with a prepared program or without a system has no term list: std::logic_error (explain_attached()).
     // explain_attached(): the statement attached to the trace, as diagnose_attached(): no term list is needed.
     // Both after commit(), before or after prove(), until the next commit(); the same bytes for the same statement.  std::logic_error
-    // before commit() and with shard_over() (a rank's structure is local and compactly numbered).
+    // before commit().  With shard_over(): explain() is lig_shard_rows_explain, a COLLECTIVE call -- every rank calls it with the same
+    // asked list and term_cap and gets the records of the unsharded batcher, whichever rank holds the rows of a term; explain_attached()
+    // stays std::logic_error there (a rank's attached structure is local and compactly numbered).
     void explain(const uint32_t* constraints, uint64_t n_asked, lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap,
                  lig_explain_info* info) {
-        if (sharded_) throw std::logic_error("hip_row_batcher::explain: not on a sharded batcher");
-        if (pass_ == 1 || !trace_) throw std::logic_error("hip_row_batcher::explain before commit");
+        if (pass_ == 1 || !(sharded_ ? (bool)shard_ : (bool)trace_)) throw std::logic_error("hip_row_batcher::explain before commit");
         if (!linear_.is_set()) throw std::logic_error("hip_row_batcher::explain without a linear system (explain_attached)");
         if (!info) throw std::invalid_argument("hip_row_batcher::explain: null info");
         lig_linear_system sys = *linear_.get();
         if (values_set_) { sys.coefs = values_.data(); sys.n_coefs = values_.size() / 32; }
         info->struct_bytes = sizeof(lig_explain_info);
+        if (sharded_) {
+            check(lig_shard_rows_explain(shard_, &sys, constraints, n_asked, con_out, terms_out, term_cap, info), "lig_shard_rows_explain");
+            return;
+        }
         check(lig_rows_explain(trace_, &sys, constraints, n_asked, con_out, terms_out, term_cap, info), "lig_rows_explain");
     }
     void explain_attached(const uint32_t* constraints, uint64_t n_asked, lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap,
@@ -370,9 +375,13 @@ public:
     }
     // the committed witness elements of `slots` (row * l + column over the committed rows of any kind: derived and mixed rows as the
     // device holds them; any order, repeats allowed) -> values, n_slots x 32 canonical bytes (lig_rows_read_slots).  Window as explain().
+    // With shard_over(): lig_shard_rows_read_slots, COLLECTIVE -- the slots are those of the whole trace, every rank passes the same list.
     void read_slots(const uint32_t* slots, uint64_t n_slots, uint8_t* values) {
-        if (sharded_) throw std::logic_error("hip_row_batcher::read_slots: not on a sharded batcher");
-        if (pass_ == 1 || !trace_) throw std::logic_error("hip_row_batcher::read_slots before commit");
+        if (pass_ == 1 || !(sharded_ ? (bool)shard_ : (bool)trace_)) throw std::logic_error("hip_row_batcher::read_slots before commit");
+        if (sharded_) {
+            check(lig_shard_rows_read_slots(shard_, slots, n_slots, values), "lig_shard_rows_read_slots");
+            return;
+        }
         check(lig_rows_read_slots(trace_, slots, n_slots, values), "lig_rows_read_slots");
     }
     // the next proof with this batcher: staging and (for the same row kinds) every device buffer of the trace are kept

@@ -44,6 +44,7 @@ EXPORTS = [
     "lig_rows_set_linear_values", "lig_rows_verify_set_linear_values", "lig_linear_program_form",
     "lig_rows_diagnose", "lig_rows_diagnose_attached",
     "lig_rows_explain", "lig_rows_explain_attached", "lig_rows_read_slots",
+    "lig_shard_rows_explain", "lig_shard_rows_read_slots",
 ]
 
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
@@ -382,6 +383,8 @@ def load_library():
     L.lig_rows_explain.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
     L.lig_rows_explain_attached.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
     L.lig_rows_read_slots.argtypes = [vp, vp, u64, vp]
+    L.lig_shard_rows_explain.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
+    L.lig_shard_rows_read_slots.argtypes = [vp, vp, u64, vp]
     return L
 
 
@@ -1159,6 +1162,19 @@ class Context:
         self.check(self.L.lig_shard_rows_diagnose(shard, C.byref(system) if system is not None else None, _hptr(lin) if lin_cap else None, lin_cap,
                                                   _hptr(quad) if quad_cap else None, quad_cap, C.byref(info)))
         return info, lin[:info.n_linear_reported], quad[:info.n_quad_reported]
+
+    def shard_rows_explain(self, shard, system, constraints, term_cap=4096):
+        """lig_shard_rows_explain: rows_explain on a rows shard.  Collective: every rank passes the same `system` (of the WHOLE trace, global
+        slots), the same constraints and the same term_cap, and every rank gets the triple rows_explain gives for the whole trace on one GPU"""
+        return self._rows_explain(self.L.lig_shard_rows_explain, (shard, C.byref(system) if system is not None else None), constraints, term_cap)
+
+    def shard_rows_read_slots(self, shard, slots):
+        """lig_shard_rows_read_slots: rows_read_slots on a rows shard.  Collective: every rank passes the same global slots (row * l + column
+        over the rows of the WHOLE trace) and gets the same (n, 8) uint32 limbs, whichever rank holds the rows"""
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        out = np.zeros((len(sl), 8), dtype=np.uint32)
+        self.check(self.L.lig_shard_rows_read_slots(shard, _hptr(sl) if len(sl) else None, len(sl), _hptr(out) if len(sl) else None))
+        return out
 
     def vtrace_destroy(self, vtrace):
         """give up a verification between begin and finish (finish frees the trace itself)"""

@@ -12,6 +12,7 @@
 //                      table: a * w of the terms whose row the rank holds, the others skipped; a canonical PARTIAL per constraint, no b_c, no flag
 //   k_diag_reduce      the owner of a sub-block of the slice adds the W partials it received, subtracts b_c, writes residual and flag
 // (exact arithmetic mod p: no result depends on an order).
+// lig_rows_explain* / lig_rows_read_slots and their sharded counterparts (k_explain_*, k_read_slots) have a header of their own below.
 // Where the constraint-major list comes from is the only difference between the two one-GPU entries:
 //   lig_rows_diagnose            the caller's lig_linear_system, uploaded, with a scratch copy of its table in Montgomery form
 //   lig_rows_diagnose_attached   the statement ATTACHED to the trace.  Its program keeps the terms slot-major (linear.hip: begin[], ent[] =
@@ -56,16 +57,19 @@ static __device__ __forceinline__ fr diag_one() {
 // (LIN_NOT_LOCAL: another rank holds that row)
 struct DiagAllRows { __device__ __forceinline__ uint32_t operator()(uint32_t row) const { return row; } };
 struct DiagLocalRows { const uint32_t* __restrict__ local_of; __device__ __forceinline__ uint32_t operator()(uint32_t row) const { return local_of[row]; } };
+// acc (canonical) += a * w for the coefficient index `coef` and the canonical witness value w
+static __device__ __forceinline__ fr diag_apply(const fr& acc, uint32_t coef, const fr& w, const fr* __restrict__ coef_mont) {
+    if (coef == LIG_COEF_ONE) return fr_add(acc, w);
+    if (coef == LIG_COEF_NEG_ONE) return fr_sub(acc, w);
+    return fr_add(acc, fr_montmul(w, fr_load(coef_mont + coef)));         // w * (a R) / R = a * w, canonical
+}
 // acc (canonical) += coef * w[slot] for one term (unchanged for a term whose row is not in `msgs`)
 template <class Rows>
 static __device__ __forceinline__ fr diag_accumulate(const fr& acc, const lig_lin_term tm, const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip,
                                                      const fr* __restrict__ coef_mont, const Rows rows) {
     const uint32_t grow = diag_div(tm.slot, l_recip), col = tm.slot - grow * l, row = rows(grow);
     if (row == LIN_NOT_LOCAL) return acc;
-    const fr w = fr_load(msgs + (size_t)row * k + col);
-    if (tm.coef == LIG_COEF_ONE) return fr_add(acc, w);
-    if (tm.coef == LIG_COEF_NEG_ONE) return fr_sub(acc, w);
-    return fr_add(acc, fr_montmul(w, fr_load(coef_mont + tm.coef)));      // w * (a R) / R = a * w, canonical
+    return diag_apply(acc, tm.coef, fr_load(msgs + (size_t)row * k + col), coef_mont);
 }
 // the canonical value a coefficient index stands for
 static __device__ __forceinline__ fr diag_coef_value(uint32_t coef, const fr* __restrict__ coef_mont) {
@@ -253,9 +257,12 @@ __global__ void __launch_bounds__(LIN_WG) k_diag_scatter_quad(const uint32_t* __
 // The host puts the m items into the output order (explain_order: a total order on the 12 bytes, so the bytes depend neither on the order
 // of the entries inside a slot's segment -- which prepare made the program -- nor on the sort) and uploads them again; then
 //   k_explain_fill     one lane per reported record: coefficient value (diag_coef_value), the 32-byte gather of w[slot], 16-byte stores
-//   k_explain_finish   one workgroup per asked constraint over its segment of the ordered items: diag_sum_block and the fixed tree, b_c as in
+//   k_explain_finish   one workgroup per asked constraint over its segment of the ordered items: the lanes stride it, the fixed tree, b_c as in
 //                      diag_finish; writes the whole 88-byte record
 //   k_read_slots       one lane per slot: gather, store
+// On a rank of a sharded rows job (lig_shard_rows_explain / lig_shard_rows_read_slots) the items are formed and ordered on the host from the
+// caller's term list (explain_items_of), the values cross the ranks in pieces (k_explain_part, one all-gather, k_explain_sum), and the same
+// fill and finish run over the value list instead of the matrix (their witness source is a template parameter).
 // position of c in the ascending list asked[0 .. n), n when it is not there
 static __device__ __forceinline__ uint32_t explain_find(const uint32_t* __restrict__ asked, uint32_t n, uint32_t c) {
     uint32_t lo = 0, hi = n;
@@ -300,30 +307,50 @@ static __device__ __forceinline__ fr diag_witness(uint32_t slot, const fr* __res
     const uint32_t row = diag_div(slot, l_recip);
     return fr_load(msgs + (size_t)row * k + (slot - row * l));
 }
+// Where k_explain_fill / k_explain_finish take the committed w of the term at position t of the ordered list from, and how they find b_c:
+//   ExplainFromMatrix   the rows x k matrix (one GPU): w[slot]; rhs_index is indexed by the constraint number (k_diag_rhs_index)
+//   ExplainFromValues   vals[t], the values the ranks of a shard exchanged (k_explain_part, k_explain_sum: no rank holds every row);
+//                       rhs_index is indexed by the position in the asked list (made on the host: only the asked constraints are uploaded)
+struct ExplainFromMatrix {
+    static constexpr bool rhs_by_asked = false;
+    const fr* __restrict__ msgs; uint32_t l, k; uint64_t l_recip;
+    __device__ __forceinline__ fr operator()(uint32_t, uint32_t slot) const { return diag_witness(slot, msgs, l, k, l_recip); }
+};
+struct ExplainFromValues {
+    static constexpr bool rhs_by_asked = true;
+    const fr* __restrict__ vals;
+    __device__ __forceinline__ fr operator()(uint32_t t, uint32_t) const { return fr_load(vals + t); }
+};
 // record i = the i-th item of the output order: terms[i] with ask[i]; out is 16-byte aligned and a record has 80 bytes
+template <class Wit>
 __global__ void __launch_bounds__(LIN_WG) k_explain_fill(const lig_lin_term* __restrict__ terms, const uint32_t* __restrict__ ask, uint32_t n,
-                                                         const uint32_t* __restrict__ asked, const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip,
-                                                         const fr* __restrict__ coef_mont, lig_explain_term* __restrict__ out) {
+                                                         const uint32_t* __restrict__ asked, const Wit wit, const fr* __restrict__ coef_mont,
+                                                         lig_explain_term* __restrict__ out) {
     for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG) {
         const lig_lin_term tm = terms[i];
         uint4* o = reinterpret_cast<uint4*>(out + i);
         o[0] = make_uint4(asked[ask[i]], tm.slot, tm.coef, 0u);
         fr_store(reinterpret_cast<fr*>(o + 1), diag_coef_value(tm.coef, coef_mont));
-        fr_store(reinterpret_cast<fr*>(o + 3), diag_witness(tm.slot, msgs, l, k, l_recip));
+        fr_store(reinterpret_cast<fr*>(o + 3), wit((uint32_t)i, tm.slot));
     }
 }
-// workgroup -> asked constraint blockIdx.x + i * gridDim.x; first[0 .. n_asked]: its items are terms[first[a] .. first[a + 1]).  A record has 88
-// bytes: 8-byte stores.
+// workgroup -> asked constraint blockIdx.x + i * gridDim.x; first[0 .. n_asked]: its items are terms[first[a] .. first[a + 1]): the lanes stride
+// the segment, then the fixed tree (as diag_sum_block).  A record has 88 bytes: 8-byte stores.
+template <class Wit>
 __global__ void __launch_bounds__(LIN_WG) k_explain_finish(const uint32_t* __restrict__ first, const lig_lin_term* __restrict__ terms, const uint32_t* __restrict__ asked,
-                                                           uint32_t n_asked, const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip,
-                                                           const fr* __restrict__ coef_mont, const uint32_t* __restrict__ rhs_index,
+                                                           uint32_t n_asked, const Wit wit, const fr* __restrict__ coef_mont, const uint32_t* __restrict__ rhs_index,
                                                            const uint32_t* __restrict__ rhs_coef, lig_explain_constraint* __restrict__ out) {
     __shared__ fr sh[LIN_WG];
     for (uint32_t a = blockIdx.x; a < n_asked; a += gridDim.x) {          // (uniform over the workgroup, as in k_diag_lin_heavy)
         const uint32_t b = first[a], e = first[a + 1];
-        const fr acc = diag_sum_block(b, e, terms, msgs, l, k, l_recip, coef_mont, DiagAllRows{}, sh);
+        fr acc = fr_zero();
+        for (uint32_t t = b + threadIdx.x; t < e; t += LIN_WG) {
+            const lig_lin_term tm = terms[t];
+            acc = diag_apply(acc, tm.coef, wit(t, tm.slot), coef_mont);
+        }
+        acc = lin_block_sum(acc, sh);
         if (threadIdx.x == 0) {
-            const uint32_t cn = asked[a], ri = rhs_index[cn];
+            const uint32_t cn = asked[a], ri = rhs_index[Wit::rhs_by_asked ? a : cn];
             const fr rhs = ri ? diag_coef_value(rhs_coef[ri - 1], coef_mont) : fr_zero();
             const fr res = fr_sub(acc, rhs);
             uint2* o = reinterpret_cast<uint2*>(out + a);
@@ -333,6 +360,27 @@ __global__ void __launch_bounds__(LIN_WG) k_explain_finish(const uint32_t* __res
             for (int w = 0; w < 4; w++) { o[3 + w] = make_uint2(rhs.v[2 * w], rhs.v[2 * w + 1]); o[7 + w] = make_uint2(res.v[2 * w], res.v[2 * w + 1]); }
         }
         __syncthreads();                                                  // sh is reused by the next constraint
+    }
+}
+// ---- one rank of a sharded rows job (lig_shard_rows_explain, lig_shard_rows_read_slots): the value of a slot exists on the rank that was
+// dealt its row, and nowhere else.
+//   k_explain_part   one lane per entry of a piece: send[i] = the canonical w of slot[i * stride] when this rank holds its row (local_of, as
+//                    k_diag_lin_part), zero when it does not.  stride = 2: the slots of a lig_lin_term list; 1: a plain slot list.
+//                    Every slot is < rows_global * l (the host checked it): the row indexes local_of inside its rows_global entries.
+//   k_explain_sum    one lane per entry: vals[i] = the sum of the W received values (recv = W blocks of P entries, block g from rank g).
+//                    A row has one owner, so exactly one summand is non-zero: the sum is the value, no owner table, no dependence on order.
+__global__ void __launch_bounds__(LIN_WG) k_explain_part(const uint32_t* __restrict__ slot, uint32_t stride, uint32_t n, const fr* __restrict__ msgs, uint32_t l,
+                                                         uint32_t k, uint64_t l_recip, const uint32_t* __restrict__ local_of, fr* __restrict__ send) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t sl = slot[i * stride], grow = diag_div(sl, l_recip), row = local_of[grow];
+        fr_store(send + i, row == LIN_NOT_LOCAL ? fr_zero() : fr_load(msgs + (size_t)row * k + (sl - grow * l)));
+    }
+}
+__global__ void __launch_bounds__(LIN_WG) k_explain_sum(const fr* __restrict__ recv, uint32_t W, uint32_t P, uint32_t n, fr* __restrict__ vals) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG) {
+        fr acc = fr_load(recv + i);
+        for (uint32_t g = 1; g < W; g++) acc = fr_add(acc, fr_load(recv + (size_t)g * P + i));
+        fr_store(vals + i, acc);
     }
 }
 __global__ void __launch_bounds__(LIN_WG) k_read_slots(const uint32_t* __restrict__ slots, uint32_t n, const fr* __restrict__ msgs, uint32_t l, uint32_t k,
@@ -658,9 +706,10 @@ int explain_rows(lig_ctx* c, const fr* msgs, const lig_linear_system* sys, const
     if (m) HIP_TRY(c, hipMemcpyAsync(d_ordered, ordered.data(), (size_t)m * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
     if (rep) HIP_TRY(c, hipMemcpyAsync(d_ask, ask.data(), (size_t)rep * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d_first, first32.data(), ((size_t)NA + 1) * 4, hipMemcpyHostToDevice, s));
-    if (rep) hipLaunchKernelGGL(lig::k_explain_fill, dim3(diag_grid(rep)), dim3(lig::LIN_WG), 0, s, d_ordered, d_ask, rep, d_asked, msgs, l, k, l_recip, d.coef, d_out);
-    hipLaunchKernelGGL(lig::k_explain_finish, dim3(std::min<uint32_t>(NA, lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d_first, d_ordered, d_asked, NA, msgs, l, k,
-                       l_recip, d.coef, d.rhs_index, d.rhs_coef, d_con);
+    const lig::ExplainFromMatrix wit{msgs, l, k, l_recip};
+    if (rep) hipLaunchKernelGGL(lig::k_explain_fill<lig::ExplainFromMatrix>, dim3(diag_grid(rep)), dim3(lig::LIN_WG), 0, s, d_ordered, d_ask, rep, d_asked, wit, d.coef, d_out);
+    hipLaunchKernelGGL(lig::k_explain_finish<lig::ExplainFromMatrix>, dim3(std::min<uint32_t>(NA, lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d_first, d_ordered, d_asked, NA,
+                       wit, d.coef, d.rhs_index, d.rhs_coef, d_con);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(con_out, d_con, (size_t)NA * sizeof(lig_explain_constraint), hipMemcpyDeviceToHost, s));
     if (rep) HIP_TRY(c, hipMemcpyAsync(terms_out, d_out, (size_t)rep * sizeof(lig_explain_term), hipMemcpyDeviceToHost, s));
@@ -890,5 +939,185 @@ int lig_internal_shard_diagnose(lig_ctx* c, const lig_diag_shard& v, const lig_l
     if (trace_on && rc == LIG_OK)
         std::fprintf(stderr, "[lig_trace] shard_diagnose rank %u: partial %.3f exchange %.3f reduce %.3f records %.3f quadratic %.3f ms\n", v.rank, ph[PH_PARTIAL],
                      ph[PH_EXCHANGE], ph[PH_REDUCE], ph[PH_RECORDS], ph[PH_QUAD]);
+    return rc;
+}
+
+namespace {
+// What lig_shard_rows_explain and lig_shard_rows_read_slots share: the committed values of n_items slots, each held by one rank, on every
+// rank.  d_slot: the slots on the device, `stride` 32-bit words apart (k_explain_part).  In pieces of P = explain_piece_size(n_items, slice)
+// entries: part -> d_send (the ragged tail of the last piece zeroed, so that every piece is sent at the fixed size), ONE all-gather of
+// P x 32 bytes per rank, sum -> the caller's buffer for the piece.  The schedule depends on n_items, W and the slice alone.
+struct ExplainExchange {
+    uint32_t* d_local = nullptr; fr *d_send = nullptr, *d_recv = nullptr;
+    uint64_t P = 0;
+};
+enum { XPH_PART, XPH_EXCHANGE, XPH_SUM, XPH_RECORDS, XPH_N };
+int explain_exchange_alloc(lig_ctx* c, DiagScratch& sc, const lig_diag_shard& v, std::vector<uint32_t>& local_of, uint64_t n_items, ExplainExchange& x) {
+    x.P = lig::explain_piece_size(n_items, v.slice);
+    local_of.assign(v.rows_global, lig::LIN_NOT_LOCAL);
+    for (size_t lr = 0; lr < v.grow->size(); lr++) local_of[(*v.grow)[lr]] = (uint32_t)lr;
+    TRY(sc.alloc((void**)&x.d_local, local_of.size() * 4));
+    TRY(sc.alloc((void**)&x.d_send, (size_t)x.P * 32));
+    TRY(sc.alloc((void**)&x.d_recv, (size_t)v.world * x.P * 32));
+    if (!local_of.empty()) HIP_TRY(c, hipMemcpyAsync(x.d_local, local_of.data(), local_of.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return LIG_OK;
+}
+// piece j of the n_items entries: d_slot points at the first slot of the piece, the sums go to d_out[0 .. n)
+int explain_exchange_piece(lig_ctx* c, const lig_diag_shard& v, const ExplainExchange& x, const uint32_t* d_slot, uint32_t stride, uint32_t n, fr* d_out,
+                           const std::function<int(int)>& mark, const char* what) {
+    hipStream_t s = c->stream;
+    if (n < x.P) HIP_TRY(c, hipMemsetAsync(x.d_send + n, 0, (size_t)(x.P - n) * 32, s));
+    hipLaunchKernelGGL(lig::k_explain_part, dim3(diag_grid(n)), dim3(lig::LIN_WG), 0, s, d_slot, stride, n, v.msgs, c->l, c->k, diag_reciprocal(c->l), x.d_local, x.d_send);
+    HIP_TRY(c, hipGetLastError());
+    TRY(mark(XPH_PART));
+    TRY(v.all_gather(x.d_send, x.d_recv, (size_t)x.P * 32, what));
+    TRY(mark(XPH_EXCHANGE));
+    hipLaunchKernelGGL(lig::k_explain_sum, dim3(diag_grid(n)), dim3(lig::LIN_WG), 0, s, x.d_recv, v.world, (uint32_t)x.P, n, d_out);
+    HIP_TRY(c, hipGetLastError());
+    TRY(mark(XPH_SUM));
+    return LIG_OK;
+}
+}  // namespace
+
+// One rank of a sharded rows job (lig_shard_rows_explain, lig_hip.h).  sys has passed lig_linear_check, asked explain_asked_ok, n_asked > 0.
+// Collective: with m = the terms of the asked constraints (known on every host from sys->term_begin) and P = min(m, LIG_DIAG_SLICE) there are
+// ceil(m / P) all-gathers of 32 P bytes per rank -- whatever this rank holds, whatever term_cap is (con_out needs every value).
+// The items are formed and ordered on the host (explain_items_of, explain_order): no k_explain_gather, no copy back, and the system is not
+// uploaded -- only the m ordered terms, first[], the asked list, one right-hand-side coefficient index per asked constraint and the table.
+// Scratch: 32 P (send) + 32 W P (receive) + 32 m (values) + 8 m (terms) + 4 rows_global + 32 n_coefs + 12 n_asked + 4 (n_asked + 1), and
+// the records: 88 n_asked + 84 min(m, term_cap).  Every send buffer is an allocation of its own; v.forget runs before any of them is freed.
+int lig_internal_shard_explain(lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, const uint32_t* asked, uint64_t n_asked,
+                               lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info) {
+    hipStream_t s = c->stream;
+    const uint32_t NA = (uint32_t)n_asked;
+    // (sources of queued uploads: declared before the scratch, whose destructor drains the stream)
+    std::vector<lig::ExplainItem> items;
+    std::vector<uint64_t> first;
+    std::vector<uint32_t> first32, ask, rhs_index, rhs_coef, local_of;
+    std::vector<lig_lin_term> ordered;
+    DiagScratch sc(c);
+    bool used_comm = false;
+    const DiagWait wait = [&v]() -> int { return v.drain("lig_shard_rows_explain"); };
+    const bool trace_on = lig::knobs().trace;
+    double ph[XPH_N] = {0, 0, 0, 0};
+    auto t_mark = clk::now();
+    const std::function<int(int)> mark = [&](int p) -> int {
+        if (!trace_on) return LIG_OK;
+        TRY(wait());
+        ph[p] += ms_since(t_mark);
+        t_mark = clk::now();
+        return LIG_OK;
+    };
+    uint32_t m = 0, rep = 0;
+
+    auto body = [&]() -> int {
+        m = (uint32_t)lig::explain_items_of(*sys, asked, n_asked, items);       // <= n_terms < 2^32: the asked are distinct
+        if (!lig::explain_order(items, NA, first)) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain: a term names no asked constraint");
+        rep = (uint32_t)std::min<uint64_t>(m, term_cap);
+        ordered.resize(m);
+        ask.resize(rep);
+        first32.assign(first.begin(), first.end());
+        for (uint32_t i = 0; i < m; i++) { ordered[i].slot = items[i].slot; ordered[i].coef = items[i].coef; }
+        for (uint32_t i = 0; i < rep; i++) ask[i] = items[i].ask;
+        // b_c of asked constraint a: rhs_coef[rhs_index[a] - 1], rhs_index[a] = a + 1 when it has one, else 0 (rhs_constraint is ascending)
+        lig::explain_rhs_of(*sys, asked, n_asked, rhs_index, rhs_coef);
+        lig_lin_term* d_ordered = nullptr; uint32_t *d_asked = nullptr, *d_ask = nullptr, *d_first = nullptr, *d_rhs_index = nullptr, *d_rhs_coef = nullptr;
+        fr *d_coef = nullptr, *d_vals = nullptr; lig_explain_constraint* d_con = nullptr; lig_explain_term* d_out = nullptr;
+        ExplainExchange x;
+        TRY(sc.alloc((void**)&d_ordered, (size_t)m * sizeof(lig_lin_term)));
+        TRY(sc.alloc((void**)&d_asked, (size_t)NA * 4));
+        TRY(sc.alloc((void**)&d_ask, (size_t)rep * 4));
+        TRY(sc.alloc((void**)&d_first, ((size_t)NA + 1) * 4));
+        TRY(sc.alloc((void**)&d_rhs_index, (size_t)NA * 4));
+        TRY(sc.alloc((void**)&d_rhs_coef, (size_t)NA * 4));
+        TRY(sc.alloc((void**)&d_coef, (size_t)sys->n_coefs * 32));
+        TRY(sc.alloc((void**)&d_vals, (size_t)m * 32));
+        TRY(sc.alloc((void**)&d_con, (size_t)NA * sizeof(lig_explain_constraint)));
+        TRY(sc.alloc((void**)&d_out, (size_t)rep * sizeof(lig_explain_term)));
+        if (m) TRY(explain_exchange_alloc(c, sc, v, local_of, m, x));
+        if (m) HIP_TRY(c, hipMemcpyAsync(d_ordered, ordered.data(), (size_t)m * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_asked, asked, (size_t)NA * 4, hipMemcpyHostToDevice, s));
+        if (rep) HIP_TRY(c, hipMemcpyAsync(d_ask, ask.data(), (size_t)rep * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_first, first32.data(), ((size_t)NA + 1) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_rhs_index, rhs_index.data(), (size_t)NA * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_rhs_coef, rhs_coef.data(), (size_t)NA * 4, hipMemcpyHostToDevice, s));
+        if (sys->n_coefs) HIP_TRY(c, hipMemcpyAsync(d_coef, sys->coefs, (size_t)sys->n_coefs * 32, hipMemcpyHostToDevice, s));
+        lig::launch_lin_coefs_mont(s, d_coef, sys->n_coefs);
+        HIP_TRY(c, hipGetLastError());
+        TRY(mark(XPH_RECORDS));      // (uploads, table conversion)
+        const uint64_t n_pieces = lig::explain_piece_count(m, x.P);
+        for (uint64_t j = 0; j < n_pieces; j++) {
+            const uint32_t n = (uint32_t)lig::explain_piece_len(m, x.P, j);
+            used_comm = true;
+            TRY(explain_exchange_piece(c, v, x, &d_ordered[j * x.P].slot, 2, n, d_vals + j * x.P, mark, "all_gather(witness values of the asked terms)"));
+        }
+        const lig::ExplainFromValues wit{d_vals};
+        if (rep) hipLaunchKernelGGL(lig::k_explain_fill<lig::ExplainFromValues>, dim3(diag_grid(rep)), dim3(lig::LIN_WG), 0, s, d_ordered, d_ask, rep, d_asked, wit, d_coef, d_out);
+        hipLaunchKernelGGL(lig::k_explain_finish<lig::ExplainFromValues>, dim3(std::min<uint32_t>(NA, lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d_first, d_ordered, d_asked, NA,
+                           wit, d_coef, d_rhs_index, d_rhs_coef, d_con);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(con_out, d_con, (size_t)NA * sizeof(lig_explain_constraint), hipMemcpyDeviceToHost, s));
+        if (rep) HIP_TRY(c, hipMemcpyAsync(terms_out, d_out, (size_t)rep * sizeof(lig_explain_term), hipMemcpyDeviceToHost, s));
+        TRY(wait());
+        TRY(mark(XPH_RECORDS));
+        return LIG_OK;
+    };
+    const int rc = body();
+    if (rc != LIG_OK && v.settle_failed()) { sc.abandon(); return rc; }      // poisoned: the scratch outlives the call
+    if (rc == LIG_OK) (void)wait();
+    if (used_comm) v.forget();                                                // before any send buffer is freed (lig_comm.forget)
+    if (rc != LIG_OK) return rc;
+    info->n_terms_total = m;
+    info->n_terms_reported = rep;
+    if (trace_on)
+        std::fprintf(stderr, "[lig_trace] shard_explain rank %u: part %.3f exchange %.3f sum %.3f records %.3f ms\n", v.rank, ph[XPH_PART], ph[XPH_EXCHANGE], ph[XPH_SUM],
+                     ph[XPH_RECORDS]);
+    return LIG_OK;
+}
+
+// lig_shard_rows_read_slots: the same part / all-gather / sum over the slot list (it has passed explain_slots_ok against the rows of the WHOLE
+// trace, n_slots > 0) in pieces of P = min(n_slots, LIG_DIAG_SLICE); the summed piece is copied to `values`.  ceil(n_slots / P) all-gathers.
+// Scratch: 4 P (slots) + 32 P (send) + 32 W P (receive) + 32 P (sums) + 4 rows_global.
+int lig_internal_shard_read_slots(lig_ctx* c, const lig_diag_shard& v, const uint32_t* slots, uint64_t n_slots, uint8_t* values) {
+    hipStream_t s = c->stream;
+    std::vector<uint32_t> local_of;
+    DiagScratch sc(c);
+    bool used_comm = false;
+    const DiagWait wait = [&v]() -> int { return v.drain("lig_shard_rows_read_slots"); };
+    const bool trace_on = lig::knobs().trace;
+    double ph[XPH_N] = {0, 0, 0, 0};
+    auto t_mark = clk::now();
+    const std::function<int(int)> mark = [&](int p) -> int {
+        if (!trace_on) return LIG_OK;
+        TRY(wait());
+        ph[p] += ms_since(t_mark);
+        t_mark = clk::now();
+        return LIG_OK;
+    };
+    auto body = [&]() -> int {
+        ExplainExchange x;
+        uint32_t* d_slots = nullptr; fr* d_val = nullptr;
+        TRY(explain_exchange_alloc(c, sc, v, local_of, n_slots, x));
+        TRY(sc.alloc((void**)&d_slots, (size_t)x.P * 4));
+        TRY(sc.alloc((void**)&d_val, (size_t)x.P * 32));
+        const uint64_t n_pieces = lig::explain_piece_count(n_slots, x.P);
+        for (uint64_t j = 0; j < n_pieces; j++) {
+            const uint32_t n = (uint32_t)lig::explain_piece_len(n_slots, x.P, j);
+            HIP_TRY(c, hipMemcpyAsync(d_slots, slots + j * x.P, (size_t)n * 4, hipMemcpyHostToDevice, s));
+            used_comm = true;
+            TRY(explain_exchange_piece(c, v, x, d_slots, 1, n, d_val, mark, "all_gather(witness values of the slots)"));
+            HIP_TRY(c, hipMemcpyAsync(values + j * x.P * 32, d_val, (size_t)n * 32, hipMemcpyDeviceToHost, s));
+            TRY(wait());
+            TRY(mark(XPH_RECORDS));
+        }
+        return LIG_OK;
+    };
+    const int rc = body();
+    if (rc != LIG_OK && v.settle_failed()) { sc.abandon(); return rc; }      // poisoned: the scratch outlives the call
+    if (rc == LIG_OK) (void)wait();
+    if (used_comm) v.forget();                                                // before any send buffer is freed (lig_comm.forget)
+    if (trace_on && rc == LIG_OK)
+        std::fprintf(stderr, "[lig_trace] shard_read_slots rank %u: part %.3f exchange %.3f sum %.3f records %.3f ms\n", v.rank, ph[XPH_PART], ph[XPH_EXCHANGE], ph[XPH_SUM],
+                     ph[XPH_RECORDS]);
     return rc;
 }

@@ -505,6 +505,11 @@ struct lig_diag_shard {
 };
 int lig_internal_shard_diagnose(lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out,
                                 uint64_t quad_cap, lig_diag_info* info);
+// lig_shard_rows_explain / lig_shard_rows_read_slots (diagnose.hip) on the same view (all_to_all is not used): sys has passed
+// lig_linear_check, asked explain_asked_ok, the slots explain_slots_ok against the rows of the whole trace; n_asked > 0, n_slots > 0.
+int lig_internal_shard_explain(lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, const uint32_t* asked, uint64_t n_asked,
+                               lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info);
+int lig_internal_shard_read_slots(lig_ctx* c, const lig_diag_shard& v, const uint32_t* slots, uint64_t n_slots, uint8_t* values);
 
 // the batch program of a job on the device: committed rows are written to rows_out in program order (prover.hip)
 int lig_run_batch_program(lig_ctx* c, const lig_synth_job& job, fr* rows_out);

@@ -1,4 +1,5 @@
 // shard.hip -- one trace sharded over the GPUs of a node (lig_shard_*).
+#include "explain_plan.hpp"
 #include "prover_common.hpp"
 #include "upload.hpp"
 #include <unistd.h>
@@ -921,6 +922,24 @@ int lig_shard_rows_prove(lig_shard* S, const void* local_rands, int rands_on_dev
     return LIG_OK;
 }
 
+// what diagnose.hip needs of a rows shard for a collective call (lig_diag_shard, prover_common.hpp); inside a function that began with SHARD_COMMON
+#define SHARD_DIAG_VIEW(v) \
+    lig_diag_shard v; \
+    v.msgs = S->msgs; v.grow = &S->grow; v.rows_global = R; v.tri_dev = S->tri_dev; v.triple_ord = &S->triple_ord; \
+    v.n_terms_global = quad_terms(S->rows).size() / 3; \
+    v.rank = S->rank; v.world = W; v.slice = lig::knobs().diag_slice; \
+    v.all_to_all = [&](const void* src, void* dst, size_t block_bytes, const char* what) -> int { \
+        S->used_comm = true; \
+        if (ordered) { if (S->comm.all_to_all_on(S->comm.user, src, dst, block_bytes, s)) return comm_fail(what); return LIG_OK; } \
+        HIP_TRY(c, hipStreamSynchronize(s)); \
+        if (S->comm.all_to_all(S->comm.user, src, dst, block_bytes)) return comm_fail(what); \
+        return LIG_OK; \
+    }; \
+    v.all_gather = [&](const void* src, void* dst, size_t bytes, const char* what) -> int { return all_gather(src, dst, bytes, s, what); }; \
+    v.drain = [&](const char* what) -> int { return drain(s, what); }; \
+    v.settle_failed = [&]() -> bool { shard_settle(S); return S->poisoned; }; \
+    v.forget = [&] { if (S->comm.forget) S->comm.forget(S->comm.user); };
+
 // Which constraints does the committed witness violate, on a rows shard (diagnose.hip): collective, every rank obtains the bytes of
 // lig_rows_diagnose on the whole trace.  Everything that can be refused is refused here, on the host, identically on every rank, before
 // anything is launched and before any collective.
@@ -945,24 +964,59 @@ int lig_shard_rows_diagnose(lig_shard* S, const lig_linear_system* sys, lig_diag
         info->ms_total = ms_since(t_begin);
         return LIG_OK;
     }
-    lig_diag_shard v;
-    v.msgs = S->msgs; v.grow = &S->grow; v.rows_global = R; v.tri_dev = S->tri_dev; v.triple_ord = &S->triple_ord;
-    v.n_terms_global = quad_terms(S->rows).size() / 3;
-    v.rank = S->rank; v.world = W; v.slice = lig::knobs().diag_slice;
-    v.all_to_all = [&](const void* src, void* dst, size_t block_bytes, const char* what) -> int {
-        S->used_comm = true;
-        if (ordered) { if (S->comm.all_to_all_on(S->comm.user, src, dst, block_bytes, s)) return comm_fail(what); return LIG_OK; }
-        HIP_TRY(c, hipStreamSynchronize(s));
-        if (S->comm.all_to_all(S->comm.user, src, dst, block_bytes)) return comm_fail(what);
-        return LIG_OK;
-    };
-    v.all_gather = [&](const void* src, void* dst, size_t bytes, const char* what) -> int { return all_gather(src, dst, bytes, s, what); };
-    v.drain = [&](const char* what) -> int { return drain(s, what); };
-    v.settle_failed = [&]() -> bool { shard_settle(S); return S->poisoned; };
-    v.forget = [&] { if (S->comm.forget) S->comm.forget(S->comm.user); };
+    SHARD_DIAG_VIEW(v);
     TRY(lig_internal_shard_diagnose(c, v, sys, lin_out, lin_cap, quad_out, quad_cap, info));
     info->ms_total = ms_since(t_begin);
     return LIG_OK;
+}
+
+// lig_rows_explain / lig_rows_read_slots on a rows shard (diagnose.hip): collective, every rank obtains the bytes of the one-GPU call on the
+// whole trace.  Window, state checks and refusals as lig_shard_rows_diagnose: decided here, on the host, identically on every rank, before
+// anything is launched and before any collective.
+int lig_shard_rows_explain(lig_shard* S, const lig_linear_system* sys, const uint32_t* asked, uint64_t n_asked, lig_explain_constraint* con_out,
+                           lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info) {
+    if (!S || !info || info->struct_bytes < sizeof(lig_explain_info)) return LIG_E_ARG;
+    if ((n_asked && (!con_out || !asked)) || (term_cap && !terms_out)) return LIG_E_ARG;
+    const auto t_begin = clk::now();
+    SHARD_COMMON;
+    (void)n;
+    CHECK_CTX(c);
+    if (S->poisoned) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain: the shard is poisoned (work queued behind a failed collective never drained): destroy it");
+    if (!S->from_rows) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain: not a rows shard (lig_shard_rows_begin)");
+    if (!S->diag_ok) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain: no committed matrix (between lig_shard_rows_commit and the next lig_shard_rows_restart)");
+    if (!sys) FAIL(c, LIG_E_ARG, "lig_shard_rows_explain: null linear system");
+    if (lig_linear_check(sys, kinds_of(S->rows).data(), R, l) != LIG_OK) FAIL(c, LIG_E_ARG, "lig_shard_rows_explain: linear system rejected by lig_linear_check");
+    if (!lig::explain_asked_ok(asked, n_asked, sys->n_constraints))
+        FAIL(c, LIG_E_ARG, "lig_shard_rows_explain: the asked constraints must be strictly ascending and below n_constraints");
+    const uint32_t struct_bytes = info->struct_bytes;
+    std::memset(info, 0, sizeof *info);
+    info->struct_bytes = struct_bytes;
+    if (!n_asked) return LIG_OK;
+    ShardDebugScope dbg(S, "explain", nullptr);
+    if (W == 1 && !S->exchange_even_alone) {       // one rank holds every row in commit order: the one-GPU call, no collective
+        TRY(lig_internal_rows_explain(c, S->msgs, sys, asked, n_asked, con_out, terms_out, term_cap, info));
+        info->ms_total = ms_since(t_begin);
+        return LIG_OK;
+    }
+    SHARD_DIAG_VIEW(v);
+    TRY(lig_internal_shard_explain(c, v, sys, asked, n_asked, con_out, terms_out, term_cap, info));
+    info->ms_total = ms_since(t_begin);
+    return LIG_OK;
+}
+int lig_shard_rows_read_slots(lig_shard* S, const uint32_t* slots, uint64_t n_slots, uint8_t* values) {
+    if (!S || (n_slots && (!slots || !values))) return LIG_E_ARG;
+    SHARD_COMMON;
+    (void)n;
+    CHECK_CTX(c);
+    if (S->poisoned) FAIL(c, LIG_E_STATE, "lig_shard_rows_read_slots: the shard is poisoned (work queued behind a failed collective never drained): destroy it");
+    if (!S->from_rows) FAIL(c, LIG_E_STATE, "lig_shard_rows_read_slots: not a rows shard (lig_shard_rows_begin)");
+    if (!S->diag_ok) FAIL(c, LIG_E_STATE, "lig_shard_rows_read_slots: no committed matrix (between lig_shard_rows_commit and the next lig_shard_rows_restart)");
+    if (!lig::explain_slots_ok(slots, n_slots, R, l)) FAIL(c, LIG_E_ARG, "lig_shard_rows_read_slots: a slot is not below rows * l of the whole trace");
+    if (!n_slots) return LIG_OK;
+    ShardDebugScope dbg(S, "read_slots", nullptr);
+    if (W == 1 && !S->exchange_even_alone) return lig_internal_rows_read_slots(c, S->msgs, R, slots, n_slots, values);
+    SHARD_DIAG_VIEW(v);
+    return lig_internal_shard_read_slots(c, v, slots, n_slots, values);
 }
 
 // The sparse linear system of the WHOLE trace on a rows shard: every rank passes the same system (a collective contract, like the kinds) and
