@@ -439,7 +439,8 @@ int lig_linear_form(lig_ctx *ctx, const lig_linear_system *sys, const uint8_t *k
  * trace to it (what a proof writes: the sampled r_c, partial sums, the constant, an overriding coefficient table).  A verifier
  * service prepares once and attaches per envelope; two contexts proving the same guest hold one copy; a new statement of the same
  * program (other right-hand sides) is lig_rows_set_linear_values, not a new prepare.
- * The sharded entry (lig_shard_rows_set_linear) is not covered: a rank's structure depends on its deal, and nothing shares it. */
+ * On the sharded entry a rank's structure depends on its deal and nothing shares it (no program object), but a new statement is likewise
+ * a call of lig_shard_rows_set_linear_values below, not a second lig_shard_rows_set_linear. */
 typedef struct lig_linear_program lig_linear_program;
 /* check (lig_linear_check), upload, regroup by slot -- what lig_rows_set_linear does -- into an immutable, reference-counted object
  * bound to ctx's DEVICE and (l, k), not to ctx: it may be attached to traces of any context of this process on that device, from any
@@ -529,7 +530,7 @@ int lig_rows_diagnose(lig_trace *trace, const lig_linear_system *sys, lig_diag_l
  * diagnosed this way is byte-identical to that of one that was not.  LIG_E_STATE outside the window, for a lig_synth_prepare trace and
  * when nothing is attached; LIG_E_ARG for a NULL array with a cap > 0, a NULL or too small *info, a NULL trace; all decided on the host
  * before anything is launched.  info->ms_total is the whole call.
- * The sharded entry is not covered: lig_shard_rows_diagnose takes the term list, as before. */
+ * The sharded entry has its own call, lig_shard_rows_diagnose_attached below. */
 int lig_rows_diagnose_attached(lig_trace *trace, lig_diag_linear *lin_out, uint64_t lin_cap, lig_diag_quad *quad_out, uint64_t quad_cap,
                                lig_diag_info *info);
 
@@ -700,6 +701,20 @@ int lig_shard_rows_prove(lig_shard *shard, const void *local_rands, int rands_on
  * LIG_E_ARG: a system lig_linear_check rejects (nothing is launched), a job with dense_rands_per_row, local_rands != NULL in
  * lig_shard_rows_prove while a system is set.  LIG_E_STATE: a shard not made by lig_shard_rows_begin, a poisoned shard. */
 int lig_shard_rows_set_linear(lig_shard *shard, const lig_linear_system *sys);
+/* Per-proof VALUES of the coefficient table of the system set with lig_shard_rows_set_linear: what lig_rows_set_linear_values is on one
+ * GPU.  coefs[] with the system's n_coefs, canonical -- the public right-hand sides b_c of a new statement are the entries named by
+ * rhs_coef.  The values belong to the rank's attachment and stay in force over lig_shard_rows_restart until set again (a second
+ * lig_shard_rows_set_linear drops them with the structure); coefs == NULL: back to the system's own table.  Copied before the call
+ * returns; converted on the device, on the stream the rank's form runs on.  Nothing is re-checked, re-uploaded or regrouped: the call
+ * costs one pass over n_coefs entries on the host and one small kernel, whatever the size of the system.
+ * COLLECTIVE CONTRACT as lig_shard_rows_set_linear: every rank passes the same table; ranks that differ are not detected (they produce
+ * an envelope that fails its own linear check, or differing envelopes).  No collective is involved: the call never waits for a peer.
+ * With values set, lig_shard_rows_prove(local_rands = NULL, const_sum = NULL) proves that statement: info->const_sum and the envelope are
+ * those of a shard whose system was set with these values as sys->coefs.
+ * Any time after lig_shard_rows_set_linear and before lig_shard_rows_prove.  ERRORS, decided on the host before anything is launched:
+ * LIG_E_ARG: a NULL shard, another n_coefs, an entry >= p; LIG_E_STATE: no system set, a shard not made by lig_shard_rows_begin, a
+ * poisoned shard.  A refused call leaves the values in force as they were.  Device memory: n_coefs x 32 on top of the attachment. */
+int lig_shard_rows_set_linear_values(lig_shard *shard, const uint8_t *coefs, uint64_t n_coefs);
 /* of the system set last: the terms this rank kept and the distinct stream elements it samples per proof (LIG_E_STATE: no system set) */
 int lig_shard_rows_linear_stats(const lig_shard *shard, uint64_t *local_terms, uint64_t *sampled_constraints);
 /* host only, no context: the same two numbers for `rank` of `world` from the deal of lig_shard_rows_plan -- to size a node before a
@@ -736,6 +751,32 @@ int lig_linear_shard_count(const lig_linear_system *sys, const uint8_t *kinds, u
  * Not done: skipping the exchange for constraints whose terms all lie on one rank (it would make the schedule depend on the data). */
 int lig_shard_rows_diagnose(lig_shard *shard, const lig_linear_system *sys, lig_diag_linear *lin_out, uint64_t lin_cap,
                             lig_diag_quad *quad_out, uint64_t quad_cap, lig_diag_info *info);
+/* lig_shard_rows_diagnose against the system ATTACHED to the shard (lig_shard_rows_set_linear), with the values of
+ * lig_shard_rows_set_linear_values in force: the statement lig_shard_rows_prove(local_rands = NULL, const_sum = NULL) would prove.  What
+ * lig_rows_diagnose_attached is on one GPU: for the caller who has released the term list, and the only call that needs no hand-passed
+ * "table of THIS statement".  COLLECTIVE: every rank calls it with the same caps.  EVERY RANK RETURNS THE SAME BYTES, and they are what
+ * lig_shard_rows_diagnose -- and hence lig_rows_diagnose on the whole trace -- returns for the same statement.  Window, caps, *info, the
+ * quadratic part, failure and poisoning rules are exactly those of lig_shard_rows_diagnose; whether a collective is issued, how many and
+ * of which size depends on the system's sizes, the caps, world and the slice size alone.
+ * HOW: a rank holds the slot-major index of its own rows with constraints numbered compactly through its need list, its slice of the
+ * right-hand sides and the table in force -- all on its device.  The call regroups the index by compact constraint there (count, scan,
+ * scatter, as lig_rows_diagnose_attached; the atomics only place a term inside its segment, the sums are exact).  The need list is
+ * ascending, so a slice of LIG_DIAG_SLICE constraints of the whole trace is a contiguous compact range: the send buffer is zeroed, one lane
+ * per compact constraint of the range (one workgroup and the fixed tree for one with more than 2048 local terms) sums a * w over its
+ * local terms and -- a right-hand side has exactly one holder -- subtracts b_c when this rank holds it.  The owner of a sub-block then
+ * only adds the W partials: the sum is the residual, exact and independent of rank order.  A constraint with a right-hand side and no
+ * term anywhere comes out as -b_c, as on one GPU.  Everything behind the reduce is lig_shard_rows_diagnose.  No host pass over the terms,
+ * no upload of the system; the table in force is read in place, behind an event when its conversion is still running on the side stream.
+ * world == 1 without LIG_SHARD_FORCE_EXCHANGE: no collective, the call is lig_rows_diagnose_attached on the rank's matrix.
+ * ERRORS, all decided on the host, identically on every rank, before any launch and any collective: LIG_E_ARG for a NULL shard, a NULL
+ * array with a cap > 0, a NULL or short *info; LIG_E_STATE when no system is set, before the commit, for a shard not made by
+ * lig_shard_rows_begin, for a poisoned shard.
+ * SCRATCH lives for the call only, on the context's main stream (lig_comm.forget runs before any send buffer is freed); nothing the
+ * attachment owns is written, and the envelope of a shard diagnosed this way is byte-identical to that of one that was not.  In the
+ * formula of lig_shard_rows_diagnose the uploaded system is replaced by 8 bytes per local term, 12 per needed constraint and 4 per slice.
+ * Not done: an attached explain on a shard, sharing a prepared program between ranks, caching the regrouped list between calls. */
+int lig_shard_rows_diagnose_attached(lig_shard *shard, lig_diag_linear *lin_out, uint64_t lin_cap, lig_diag_quad *quad_out,
+                                     uint64_t quad_cap, lig_diag_info *info);
 
 /* lig_rows_explain / lig_rows_read_slots on a rows shard (csrc/diagnose.hip, csrc/shard.hip).  lig_shard_rows_diagnose hands every rank
  * a constraint number and 32 residual bytes; a constraint may span ranks and no process holds the witness: the value of a term on a

@@ -142,7 +142,7 @@ public:
     // the batcher.  Every rank's prove() returns the same envelope as an unsharded batcher would.
     void shard_over(uint32_t rank, uint32_t world, const lig_comm* comm) {
         if (pass_ != 1 || !comm || !world || rank >= world) throw std::invalid_argument("hip_row_batcher::shard_over");
-        if (program_ || values_set_) throw std::logic_error("hip_row_batcher::shard_over: a prepared linear program / values of its table are not for a sharded batcher");
+        if (program_) throw std::logic_error("hip_row_batcher::shard_over: a prepared linear program is not for a sharded batcher (set_linear_system)");
         if (shard_) { lig_shard_destroy(shard_); shard_ = nullptr; linear_on_trace_ = false; }      // another deal: nothing of the old shard is reused
         sharded_ = true; rank_ = rank; world_ = world; comm_ = *comm;
     }
@@ -181,10 +181,11 @@ public:
     // The values of the coefficient table for the proofs that follow (lig_rows_set_linear_values): n_coefs x 32 bytes, canonical,
     // n_coefs as in the system / program -- the public right-hand sides of a new statement of the same program are the entries that
     // rhs_coef names.  Copied; kept across reset() until set again; nullptr: the table the system / program came with.
+    // With shard_over(): lig_shard_rows_set_linear_values -- every rank sets the same values (no collective is involved); the rank's
+    // share of the system stays as it is, nothing is checked, uploaded or regrouped again.
     void set_linear_values(const uint8_t* coefs, uint64_t n_coefs) {
         if (pass_ == 3) throw std::logic_error("hip_row_batcher::set_linear_values after prove (reset() first)");
         if (!has_linear()) throw std::logic_error("hip_row_batcher::set_linear_values without a linear system or program");
-        if (sharded_) throw std::logic_error("hip_row_batcher::set_linear_values: not on a sharded batcher");
         values_set_ = coefs != nullptr;
         values_.assign(coefs, coefs + (coefs ? n_coefs * 32 : 0));
         values_on_trace_ = false;
@@ -329,14 +330,18 @@ public:
     // The same question put to the statement ATTACHED to the trace (lig_rows_diagnose_attached, lig_hip.h): the structure of
     // set_linear_system or set_linear_program as it lies on the device, with the values of set_linear_values in force if any were set --
     // exactly what prove(nullptr) proves.  No term list is needed: the caller of set_linear_program may have released its own long ago.
-    // After commit(), before or after prove(), until the next commit(); same output as diagnose().  std::logic_error before commit(),
-    // without a system or program, and with shard_over() (a rank's structure is local: diagnose() there).
+    // After commit(), before or after prove(), until the next commit(); same output as diagnose().  std::logic_error before commit() and
+    // without a system or program.  With shard_over(): lig_shard_rows_diagnose_attached, a COLLECTIVE call over every rank's share of
+    // the system as it lies on its device -- every rank calls it with the same caps and gets the output of the unsharded batcher.
     void diagnose_attached(lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
-        if (sharded_) throw std::logic_error("hip_row_batcher::diagnose_attached: not on a sharded batcher (diagnose)");
-        if (pass_ == 1 || !trace_) throw std::logic_error("hip_row_batcher::diagnose_attached before commit");
+        if (pass_ == 1 || !(sharded_ ? (bool)shard_ : (bool)trace_)) throw std::logic_error("hip_row_batcher::diagnose_attached before commit");
         if (!has_linear() || !linear_on_trace_) throw std::logic_error("hip_row_batcher::diagnose_attached without a linear system or program");
         if (!info) throw std::invalid_argument("hip_row_batcher::diagnose_attached: null info");
         info->struct_bytes = sizeof(lig_diag_info);
+        if (sharded_) {
+            check(lig_shard_rows_diagnose_attached(shard_, lin_out, lin_cap, quad_out, quad_cap, info), "lig_shard_rows_diagnose_attached");
+            return;
+        }
         check(lig_rows_diagnose_attached(trace_, lin_out, lin_cap, quad_out, quad_cap, info), "lig_rows_diagnose_attached");
     }
     // ---- diagnose() names the violated constraints; these SHOW constraints: every term with its slot, coefficient index, coefficient
@@ -427,10 +432,11 @@ private:
             linear_on_trace_ = true;
             values_on_trace_ = !values_set_;              // a fresh attachment reads the table it came with
         }
-        if (!sharded_ && !values_on_trace_) apply_values();
+        if (!values_on_trace_) apply_values();
     }
-    void apply_values() {                                 // (the trace keeps them across lig_rows_restart)
-        check(lig_rows_set_linear_values(trace_, values_set_ ? values_.data() : nullptr, values_.size() / 32), "lig_rows_set_linear_values");
+    void apply_values() {                                 // (the trace / the shard keeps them across its restart)
+        if (sharded_) check(lig_shard_rows_set_linear_values(shard_, values_set_ ? values_.data() : nullptr, values_.size() / 32), "lig_shard_rows_set_linear_values");
+        else check(lig_rows_set_linear_values(trace_, values_set_ ? values_.data() : nullptr, values_.size() / 32), "lig_rows_set_linear_values");
         values_on_trace_ = true;
     }
     void push_rands(size_t upto) {

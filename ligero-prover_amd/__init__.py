@@ -45,6 +45,7 @@ EXPORTS = [
     "lig_rows_diagnose", "lig_rows_diagnose_attached",
     "lig_rows_explain", "lig_rows_explain_attached", "lig_rows_read_slots",
     "lig_shard_rows_explain", "lig_shard_rows_read_slots",
+    "lig_shard_rows_set_linear_values", "lig_shard_rows_diagnose_attached",
 ]
 
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
@@ -380,6 +381,8 @@ def load_library():
     L.lig_rows_diagnose.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, u64, C.POINTER(DiagInfo)]
     L.lig_shard_rows_diagnose.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, u64, C.POINTER(DiagInfo)]
     L.lig_rows_diagnose_attached.argtypes = [vp, vp, u64, vp, u64, C.POINTER(DiagInfo)]
+    L.lig_shard_rows_set_linear_values.argtypes = [vp, vp, u64]
+    L.lig_shard_rows_diagnose_attached.argtypes = [vp, vp, u64, vp, u64, C.POINTER(DiagInfo)]
     L.lig_rows_explain.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
     L.lig_rows_explain_attached.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
     L.lig_rows_read_slots.argtypes = [vp, vp, u64, vp]
@@ -1161,6 +1164,23 @@ class Context:
         lin, quad = np.zeros(lin_cap, dtype=DIAG_LINEAR), np.zeros(quad_cap, dtype=DIAG_QUAD)
         self.check(self.L.lig_shard_rows_diagnose(shard, C.byref(system) if system is not None else None, _hptr(lin) if lin_cap else None, lin_cap,
                                                   _hptr(quad) if quad_cap else None, quad_cap, C.byref(info)))
+        return info, lin[:info.n_linear_reported], quad[:info.n_quad_reported]
+
+    def shard_rows_set_linear_values(self, shard, coefs):
+        """lig_shard_rows_set_linear_values: rows_set_linear_values on a rows shard -- this rank's values of the coefficient table of the
+        system of shard_rows_set_linear (integers or (n, 8) uint32); None: the system's own.  Every rank passes the same table; no collective"""
+        tab = coef_table(coefs) if coefs is not None else None
+        self.check(self.L.lig_shard_rows_set_linear_values(shard, _hptr(tab) if tab is not None and len(tab) else None, len(tab) if tab is not None else 0))
+
+    def shard_rows_diagnose_attached(self, shard, lin_cap=1024, quad_cap=1024):
+        """lig_shard_rows_diagnose_attached: shard_rows_diagnose against the system attached to the shard (shard_rows_set_linear, with the
+        values of shard_rows_set_linear_values in force): no term list is passed.  Collective: every rank passes the same caps and gets
+        the same triple as shard_rows_diagnose"""
+        info = DiagInfo()
+        info.struct_bytes = C.sizeof(DiagInfo)
+        lin, quad = np.zeros(lin_cap, dtype=DIAG_LINEAR), np.zeros(quad_cap, dtype=DIAG_QUAD)
+        self.check(self.L.lig_shard_rows_diagnose_attached(shard, _hptr(lin) if lin_cap else None, lin_cap, _hptr(quad) if quad_cap else None, quad_cap,
+                                                           C.byref(info)))
         return info, lin[:info.n_linear_reported], quad[:info.n_quad_reported]
 
     def shard_rows_explain(self, shard, system, constraints, term_cap=4096):

@@ -11,7 +11,9 @@
 //   k_diag_lin_part, k_diag_lin_part_heavy   the same two walks over a slice of the constraints, through the rank's global -> local row
 //                      table: a * w of the terms whose row the rank holds, the others skipped; a canonical PARTIAL per constraint, no b_c, no flag
 //   k_diag_reduce      the owner of a sub-block of the slice adds the W partials it received, subtracts b_c, writes residual and flag
-// (exact arithmetic mod p: no result depends on an order).
+// (exact arithmetic mod p: no result depends on an order).  lig_shard_rows_diagnose_attached takes the partials from the rank's share
+// ATTACHED to the shard instead (k_diag_att_bounds, k_diag_att_part*: their header below) and lets the one holder of a right-hand side
+// subtract it there; the owner then only adds (k_diag_reduce<false>).
 // lig_rows_explain* / lig_rows_read_slots and their sharded counterparts (k_explain_*, k_read_slots) have a header of their own below.
 // Where the constraint-major list comes from is the only difference between the two one-GPU entries:
 //   lig_rows_diagnose            the caller's lig_linear_system, uploaded, with a scratch copy of its table in Montgomery form
@@ -113,8 +115,13 @@ static __device__ __forceinline__ uint32_t diag_slot_of(const uint32_t* __restri
     }
     return lo;
 }
-__global__ void __launch_bounds__(LIN_WG) k_diag_att_count(const uint2* __restrict__ ent, uint32_t n_terms, uint32_t* __restrict__ count) {
-    for (uint64_t e = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; e < n_terms; e += (uint64_t)gridDim.x * LIN_WG) atomicAdd(count + ent[e].x, 1u);
+// One rank's share of a sharded trace numbers its constraints compactly (linear.hip: ent[].x, rhs_c[] < n_need, need[i] = the constraint of
+// the whole trace).  `need` != NULL regroups such a share by the numbers of the whole trace (one rank that holds every row: the one-GPU pass);
+// NULL takes the numbers as they are -- a trace's own program, or the compact segments of lig_shard_rows_diagnose_attached.
+static __device__ __forceinline__ uint32_t diag_number(const uint32_t* __restrict__ need, uint32_t c) { return need ? need[c] : c; }
+__global__ void __launch_bounds__(LIN_WG) k_diag_att_count(const uint2* __restrict__ ent, uint32_t n_terms, const uint32_t* __restrict__ need,
+                                                           uint32_t* __restrict__ count) {
+    for (uint64_t e = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; e < n_terms; e += (uint64_t)gridDim.x * LIN_WG) atomicAdd(count + diag_number(need, ent[e].x), 1u);
 }
 // constraints with more than HEAVY_MIN terms, appended in any order: the host sorts the list
 __global__ void __launch_bounds__(LIN_WG) k_diag_att_classify(const uint32_t* __restrict__ count, uint32_t n_constraints, uint32_t* __restrict__ heavy,
@@ -127,18 +134,21 @@ __global__ void __launch_bounds__(LIN_WG) k_diag_att_classify(const uint32_t* __
 }
 // cursor[c] counts up to the number of terms of c (the counts cbegin was scanned from): every position lies inside the segment of c
 __global__ void __launch_bounds__(LIN_WG) k_diag_att_scatter(const uint2* __restrict__ ent, uint32_t n_terms, const uint32_t* __restrict__ begin, uint32_t n_slots,
-                                                             const uint32_t* __restrict__ cbegin, uint32_t* __restrict__ cursor, lig_lin_term* __restrict__ terms) {
+                                                             const uint32_t* __restrict__ need, const uint32_t* __restrict__ cbegin,
+                                                             uint32_t* __restrict__ cursor, lig_lin_term* __restrict__ terms) {
     for (uint64_t e = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; e < n_terms; e += (uint64_t)gridDim.x * LIN_WG) {
         const uint2 en = ent[e];
+        const uint32_t cn = diag_number(need, en.x);
         lig_lin_term tm;
         tm.slot = diag_slot_of(begin, n_slots, (uint32_t)e); tm.coef = en.y;
-        terms[cbegin[en.x] + atomicAdd(cursor + en.x, 1u)] = tm;
+        terms[cbegin[cn] + atomicAdd(cursor + cn, 1u)] = tm;
     }
 }
 
 // rhs_constraint is strictly ascending: every entry of rhs_index is written at most once
-__global__ void __launch_bounds__(LIN_WG) k_diag_rhs_index(const uint32_t* __restrict__ rhs_c, uint32_t n_rhs, uint32_t* __restrict__ rhs_index) {
-    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n_rhs; i += (uint64_t)gridDim.x * LIN_WG) rhs_index[rhs_c[i]] = (uint32_t)i + 1;
+__global__ void __launch_bounds__(LIN_WG) k_diag_rhs_index(const uint32_t* __restrict__ rhs_c, uint32_t n_rhs, const uint32_t* __restrict__ need,
+                                                           uint32_t* __restrict__ rhs_index) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n_rhs; i += (uint64_t)gridDim.x * LIN_WG) rhs_index[diag_number(need, rhs_c[i])] = (uint32_t)i + 1;
 }
 __global__ void __launch_bounds__(LIN_WG) k_diag_lin(const uint32_t* __restrict__ term_begin, const lig_lin_term* __restrict__ terms, uint32_t n_constraints,
                                                      const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip, const fr* __restrict__ coef_mont,
@@ -188,8 +198,75 @@ __global__ void __launch_bounds__(LIN_WG) k_diag_lin_part_heavy(const uint32_t* 
         __syncthreads();
     }
 }
+// ---- one rank of a sharded rows job, the share ATTACHED to it (lig_shard_rows_diagnose_attached): the regrouped list has one segment per
+// COMPACT constraint i < n_need, its terms carry LOCAL slots (every one lies in the rank's own rows x k matrix), need[] is ascending.
+//   k_diag_att_bounds        bound[j] = the first i with need[i] >= min(j * per, n_constraints), j = 0 .. n_slices: slice j of the constraints of
+//                            the whole trace is the contiguous compact range [bound[j], bound[j + 1])
+//   k_diag_att_heavy_global  the numbers of the whole trace of the (few) compact constraints with more than HEAVY_MIN local terms: the host
+//                            cuts the sorted list at the slice boundaries
+//   k_diag_att_part, k_diag_att_part_heavy   part[need[i] - c0] = the sum of a * w over the local terms of compact constraint i, MINUS b_c when
+//                            this rank holds the right-hand side of it (rhs_index[i], over the compact numbers): a right-hand side has
+//                            exactly one holder, so the W partials add up to the residual.  The send buffer was zeroed first: a
+//                            constraint this rank does not need contributes zero.
+static __device__ __forceinline__ uint32_t diag_lower_bound(const uint32_t* __restrict__ a, uint32_t n, uint64_t x) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__global__ void __launch_bounds__(LIN_WG) k_diag_att_bounds(const uint32_t* __restrict__ need, uint32_t n_need, uint64_t per, uint32_t n_slices,
+                                                            uint64_t n_constraints, uint32_t* __restrict__ bound) {
+    for (uint64_t j = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; j <= n_slices; j += (uint64_t)gridDim.x * LIN_WG) {
+        const uint64_t c = j * per;
+        bound[j] = diag_lower_bound(need, n_need, c < n_constraints ? c : n_constraints);
+    }
+}
+__global__ void __launch_bounds__(LIN_WG) k_diag_att_heavy_global(const uint32_t* __restrict__ heavy, uint32_t n_heavy, const uint32_t* __restrict__ need,
+                                                                  uint32_t* __restrict__ out) {
+    for (uint64_t h = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; h < n_heavy; h += (uint64_t)gridDim.x * LIN_WG) out[h] = need[heavy[h]];
+}
+// acc - b_c (when this rank holds it) -> the partial of compact constraint i; the range came from k_diag_att_bounds, so need[i] - c0 < n
+// (checked all the same: nothing is ever stored outside the n entries of the slice)
+static __device__ __forceinline__ void diag_part_store(uint32_t i, fr acc, const uint32_t* __restrict__ need, uint32_t c0, uint32_t n,
+                                                       const uint32_t* __restrict__ rhs_index, const uint32_t* __restrict__ rhs_coef,
+                                                       const fr* __restrict__ coef_mont, fr* __restrict__ part) {
+    const uint32_t at = need[i] - c0;
+    if (at >= n) return;
+    const uint32_t ri = rhs_index[i];
+    if (ri) acc = fr_sub(acc, diag_coef_value(rhs_coef[ri - 1], coef_mont));
+    fr_store(part + at, acc);
+}
+// range[0], range[1] = the compact range of the slice [c0, c0 + n)
+__global__ void __launch_bounds__(LIN_WG) k_diag_att_part(const uint32_t* __restrict__ range, const uint32_t* __restrict__ term_begin,
+                                                          const lig_lin_term* __restrict__ terms, const uint32_t* __restrict__ need, uint32_t c0, uint32_t n,
+                                                          const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip, const fr* __restrict__ coef_mont,
+                                                          const uint32_t* __restrict__ rhs_index, const uint32_t* __restrict__ rhs_coef, fr* __restrict__ part) {
+    const uint32_t i0 = range[0], i1 = range[1];
+    for (uint64_t i = (uint64_t)i0 + (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < i1; i += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t b = term_begin[i], e = term_begin[i + 1];
+        if (e - b > HEAVY_MIN) continue;                                  // k_diag_att_part_heavy
+        diag_part_store((uint32_t)i, diag_sum_lane(b, e, terms, msgs, l, k, l_recip, coef_mont, DiagAllRows{}), need, c0, n, rhs_index, rhs_coef, coef_mont, part);
+    }
+}
+// workgroup -> heavy compact constraint heavy[blockIdx.x + i * gridDim.x]; heavy[0 .. n_heavy) are those of the slice
+__global__ void __launch_bounds__(LIN_WG) k_diag_att_part_heavy(const uint32_t* __restrict__ heavy, uint32_t n_heavy, const uint32_t* __restrict__ term_begin,
+                                                                const lig_lin_term* __restrict__ terms, const uint32_t* __restrict__ need, uint32_t c0, uint32_t n,
+                                                                const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip, const fr* __restrict__ coef_mont,
+                                                                const uint32_t* __restrict__ rhs_index, const uint32_t* __restrict__ rhs_coef, fr* __restrict__ part) {
+    __shared__ fr sh[LIN_WG];
+    for (uint32_t h = blockIdx.x; h < n_heavy; h += gridDim.x) {          // (uniform over the workgroup, as in k_diag_lin_heavy)
+        const uint32_t i = heavy[h], b = term_begin[i], e = term_begin[i + 1];
+        const fr acc = diag_sum_block(b, e, terms, msgs, l, k, l_recip, coef_mont, DiagAllRows{}, sh);
+        if (threadIdx.x == 0) diag_part_store(i, acc, need, c0, n, rhs_index, rhs_coef, coef_mont, part);
+        __syncthreads();
+    }
+}
 // The owner of constraints [first, first + n_valid): recv = W blocks of B partials, block g from rank g, entry i of every block = constraint
-// first + i.  res[i] = their sum - b_c, flag[i]; entries [n_valid, B) (beyond the end of the system) get flag 0.
+// first + i.  res[i] = their sum - b_c, flag[i]; entries [n_valid, B) (beyond the end of the system) get flag 0.  RHS = false: the holder of
+// b_c has subtracted it in its partial (k_diag_att_part*), the sum is the residual and rhs_index / rhs_coef / coef_mont are not read.
+template <bool RHS>
 __global__ void __launch_bounds__(LIN_WG) k_diag_reduce(const fr* __restrict__ recv, uint32_t W, uint32_t B, uint32_t n_valid, uint32_t first,
                                                         const uint32_t* __restrict__ rhs_index, const uint32_t* __restrict__ rhs_coef, const fr* __restrict__ coef_mont,
                                                         fr* __restrict__ res, uint32_t* __restrict__ flag) {
@@ -197,7 +274,9 @@ __global__ void __launch_bounds__(LIN_WG) k_diag_reduce(const fr* __restrict__ r
         if (i >= n_valid) { flag[i] = 0u; continue; }
         fr acc = fr_load(recv + i);
         for (uint32_t g = 1; g < W; g++) acc = fr_add(acc, fr_load(recv + (size_t)g * B + i));
-        diag_finish(first + (uint32_t)i, (uint32_t)i, acc, rhs_index, rhs_coef, coef_mont, res, flag);
+        if (RHS) { diag_finish(first + (uint32_t)i, (uint32_t)i, acc, rhs_index, rhs_coef, coef_mont, res, flag); continue; }
+        fr_store(res + i, acc);
+        flag[i] = fr_is_zero(acc) ? 0u : 1u;
     }
 }
 // item i of the slice = (term first_term + i / l, column i % l); tri = (x, y, z) rows per term, y = 0xFFFFFFFF: the equality term x - z
@@ -467,17 +546,21 @@ int diag_upload_system(lig_ctx* c, DiagScratch& sc, const lig_linear_system* sys
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemsetAsync(d.rhs_index, 0, (size_t)NC * 4, s));
     if (NR) {
-        hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, d_rhs_c, NR, d.rhs_index);
+        hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, d_rhs_c, NR, nullptr, d.rhs_index);
         HIP_TRY(c, hipGetLastError());
     }
     return LIG_OK;
 }
-// The statement attached to the trace (v: prover_common.hpp, not sharded) -> constraint-major, in scratch: count, scan, scatter (file header).
+// The statement attached to the trace (v: prover_common.hpp) -> constraint-major, in scratch: count, scan, scatter (file header).
 // Scratch: cbegin (n_constraints + 1) x 4, counters / cursor (n_constraints + 1) x 4, terms n_terms x 8, rhs_index, the short heavy list.
 // Blocks once, for the scan's total and the number of heavy constraints.
-int diag_regroup_system(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, void** scan_tmp, size_t* scan_cap, const lig_linear_view& v, DiagSystem& d) {
+// One rank's share of a sharded trace (v.sharded): compact = false numbers the segments as the whole trace does, through need[] -- for the
+// rank that holds every row, whose local slots are the trace's; compact = true keeps the rank's own numbers: d.NC = n_need segments, d.tb,
+// d.rhs_index and d.heavy all over i < n_need, local slots (lig_shard_rows_diagnose_attached).
+int diag_regroup_system(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, void** scan_tmp, size_t* scan_cap, const lig_linear_view& v, bool compact, DiagSystem& d) {
     hipStream_t s = c->stream;
-    const uint32_t NC = d.NC = (uint32_t)v.n_constraints, NT = (uint32_t)v.n_terms, NR = (uint32_t)v.n_rhs;
+    const uint32_t NC = d.NC = (uint32_t)(compact ? v.n_need : v.n_constraints), NT = (uint32_t)v.n_terms, NR = (uint32_t)v.n_rhs;
+    const uint32_t* number = v.sharded && !compact ? v.need : nullptr;
     const uint32_t heavy_cap = NT / (lig::HEAVY_MIN + 1) + 1;
     uint32_t *d_cursor = nullptr, *d_nheavy = nullptr;
     TRY(sc.alloc((void**)&d.tb, ((size_t)NC + 1) * 4));
@@ -491,7 +574,7 @@ int diag_regroup_system(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, void*
     if (v.coef_ready) HIP_TRY(c, hipStreamWaitEvent(s, v.coef_ready, 0));
     HIP_TRY(c, hipMemsetAsync(d_cursor, 0, ((size_t)NC + 1) * 4, s));
     HIP_TRY(c, hipMemsetAsync(d_nheavy, 0, 4, s));
-    if (NT) hipLaunchKernelGGL(lig::k_diag_att_count, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, d_cursor);
+    if (NT) hipLaunchKernelGGL(lig::k_diag_att_count, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, number, d_cursor);
     hipLaunchKernelGGL(lig::k_diag_att_classify, dim3(diag_grid(NC)), dim3(lig::LIN_WG), 0, s, d_cursor, NC, d.heavy_dev, heavy_cap, d_nheavy);
     HIP_TRY(c, hipGetLastError());
     uint32_t total = 0, n_heavy = 0;
@@ -507,9 +590,9 @@ int diag_regroup_system(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, void*
         HIP_TRY(c, hipMemcpyAsync(d.heavy_dev, d.heavy.data(), (size_t)n_heavy * 4, hipMemcpyHostToDevice, s));
     }
     HIP_TRY(c, hipMemsetAsync(d_cursor, 0, ((size_t)NC + 1) * 4, s));
-    if (NT) hipLaunchKernelGGL(lig::k_diag_att_scatter, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, v.begin, v.n_slots, d.tb, d_cursor, d.terms);
+    if (NT) hipLaunchKernelGGL(lig::k_diag_att_scatter, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, v.begin, v.n_slots, number, d.tb, d_cursor, d.terms);
     HIP_TRY(c, hipMemsetAsync(d.rhs_index, 0, (size_t)NC * 4, s));
-    if (NR) hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, v.rhs_c, NR, d.rhs_index);
+    if (NR) hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, v.rhs_c, NR, number, d.rhs_index);
     HIP_TRY(c, hipGetLastError());
     return LIG_OK;
 }
@@ -580,7 +663,7 @@ int diag_rows(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* tri_dev
     if (sys ? sys->n_constraints : att ? att->n_constraints : 0) {
         DiagSystem d;
         if (sys) TRY(diag_upload_system(c, sc, sys, d));
-        else TRY(diag_regroup_system(c, sc, wait, &scan_tmp, &scan_cap, *att, d));
+        else TRY(diag_regroup_system(c, sc, wait, &scan_tmp, &scan_cap, *att, false, d));
         const uint32_t NC = d.NC;
         uint32_t *d_flag = nullptr, *d_pos = nullptr; fr* d_res = nullptr;
         TRY(sc.alloc((void**)&d_res, (size_t)NC * 32));
@@ -624,8 +707,9 @@ int lig_internal_rows_diagnose(lig_ctx* c, const fr* msgs, uint64_t rows, const 
 }
 int lig_internal_rows_diagnose_attached(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* tri_dev, uint64_t n_quad_terms, const lig_linear* att,
                                         lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
+    // (a sharded share: the caller is the ONE rank of its world and holds every row in commit order -- its local slots are the trace's, and
+    // diag_regroup_system numbers the segments through need[])
     const lig_linear_view v = lig_internal_linear_view(att);
-    if (v.sharded) FAIL(c, LIG_E_STATE, "lig_rows_diagnose_attached: the attached structure is one rank's share of a sharded trace");
     return diag_rows(c, msgs, rows, tri_dev, n_quad_terms, nullptr, &v, lin_out, lin_cap, quad_out, quad_cap, info);
 }
 
@@ -682,7 +766,7 @@ int explain_rows(lig_ctx* c, const fr* msgs, const lig_linear_system* sys, const
         TRY(sc.alloc((void**)&d_items, (size_t)m * sizeof(lig::ExplainItem)));
         if (m) hipLaunchKernelGGL(lig::k_explain_collect, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, v.begin, v.n_slots, d_mark, d_pos, d_items);
         HIP_TRY(c, hipMemsetAsync(d.rhs_index, 0, (size_t)NC * 4, s));
-        if (NR) hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, v.rhs_c, NR, d.rhs_index);
+        if (NR) hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, v.rhs_c, NR, nullptr, d.rhs_index);
         HIP_TRY(c, hipGetLastError());
     }
     // the m items -> the output order, on the host (explain_plan.hpp)
@@ -767,15 +851,23 @@ int lig_internal_rows_read_slots(lig_ctx* c, const fr* msgs, uint64_t rows, cons
 //   quadratic  every term is local to one rank: the one-GPU pass over the local terms, global rows through `grow`, at most quad_cap records
 //              kept with the terms' global ordinals; one all-gather of [count, kept | records | ordinals], merged by (ordinal, column).
 // Every send buffer is an allocation of its own; v.forget runs before any of them is freed.
-int lig_internal_shard_diagnose(lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out,
-                                uint64_t quad_cap, lig_diag_info* info) {
+// The linear statement is `sys` (the term list of the WHOLE trace; it has passed lig_linear_check) or `att` (the view of the rank's share
+// attached to the shard), at most one of them.  Where the partials of a slice come from is all that differs:
+//   sys   the uploaded list walked through the rank's global -> local row table (k_diag_lin_part*); the owner subtracts b_c (k_diag_reduce<true>)
+//   att   the share regrouped by compact constraint (diag_regroup_system), the slice as a compact range (k_diag_att_bounds), the send buffer
+//         zeroed, k_diag_att_part* with b_c subtracted by its one holder; the owner only adds (k_diag_reduce<false>).  No host pass over the
+//         terms, no upload; the table in force is read in place behind its event.  Scratch instead of the uploaded system:
+//         8 kept terms + 12 (n_need + 1) + 4 (slices + 1) and the short heavy lists.
+namespace {
+int shard_diagnose(const char* who, lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, const lig_linear_view* att, lig_diag_linear* lin_out,
+                   uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
     hipStream_t s = c->stream;
     const uint32_t l = c->l, k = c->k, W = v.world;
     const uint64_t l_recip = diag_reciprocal(l);
     DiagScratch sc(c);
     void* scan_tmp = nullptr; size_t scan_cap = 0;
     bool used_comm = false;
-    const DiagWait wait = [&v]() -> int { return v.drain("lig_shard_rows_diagnose"); };
+    const DiagWait wait = [&v, who]() -> int { return v.drain(who); };
     // LIG_TRACE: a synchronised split of the call into its phases on stderr
     const bool trace_on = lig::knobs().trace;
     enum { PH_PARTIAL, PH_EXCHANGE, PH_REDUCE, PH_RECORDS, PH_QUAD, PH_N };
@@ -788,21 +880,26 @@ int lig_internal_shard_diagnose(lig_ctx* c, const lig_diag_shard& v, const lig_l
         t_mark = clk::now();
         return LIG_OK;
     };
-    std::vector<uint32_t> local_of, grow32, ord32;      // (sources of queued uploads: they live until the call returns)
+    std::vector<uint32_t> local_of, grow32, ord32, heavy_global;      // (sources / targets of queued copies: they live until the call returns)
     std::vector<uint8_t> gathered;
     uint64_t header[2] = {0, 0}, qheader[2] = {0, 0};
 
     auto body = [&]() -> int {
         // ---------------------------------------------------------------- linear constraints
-        if (sys && sys->n_constraints) {
+        if (sys ? sys->n_constraints : att ? att->n_constraints : 0) {
             DiagSystem d;
-            TRY(diag_upload_system(c, sc, sys, d));
-            const uint32_t NC = d.NC;
-            local_of.assign(v.rows_global, lig::LIN_NOT_LOCAL);
-            for (size_t lr = 0; lr < v.grow->size(); lr++) local_of[(*v.grow)[lr]] = (uint32_t)lr;
-            uint32_t* d_local = nullptr;
-            TRY(sc.alloc((void**)&d_local, local_of.size() * 4));
-            if (!local_of.empty()) HIP_TRY(c, hipMemcpyAsync(d_local, local_of.data(), local_of.size() * 4, hipMemcpyHostToDevice, s));
+            const uint32_t NC = (uint32_t)(sys ? sys->n_constraints : att->n_constraints);      // constraints of the WHOLE trace
+            uint32_t *d_local = nullptr, *d_bound = nullptr;
+            if (sys) {
+                TRY(diag_upload_system(c, sc, sys, d));
+                local_of.assign(v.rows_global, lig::LIN_NOT_LOCAL);
+                for (size_t lr = 0; lr < v.grow->size(); lr++) local_of[(*v.grow)[lr]] = (uint32_t)lr;
+                TRY(sc.alloc((void**)&d_local, local_of.size() * 4));
+                if (!local_of.empty()) HIP_TRY(c, hipMemcpyAsync(d_local, local_of.data(), local_of.size() * 4, hipMemcpyHostToDevice, s));
+            } else {
+                if (att->rows_local != v.grow->size()) FAIL(c, LIG_E_STATE, std::string(who) + ": the attached share was made for another deal");
+                TRY(diag_regroup_system(c, sc, wait, &scan_tmp, &scan_cap, *att, true, d));
+            }
             const uint64_t SL = std::max<uint64_t>(v.slice, 1);
             const uint32_t B = (uint32_t)(NC <= SL ? ((uint64_t)NC + W - 1) / W : std::max<uint64_t>(SL / W, 1));      // constraints per sub-block
             const uint64_t SE = (uint64_t)B * W, n_slices = (NC + SE - 1) / SE;                                         // constraints per slice, slices
@@ -819,18 +916,49 @@ int lig_internal_shard_diagnose(lig_ctx* c, const lig_diag_shard& v, const lig_l
             HIP_TRY(c, hipMemsetAsync(d_flag, 0, ((size_t)B + 1) * 4, s));
             lig_diag_linear* d_rec = reinterpret_cast<lig_diag_linear*>(d_gsend + 16);
             uint64_t bad_mine = 0, rep_mine = 0;
-            TRY(mark(PH_RECORDS));      // (uploads, table conversion)
+            // the heavy constraints by their numbers of the whole trace, ascending: the uploaded list's own, or need[] of the compact ones
+            const std::vector<uint32_t>* heavy_c = &d.heavy;
+            if (att) {
+                TRY(sc.alloc((void**)&d_bound, ((size_t)n_slices + 1) * 4));
+                hipLaunchKernelGGL(lig::k_diag_att_bounds, dim3(diag_grid(n_slices + 1)), dim3(lig::LIN_WG), 0, s, att->need, d.NC, SE, (uint32_t)n_slices, (uint64_t)NC, d_bound);
+                HIP_TRY(c, hipGetLastError());
+                if (!d.heavy.empty()) {
+                    const uint32_t NH = (uint32_t)d.heavy.size();
+                    uint32_t* d_hg = nullptr;
+                    TRY(sc.alloc((void**)&d_hg, (size_t)NH * 4));
+                    heavy_global.resize(NH);
+                    hipLaunchKernelGGL(lig::k_diag_att_heavy_global, dim3(diag_grid(NH)), dim3(lig::LIN_WG), 0, s, d.heavy_dev, NH, att->need, d_hg);
+                    HIP_TRY(c, hipGetLastError());
+                    HIP_TRY(c, hipMemcpyAsync(heavy_global.data(), d_hg, (size_t)NH * 4, hipMemcpyDeviceToHost, s));
+                    TRY(wait());
+                    if (!std::is_sorted(heavy_global.begin(), heavy_global.end())) FAIL(c, LIG_E_STATE, std::string(who) + ": the attached share's need list is not ascending");
+                }
+                heavy_c = &heavy_global;
+            }
+            TRY(mark(PH_RECORDS));      // (uploads, table conversion; regrouping)
             for (uint64_t j = 0; j < n_slices; j++) {
                 const uint32_t c0 = (uint32_t)(j * SE), n = (uint32_t)std::min<uint64_t>(SE, NC - c0);
-                if (n < SE) HIP_TRY(c, hipMemsetAsync(d_send + n, 0, (size_t)(SE - n) * 32, s));       // beyond the end of the system: zero partials
-                hipLaunchKernelGGL(lig::k_diag_lin_part, dim3(diag_grid(n)), dim3(lig::LIN_WG), 0, s, d.tb, d.terms, c0, n, v.msgs, l, k, l_recip, d.coef, d_local, d_send);
-                HIP_TRY(c, hipGetLastError());
-                const size_t h0 = std::lower_bound(d.heavy.begin(), d.heavy.end(), c0) - d.heavy.begin();
-                const size_t h1 = std::lower_bound(d.heavy.begin(), d.heavy.end(), c0 + n) - d.heavy.begin();
-                if (h1 > h0) {
-                    hipLaunchKernelGGL(lig::k_diag_lin_part_heavy, dim3(std::min<uint32_t>((uint32_t)(h1 - h0), lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d.heavy_dev + h0,
-                                       (uint32_t)(h1 - h0), d.tb, d.terms, c0, v.msgs, l, k, l_recip, d.coef, d_local, d_send);
+                const size_t h0 = std::lower_bound(heavy_c->begin(), heavy_c->end(), c0) - heavy_c->begin();
+                const size_t h1 = std::lower_bound(heavy_c->begin(), heavy_c->end(), c0 + n) - heavy_c->begin();
+                if (sys) {
+                    if (n < SE) HIP_TRY(c, hipMemsetAsync(d_send + n, 0, (size_t)(SE - n) * 32, s));       // beyond the end of the system: zero partials
+                    hipLaunchKernelGGL(lig::k_diag_lin_part, dim3(diag_grid(n)), dim3(lig::LIN_WG), 0, s, d.tb, d.terms, c0, n, v.msgs, l, k, l_recip, d.coef, d_local, d_send);
                     HIP_TRY(c, hipGetLastError());
+                    if (h1 > h0) {
+                        hipLaunchKernelGGL(lig::k_diag_lin_part_heavy, dim3(std::min<uint32_t>((uint32_t)(h1 - h0), lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d.heavy_dev + h0,
+                                           (uint32_t)(h1 - h0), d.tb, d.terms, c0, v.msgs, l, k, l_recip, d.coef, d_local, d_send);
+                        HIP_TRY(c, hipGetLastError());
+                    }
+                } else {
+                    HIP_TRY(c, hipMemsetAsync(d_send, 0, (size_t)SE * 32, s));      // the constraints this rank does not need, and those beyond the end
+                    hipLaunchKernelGGL(lig::k_diag_att_part, dim3(diag_grid(std::min<uint64_t>(n, d.NC))), dim3(lig::LIN_WG), 0, s, d_bound + j, d.tb, d.terms, att->need, c0, n,
+                                       v.msgs, l, k, l_recip, d.coef, d.rhs_index, d.rhs_coef, d_send);
+                    HIP_TRY(c, hipGetLastError());
+                    if (h1 > h0) {
+                        hipLaunchKernelGGL(lig::k_diag_att_part_heavy, dim3(std::min<uint32_t>((uint32_t)(h1 - h0), lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s,
+                                           d.heavy_dev + h0, (uint32_t)(h1 - h0), d.tb, d.terms, att->need, c0, n, v.msgs, l, k, l_recip, d.coef, d.rhs_index, d.rhs_coef, d_send);
+                        HIP_TRY(c, hipGetLastError());
+                    }
                 }
                 TRY(mark(PH_PARTIAL));
                 used_comm = true;
@@ -838,8 +966,10 @@ int lig_internal_shard_diagnose(lig_ctx* c, const lig_diag_shard& v, const lig_l
                 TRY(mark(PH_EXCHANGE));
                 const uint64_t first = (uint64_t)c0 + (uint64_t)v.rank * B;                             // my sub-block of this slice
                 const uint32_t n_valid = first < NC ? (uint32_t)std::min<uint64_t>(B, NC - first) : 0u;
-                hipLaunchKernelGGL(lig::k_diag_reduce, dim3(diag_grid(B)), dim3(lig::LIN_WG), 0, s, d_recv, W, B, n_valid, (uint32_t)std::min<uint64_t>(first, NC), d.rhs_index,
-                                   d.rhs_coef, d.coef, d_res, d_flag);
+                if (sys) hipLaunchKernelGGL(lig::k_diag_reduce<true>, dim3(diag_grid(B)), dim3(lig::LIN_WG), 0, s, d_recv, W, B, n_valid, (uint32_t)std::min<uint64_t>(first, NC),
+                                            d.rhs_index, d.rhs_coef, d.coef, d_res, d_flag);
+                else hipLaunchKernelGGL(lig::k_diag_reduce<false>, dim3(diag_grid(B)), dim3(lig::LIN_WG), 0, s, d_recv, W, B, n_valid, (uint32_t)std::min<uint64_t>(first, NC),
+                                        (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const fr*)nullptr, d_res, d_flag);
                 HIP_TRY(c, hipGetLastError());
                 TRY(mark(PH_REDUCE));
                 uint32_t bad = 0;
@@ -937,9 +1067,20 @@ int lig_internal_shard_diagnose(lig_ctx* c, const lig_diag_shard& v, const lig_l
     if (rc == LIG_OK) (void)wait();
     if (used_comm) v.forget();                                                // before any send buffer is freed (lig_comm.forget)
     if (trace_on && rc == LIG_OK)
-        std::fprintf(stderr, "[lig_trace] shard_diagnose rank %u: partial %.3f exchange %.3f reduce %.3f records %.3f quadratic %.3f ms\n", v.rank, ph[PH_PARTIAL],
-                     ph[PH_EXCHANGE], ph[PH_REDUCE], ph[PH_RECORDS], ph[PH_QUAD]);
+        std::fprintf(stderr, "[lig_trace] shard_diagnose%s rank %u: partial %.3f exchange %.3f reduce %.3f records %.3f quadratic %.3f ms\n", att ? "_attached" : "", v.rank,
+                     ph[PH_PARTIAL], ph[PH_EXCHANGE], ph[PH_REDUCE], ph[PH_RECORDS], ph[PH_QUAD]);
     return rc;
+}
+}  // namespace
+int lig_internal_shard_diagnose(lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out,
+                                uint64_t quad_cap, lig_diag_info* info) {
+    return shard_diagnose("lig_shard_rows_diagnose", c, v, sys, nullptr, lin_out, lin_cap, quad_out, quad_cap, info);
+}
+int lig_internal_shard_diagnose_attached(lig_ctx* c, const lig_diag_shard& v, const lig_linear* att, lig_diag_linear* lin_out, uint64_t lin_cap,
+                                         lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
+    const lig_linear_view view = lig_internal_linear_view(att);
+    if (!view.sharded) FAIL(c, LIG_E_STATE, "lig_shard_rows_diagnose_attached: the attached structure is not a rank's share of a sharded trace");
+    return shard_diagnose("lig_shard_rows_diagnose_attached", c, v, nullptr, &view, lin_out, lin_cap, quad_out, quad_cap, info);
 }
 
 namespace {

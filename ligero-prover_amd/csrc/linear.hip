@@ -512,13 +512,14 @@ int lig_internal_linear_set_values(lig_ctx* c, lig_linear* L, const uint8_t* coe
     L->coef = L->vals;
     return LIG_OK;
 }
-// what lig_rows_diagnose_attached (diagnose.hip) reads of an attachment; nothing of it is written through the view
+// what lig_rows_diagnose_attached / lig_shard_rows_diagnose_attached (diagnose.hip) read of an attachment; nothing of it is written through the view
 lig_linear_view lig_internal_linear_view(const lig_linear* L) {
     const lig_linear_program* P = L->P;
     lig_linear_view v;
     v.sharded = P->sharded;
     v.n_constraints = P->n_constraints; v.n_terms = P->n_terms; v.n_rhs = P->n_rhs; v.n_slots = P->n_slots;
     v.begin = P->begin; v.ent = P->ent; v.rhs_c = P->rhs_c; v.rhs_coef = P->rhs_coef;
+    v.need = P->need; v.n_need = P->n_need; v.rows_local = P->sharded ? P->rows : 0;
     v.coef = L->coef;
     v.coef_ready = L->coef == L->vals && L->vals ? L->ev_mont : nullptr;
     return v;

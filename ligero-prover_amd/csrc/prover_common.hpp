@@ -460,6 +460,10 @@ struct lig_linear_view {
     bool sharded = false;                              // one rank's local, compactly numbered structure: not a system of the whole trace
     uint64_t n_constraints = 0, n_terms = 0, n_rhs = 0;
     uint32_t n_slots = 0;
+    // sharded: begin[] covers the LOCAL slots of rows_local rows, n_terms = the terms kept, n_rhs = the rank's slice of the right-hand sides;
+    // ent[].x and rhs_c[] are COMPACT numbers i < n_need, need[i] = the constraint of the whole trace (ascending); n_constraints stays global
+    const uint32_t* need = nullptr;
+    uint64_t n_need = 0, rows_local = 0;
     const uint32_t* begin = nullptr;
     const uint2* ent = nullptr;
     const uint32_t *rhs_c = nullptr, *rhs_coef = nullptr;
@@ -505,6 +509,10 @@ struct lig_diag_shard {
 };
 int lig_internal_shard_diagnose(lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out,
                                 uint64_t quad_cap, lig_diag_info* info);
+// lig_shard_rows_diagnose_attached: the same collective schedule over the rank's share ATTACHED to the shard (`att`: sharded), regrouped by
+// compact constraint on the device; the holder of a right-hand side subtracts it in its partial
+int lig_internal_shard_diagnose_attached(lig_ctx* c, const lig_diag_shard& v, const lig_linear* att, lig_diag_linear* lin_out, uint64_t lin_cap,
+                                         lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info);
 // lig_shard_rows_explain / lig_shard_rows_read_slots (diagnose.hip) on the same view (all_to_all is not used): sys has passed
 // lig_linear_check, asked explain_asked_ok, the slots explain_slots_ok against the rows of the whole trace; n_asked > 0, n_slots > 0.
 int lig_internal_shard_explain(lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, const uint32_t* asked, uint64_t n_asked,

@@ -970,6 +970,34 @@ int lig_shard_rows_diagnose(lig_shard* S, const lig_linear_system* sys, lig_diag
     return LIG_OK;
 }
 
+// lig_shard_rows_diagnose against the share of the system ATTACHED to the shard (lig_shard_rows_set_linear), with the values of
+// lig_shard_rows_set_linear_values in force: no term list, no host pass, no upload (diagnose.hip).  Window, refusals and poisoning as above.
+int lig_shard_rows_diagnose_attached(lig_shard* S, lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
+    if (!S || !info || info->struct_bytes < sizeof(lig_diag_info)) return LIG_E_ARG;
+    if ((lin_cap && !lin_out) || (quad_cap && !quad_out)) return LIG_E_ARG;
+    const auto t_begin = clk::now();
+    SHARD_COMMON;
+    (void)n;
+    CHECK_CTX(c);
+    if (S->poisoned) FAIL(c, LIG_E_STATE, "lig_shard_rows_diagnose_attached: the shard is poisoned (work queued behind a failed collective never drained): destroy it");
+    if (!S->from_rows) FAIL(c, LIG_E_STATE, "lig_shard_rows_diagnose_attached: not a rows shard (lig_shard_rows_begin)");
+    if (!S->diag_ok) FAIL(c, LIG_E_STATE, "lig_shard_rows_diagnose_attached: no committed matrix (between lig_shard_rows_commit and the next lig_shard_rows_restart)");
+    if (!S->linear) FAIL(c, LIG_E_STATE, "lig_shard_rows_diagnose_attached: no linear system is set (lig_shard_rows_set_linear)");
+    const uint32_t struct_bytes = info->struct_bytes;
+    std::memset(info, 0, sizeof *info);
+    info->struct_bytes = struct_bytes;
+    ShardDebugScope dbg(S, "diagnose_attached", nullptr);
+    if (W == 1 && !S->exchange_even_alone) {       // one rank holds every row in commit order: lig_rows_diagnose_attached on its matrix, no collective
+        TRY(lig_internal_rows_diagnose_attached(c, S->msgs, R, S->tri_dev, S->triple_ord.size(), S->linear, lin_out, lin_cap, quad_out, quad_cap, info));
+        info->ms_total = ms_since(t_begin);
+        return LIG_OK;
+    }
+    SHARD_DIAG_VIEW(v);
+    TRY(lig_internal_shard_diagnose_attached(c, v, S->linear, lin_out, lin_cap, quad_out, quad_cap, info));
+    info->ms_total = ms_since(t_begin);
+    return LIG_OK;
+}
+
 // lig_rows_explain / lig_rows_read_slots on a rows shard (diagnose.hip): collective, every rank obtains the bytes of the one-GPU call on the
 // whole trace.  Window, state checks and refusals as lig_shard_rows_diagnose: decided here, on the host, identically on every rank, before
 // anything is launched and before any collective.
@@ -1042,6 +1070,18 @@ int lig_shard_rows_set_linear(lig_shard* S, const lig_linear_system* sys) {
     lig_internal_linear_destroy(S->linear);
     S->linear = L;
     return LIG_OK;
+}
+// The values of the coefficient table of the system set above, for the proofs that follow: what lig_rows_set_linear_values is on one GPU.
+// They belong to the rank's attachment; host check, pinned copy, upload and k_lin_coefs_mont on the side stream -- the stream
+// shard_stage23 forms on, so a form queued later reads the converted table.  No collective: every rank passes the same table (contract).
+int lig_shard_rows_set_linear_values(lig_shard* S, const uint8_t* coefs, uint64_t n_coefs) {
+    if (!S) return LIG_E_ARG;
+    lig_ctx* c = S->c;
+    CHECK_CTX(c);
+    if (S->poisoned) FAIL(c, LIG_E_STATE, "lig_shard_rows_set_linear_values: the shard is poisoned (work queued behind a failed collective never drained): destroy it");
+    if (!S->from_rows) FAIL(c, LIG_E_STATE, "lig_shard_rows_set_linear_values: not a rows shard (lig_shard_rows_begin)");
+    if (!S->linear) FAIL(c, LIG_E_STATE, "lig_shard_rows_set_linear_values: no linear system is set (lig_shard_rows_set_linear)");
+    return lig_internal_linear_set_values(c, S->linear, coefs, n_coefs, c->stream2);
 }
 int lig_shard_rows_linear_stats(const lig_shard* S, uint64_t* local_terms, uint64_t* sampled_constraints) {
     if (!S || !local_terms || !sampled_constraints) return LIG_E_ARG;

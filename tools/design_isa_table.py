@@ -13,7 +13,8 @@ KERNELS = ["k_encode_in<10>", "k_encode_tiles<10, true>", "k_encode_tiles<10, fa
            "k_encode_out_dot_z<10>", "k_gather_rows_z<10>", "k_sha_update_rows", "k_sha_update_rows_ws<2>", "k_sha_update_rows_z<10, 2>", "k_rand_rlc<4, 0>", "k_rand_rlc<4, 1>", "k_rng_fill_rows_dense<4, 0>", "k_rlc_partial",
            "k_quad_rows<EvenOfView>", "k_merkle_level", "k_tiled_pass1<7, false>", "k_tiled_pass2<8>", "k_div_batched<4>",
            "k_lin_form", "k_lin_heavy_part", "k_lin_coefs_mont", "k_rng_fill_indexed<4, 0>", "k_expand_narrow", "k_expand_wide", "k_expand_product<false>", "k_expand_product<true>",
-           "k_diag_lin", "k_diag_lin_heavy", "k_diag_quad", "k_diag_lin_part", "k_diag_lin_part_heavy", "k_diag_reduce",
+           "k_diag_lin", "k_diag_lin_heavy", "k_diag_quad", "k_diag_lin_part", "k_diag_lin_part_heavy", "k_diag_reduce<true>", "k_diag_reduce<false>",
+           "k_diag_att_bounds", "k_diag_att_part", "k_diag_att_part_heavy",
            "k_explain_mark", "k_explain_collect", "k_explain_gather", "k_explain_fill<ExplainFromMatrix>", "k_explain_finish<ExplainFromMatrix>", "k_read_slots",
            "k_explain_part", "k_explain_sum", "k_explain_fill<ExplainFromValues>", "k_explain_finish<ExplainFromValues>"]
 BEGIN, END = "<!-- isa-table:begin -->", "<!-- isa-table:end -->"
