@@ -774,7 +774,8 @@ int lig_shard_rows_diagnose(lig_shard *shard, const lig_linear_system *sys, lig_
  * SCRATCH lives for the call only, on the context's main stream (lig_comm.forget runs before any send buffer is freed); nothing the
  * attachment owns is written, and the envelope of a shard diagnosed this way is byte-identical to that of one that was not.  In the
  * formula of lig_shard_rows_diagnose the uploaded system is replaced by 8 bytes per local term, 12 per needed constraint and 4 per slice.
- * Not done: an attached explain on a shard, sharing a prepared program between ranks, caching the regrouped list between calls. */
+ * The terms, coefficients and witness values of the constraints it names: lig_shard_rows_explain_attached below.
+ * Not done: sharing a prepared program between ranks, caching the regrouped list between calls. */
 int lig_shard_rows_diagnose_attached(lig_shard *shard, lig_diag_linear *lin_out, uint64_t lin_cap, lig_diag_quad *quad_out,
                                      uint64_t quad_cap, lig_diag_info *info);
 
@@ -812,11 +813,58 @@ int lig_shard_rows_diagnose_attached(lig_shard *shard, lig_diag_linear *lin_out,
  * its own); the work runs on the context's main stream.  explain: 32 P (send) + 32 W P (receive) + 32 m (values) + 8 m (ordered
  * terms) + 32 n_coefs + 16 n_asked + 4 bytes per row of the trace, and the records, 88 n_asked + 84 min(m, term_cap); read_slots:
  * 68 P + 32 W P + 4 bytes per row of the trace.
- * Not done: an attached variant (a rank's attached structure is local and compactly numbered: the term list is the caller's); an
- * all-to-all, reduce and all-gather instead of the all-gather, which would halve the bytes (the calls are for short lists). */
+ * The caller who has released the term list: lig_shard_rows_explain_attached below.  Not done: an all-to-all, reduce and all-gather
+ * instead of the all-gather, which would halve the bytes (the calls are for short lists). */
 int lig_shard_rows_explain(lig_shard *shard, const lig_linear_system *sys, const uint32_t *constraints, uint64_t n_asked,
                            lig_explain_constraint *con_out, lig_explain_term *terms_out, uint64_t term_cap, lig_explain_info *info);
 int lig_shard_rows_read_slots(lig_shard *shard, const uint32_t *slots, uint64_t n_slots, uint8_t *values /* n_slots x 32 */);
+/* lig_shard_rows_explain against the system ATTACHED to the shard (lig_shard_rows_set_linear), with the values of
+ * lig_shard_rows_set_linear_values in force if any: the statement lig_shard_rows_prove(local_rands = NULL, const_sum = NULL) would
+ * prove.  What lig_rows_explain_attached is on one GPU: no term list on any rank, no hand-passed "table of THIS statement"; a table still
+ * converting on the side stream is waited for with its event, not with a device-wide synchronise.
+ * COLLECTIVE: every rank passes the same asked list and the same term_cap.  EVERY RANK RECEIVES THE SAME BYTES, and they are exactly what
+ * lig_shard_rows_explain returns for the term list of that system under the table in force -- and hence what lig_rows_explain_attached
+ * returns on a one-GPU trace of the same rows: order (ascending asked constraint, slot, coef_index as an unsigned number), first_term,
+ * n_terms, rhs, residual, coefficient values, witness values, reserved fields zero, n_terms_total, n_terms_reported.  A term the system
+ * holds twice appears twice; a constraint with a right-hand side and no term anywhere has n_terms = 0 and residual -b_c; con_out is
+ * complete whatever term_cap is.  info->ms_total is the rank's own.
+ * WINDOW, FAILURE, POISONING as lig_shard_rows_explain: from the return of lig_shard_rows_commit until the next lig_shard_rows_restart,
+ * before or after the proof; nothing a proof, the attachment or the table depends on is written (the envelope of an explained shard is
+ * byte-identical to that of one that was not).
+ * REFUSALS are decided on the host, identically on every rank, before any launch and any collective.  LIG_E_ARG: a NULL shard; a NULL or
+ * short *info; constraints or con_out NULL with n_asked > 0; terms_out NULL with term_cap > 0; an asked list that is not strictly
+ * ascending or names a constraint >= the system's n_constraints.  LIG_E_STATE: no system set, before the commit, a shard not made by
+ * lig_shard_rows_begin, a poisoned shard.  n_asked == 0: LIG_OK, no launch, no collective.
+ * HOW: a rank keeps exactly the terms whose row it was dealt, so the value of every term it holds is in its own local matrix and no value
+ * is requested from a peer.
+ *   1. select, on every rank's device: one lane per entry of the rank's slot-major index marks the entries whose constraint is asked (the
+ *      compact number through the need list, then a binary search over the ascending asked list), a scan of the marks, and a collect
+ *      without atomics into 48-byte records {position in the asked list, slot of the WHOLE trace, coef_index, valid = 1, the canonical
+ *      committed w}: the local slot goes through the rank's local-row -> global-row table, the value comes from the local matrix.  The
+ *      rank's count m_r comes back with the scan.
+ *   2. ONE header all-gather whose size n_asked alone fixes (16 + 8 n_asked bytes per rank, n_asked rounded up to even): m_r, and per
+ *      asked constraint whether this rank's slice of the right-hand sides holds its b_c and under which coefficient index -- two fields,
+ *      LIG_COEF_ONE being 0xFFFFFFFF; a right-hand side has exactly one holder.  Afterwards every rank knows every m_r.
+ *   3. with M = max m_r and P = min(M, LIG_DIAG_SLICE): ceil(M / P) all-gathers of 48 P bytes per rank; a rank's block beyond its own m_r
+ *      is zeroed (valid = 0).  M = 0: none.
+ *   4. every rank holds all sum m_r records: the 12-byte heads are put into the output order on the host (a total order: the result
+ *      depends neither on rank order nor on the order inside a block), a kernel permutes the values, which never left the device, into
+ *      that order, and the fill and finish kernels of lig_shard_rows_explain write the records, b_c from the header, the table in force
+ *      read in place.
+ * A collective's schedule never depends on a rank's OWN share.  Step 3 is the one place where the NUMBER of collectives depends on what the
+ * ranks hold -- but only through the m_r every rank received in step 2, so every rank issues the same schedule.  A malformed block (a
+ * record that names no asked constraint, counts that do not add up, two holders of one b_c, sum m_r >= 2^32) is LIG_E_STATE, never an
+ * index.
+ * world == 1 without LIG_SHARD_FORCE_EXCHANGE: no collective -- the same passes over the rank's share, which is compactly numbered
+ * through its need list all the same, with a device copy in place of every all-gather; with the knob set the exchange path runs with one
+ * rank.
+ * SCRATCH lives for the call only, on the context's main stream (every send buffer is an allocation of its own, lig_comm.forget runs
+ * before any of them is freed, and the scratch is abandoned when the shard is poisoned).  With T = the rank's local terms, S = sum m_r,
+ * J = ceil(M / P):  8 (T + 1) marks and positions and the scan's temporary storage, 48 m_r collected records, (W + 1) header blocks,
+ * 48 P (send) + 48 W P (receive), 16 J W P heads for the host's walk, 36 S unordered values and permutation, 44 S ordered terms, asked
+ * positions and values, 4 bytes per local row, 8 W + 16 n_asked, and the records, 88 n_asked + 84 min(S, term_cap). */
+int lig_shard_rows_explain_attached(lig_shard *shard, const uint32_t *constraints, uint64_t n_asked,
+                                    lig_explain_constraint *con_out, lig_explain_term *terms_out, uint64_t term_cap, lig_explain_info *info);
 
 /* sizeof of the public structs as this build of the library sees them, in the order {lig_batch_op, lig_synth_job, lig_proof_info,
  * lig_verify_info, lig_rows_job, lig_comm}: a binding in another language (ctypes, cgo, JNI) checks its own layouts against these at

@@ -354,7 +354,7 @@ public:
     // Both after commit(), before or after prove(), until the next commit(); the same bytes for the same statement.  std::logic_error
     // before commit().  With shard_over(): explain() is lig_shard_rows_explain, a COLLECTIVE call -- every rank calls it with the same
     // asked list and term_cap and gets the records of the unsharded batcher, whichever rank holds the rows of a term; explain_attached()
-    // stays std::logic_error there (a rank's attached structure is local and compactly numbered).
+    // stays std::logic_error there: the attached statement of a sharded batcher is shown by shard_explain_attached() below.
     void explain(const uint32_t* constraints, uint64_t n_asked, lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap,
                  lig_explain_info* info) {
         if (pass_ == 1 || !(sharded_ ? (bool)shard_ : (bool)trace_)) throw std::logic_error("hip_row_batcher::explain before commit");
@@ -377,6 +377,20 @@ public:
         if (!info) throw std::invalid_argument("hip_row_batcher::explain_attached: null info");
         info->struct_bytes = sizeof(lig_explain_info);
         check(lig_rows_explain_attached(trace_, constraints, n_asked, con_out, terms_out, term_cap, info), "lig_rows_explain_attached");
+    }
+    // explain_attached() for a batcher with shard_over(): lig_shard_rows_explain_attached (lig_hip.h), a COLLECTIVE call over every rank's
+    // share of the system as it lies on its device, with the values of set_linear_values in force -- what diagnose_attached() evaluated.
+    // Every rank calls it with the same asked list and term_cap and gets the bytes of explain() on the same batcher; no term list is
+    // read.  After commit(), before or after prove(), until the next commit().  std::logic_error on an unsharded batcher, before commit()
+    // and without a system.
+    void shard_explain_attached(const uint32_t* constraints, uint64_t n_asked, lig_explain_constraint* con_out, lig_explain_term* terms_out,
+                                uint64_t term_cap, lig_explain_info* info) {
+        if (!sharded_) throw std::logic_error("hip_row_batcher::shard_explain_attached: not a sharded batcher (explain_attached)");
+        if (pass_ == 1 || !shard_) throw std::logic_error("hip_row_batcher::shard_explain_attached before commit");
+        if (!has_linear() || !linear_on_trace_) throw std::logic_error("hip_row_batcher::shard_explain_attached without a linear system");
+        if (!info) throw std::invalid_argument("hip_row_batcher::shard_explain_attached: null info");
+        info->struct_bytes = sizeof(lig_explain_info);
+        check(lig_shard_rows_explain_attached(shard_, constraints, n_asked, con_out, terms_out, term_cap, info), "lig_shard_rows_explain_attached");
     }
     // the committed witness elements of `slots` (row * l + column over the committed rows of any kind: derived and mixed rows as the
     // device holds them; any order, repeats allowed) -> values, n_slots x 32 canonical bytes (lig_rows_read_slots).  Window as explain().

@@ -44,7 +44,7 @@ EXPORTS = [
     "lig_rows_set_linear_values", "lig_rows_verify_set_linear_values", "lig_linear_program_form",
     "lig_rows_diagnose", "lig_rows_diagnose_attached",
     "lig_rows_explain", "lig_rows_explain_attached", "lig_rows_read_slots",
-    "lig_shard_rows_explain", "lig_shard_rows_read_slots",
+    "lig_shard_rows_explain", "lig_shard_rows_read_slots", "lig_shard_rows_explain_attached",
     "lig_shard_rows_set_linear_values", "lig_shard_rows_diagnose_attached",
 ]
 
@@ -388,6 +388,7 @@ def load_library():
     L.lig_rows_read_slots.argtypes = [vp, vp, u64, vp]
     L.lig_shard_rows_explain.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
     L.lig_shard_rows_read_slots.argtypes = [vp, vp, u64, vp]
+    L.lig_shard_rows_explain_attached.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
     return L
 
 
@@ -1187,6 +1188,12 @@ class Context:
         """lig_shard_rows_explain: rows_explain on a rows shard.  Collective: every rank passes the same `system` (of the WHOLE trace, global
         slots), the same constraints and the same term_cap, and every rank gets the triple rows_explain gives for the whole trace on one GPU"""
         return self._rows_explain(self.L.lig_shard_rows_explain, (shard, C.byref(system) if system is not None else None), constraints, term_cap)
+
+    def shard_rows_explain_attached(self, shard, constraints, term_cap=4096):
+        """lig_shard_rows_explain_attached: shard_rows_explain against the system attached to the shard (shard_rows_set_linear, with the
+        values of shard_rows_set_linear_values in force): no term list is passed.  Collective: every rank passes the same constraints and
+        the same term_cap and gets the same triple as shard_rows_explain"""
+        return self._rows_explain(self.L.lig_shard_rows_explain_attached, (shard,), constraints, term_cap)
 
     def shard_rows_read_slots(self, shard, slots):
         """lig_shard_rows_read_slots: rows_read_slots on a rows shard.  Collective: every rank passes the same global slots (row * l + column

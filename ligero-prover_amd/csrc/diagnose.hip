@@ -342,6 +342,8 @@ __global__ void __launch_bounds__(LIN_WG) k_diag_scatter_quad(const uint32_t* __
 // On a rank of a sharded rows job (lig_shard_rows_explain / lig_shard_rows_read_slots) the items are formed and ordered on the host from the
 // caller's term list (explain_items_of), the values cross the ranks in pieces (k_explain_part, one all-gather, k_explain_sum), and the same
 // fill and finish run over the value list instead of the matrix (their witness source is a template parameter).
+// lig_shard_rows_explain_attached selects the items from the rank's own share with k_explain_mark and gathers whole records (its kernels
+// have a header of their own below).
 // position of c in the ascending list asked[0 .. n), n when it is not there
 static __device__ __forceinline__ uint32_t explain_find(const uint32_t* __restrict__ asked, uint32_t n, uint32_t c) {
     uint32_t lo = 0, hi = n;
@@ -352,10 +354,11 @@ static __device__ __forceinline__ uint32_t explain_find(const uint32_t* __restri
     return lo < n && asked[lo] == c ? lo : n;
 }
 struct ExplainMarked { __host__ __device__ uint32_t operator()(uint32_t mark) const { return mark ? 1u : 0u; } };
-__global__ void __launch_bounds__(LIN_WG) k_explain_mark(const uint2* __restrict__ ent, uint32_t n_terms, const uint32_t* __restrict__ asked, uint32_t n_asked,
-                                                         uint32_t* __restrict__ mark) {
+// need: NULL, or the need list of a rank's share (diag_number): the asked list always holds numbers of the whole trace
+__global__ void __launch_bounds__(LIN_WG) k_explain_mark(const uint2* __restrict__ ent, uint32_t n_terms, const uint32_t* __restrict__ need,
+                                                         const uint32_t* __restrict__ asked, uint32_t n_asked, uint32_t* __restrict__ mark) {
     for (uint64_t e = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; e < n_terms; e += (uint64_t)gridDim.x * LIN_WG) {
-        const uint32_t a = explain_find(asked, n_asked, ent[e].x);
+        const uint32_t a = explain_find(asked, n_asked, diag_number(need, ent[e].x));
         mark[e] = a < n_asked ? a + 1 : 0u;
     }
 }
@@ -461,6 +464,52 @@ __global__ void __launch_bounds__(LIN_WG) k_explain_sum(const fr* __restrict__ r
         for (uint32_t g = 1; g < W; g++) acc = fr_add(acc, fr_load(recv + (size_t)g * P + i));
         fr_store(vals + i, acc);
     }
+}
+// ---- lig_shard_rows_explain_attached: a rank keeps exactly the terms whose row it was dealt, so it selects the asked ones from its own
+// share (k_explain_mark through need[], the scan) and reads their values from its own matrix; the records cross the ranks whole.
+//   k_explain_rhs_held        one lane per right-hand side of the rank's slice: held[a] = {1, coefficient index} when its constraint is
+//                             asked constraint a (rhs_c is strictly ascending: every pair is written at most once); rhs_c[i] < n_need
+//   k_explain_collect_values  a marked entry writes its 48-byte ExplainRecord at pos[e] (k_explain_collect): the LOCAL slot of the entry is
+//                             below n_slots = rows_local * l (the host checked the product), its row indexes grow[0 .. rows_local) and the
+//                             rows_local x k matrix; the slot written is the one of the whole trace, grow[row] * l + column < 2^32 (host)
+//   k_explain_keep            piece j of the record all-gathers (recv = W blocks of P records): every head is copied for the host's walk,
+//                             the value of record r of rank g goes to vals[off[g] + j * P + r] while j * P + r < m[g] (m, off: the host's
+//                             schedule, off[g] + m[g] <= the length of vals)
+//   k_explain_permute         out[i] = in[perm[i]], perm[i] < the length of in (explain_merge)
+__global__ void __launch_bounds__(LIN_WG) k_explain_rhs_held(const uint32_t* __restrict__ rhs_c, const uint32_t* __restrict__ rhs_coef, uint32_t n_rhs,
+                                                             const uint32_t* __restrict__ need, const uint32_t* __restrict__ asked, uint32_t n_asked,
+                                                             uint2* __restrict__ held) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n_rhs; i += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t a = explain_find(asked, n_asked, diag_number(need, rhs_c[i]));
+        if (a < n_asked) held[a] = make_uint2(1u, rhs_coef[i]);
+    }
+}
+__global__ void __launch_bounds__(LIN_WG) k_explain_collect_values(const uint2* __restrict__ ent, uint32_t n_terms, const uint32_t* __restrict__ begin, uint32_t n_slots,
+                                                                   const uint32_t* __restrict__ mark, const uint32_t* __restrict__ pos,
+                                                                   const uint32_t* __restrict__ grow, const fr* __restrict__ msgs, uint32_t l, uint32_t k,
+                                                                   uint64_t l_recip, ExplainRecord* __restrict__ rec) {
+    for (uint64_t e = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; e < n_terms; e += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t mk = mark[e];
+        if (!mk) continue;
+        const uint32_t sl = diag_slot_of(begin, n_slots, (uint32_t)e), row = diag_div(sl, l_recip), col = sl - row * l;
+        uint4* o = reinterpret_cast<uint4*>(rec + pos[e]);
+        o[0] = make_uint4(mk - 1, grow[row] * l + col, ent[e].y, 1u);
+        fr_store(reinterpret_cast<fr*>(o + 1), fr_load(msgs + (size_t)row * k + col));
+    }
+}
+__global__ void __launch_bounds__(LIN_WG) k_explain_keep(const ExplainRecord* __restrict__ recv, uint32_t W, uint32_t P, uint64_t j, const uint32_t* __restrict__ m,
+                                                         const uint32_t* __restrict__ off, uint4* __restrict__ heads, fr* __restrict__ vals) {
+    const uint64_t n = (uint64_t)W * P;
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t g = (uint32_t)(i / P), r = (uint32_t)(i - (uint64_t)g * P);
+        const uint4* in = reinterpret_cast<const uint4*>(recv + i);
+        heads[i] = in[0];
+        const uint64_t at = j * P + r;
+        if (at < m[g]) fr_store(vals + (off[g] + at), fr_load(reinterpret_cast<const fr*>(in + 1)));
+    }
+}
+__global__ void __launch_bounds__(LIN_WG) k_explain_permute(const fr* __restrict__ in, const uint32_t* __restrict__ perm, uint32_t n, fr* __restrict__ out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG) fr_store(out + i, fr_load(in + perm[i]));
 }
 __global__ void __launch_bounds__(LIN_WG) k_read_slots(const uint32_t* __restrict__ slots, uint32_t n, const fr* __restrict__ msgs, uint32_t l, uint32_t k,
                                                        uint64_t l_recip, fr* __restrict__ out) {
@@ -759,7 +808,7 @@ int explain_rows(lig_ctx* c, const fr* msgs, const lig_linear_system* sys, const
         // values set on the side stream (lig_rows_set_linear_values): the table is read once its conversion has finished
         if (v.coef_ready) HIP_TRY(c, hipStreamWaitEvent(s, v.coef_ready, 0));
         HIP_TRY(c, hipMemsetAsync(d_mark + NT, 0, 4, s));
-        if (NT) hipLaunchKernelGGL(lig::k_explain_mark, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, d_asked, NA, d_mark);
+        if (NT) hipLaunchKernelGGL(lig::k_explain_mark, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, nullptr, d_asked, NA, d_mark);
         HIP_TRY(c, hipGetLastError());
         TRY(diag_scan(c, sc, wait, rocprim::make_transform_iterator((const uint32_t*)d_mark, lig::ExplainMarked{}), d_pos, NT, &scan_tmp, &scan_cap, &m));
         if (m > NT) FAIL(c, LIG_E_STATE, "lig_rows_explain_attached: counted more asked terms than the attached program holds");
@@ -1213,6 +1262,180 @@ int lig_internal_shard_explain(lig_ctx* c, const lig_diag_shard& v, const lig_li
     if (trace_on)
         std::fprintf(stderr, "[lig_trace] shard_explain rank %u: part %.3f exchange %.3f sum %.3f records %.3f ms\n", v.rank, ph[XPH_PART], ph[XPH_EXCHANGE], ph[XPH_SUM],
                      ph[XPH_RECORDS]);
+    return LIG_OK;
+}
+
+// One rank of a sharded rows job (lig_shard_rows_explain_attached, lig_hip.h).  att = the rank's share attached to the shard (sharded);
+// asked has passed explain_asked_ok against the view's n_constraints (the global count), n_asked > 0.  alone: the one rank of its world
+// without LIG_SHARD_FORCE_EXCHANGE -- the same passes, a device copy in place of every all-gather, no collective.
+// Collective: ONE header all-gather of 4 explain_header_words(n_asked) bytes per rank (m_r, and who holds which b_c), then -- with
+// M = max m_r, known on every rank from the headers -- explain_piece_count(M, P) all-gathers of 48 P bytes per rank,
+// P = explain_piece_size(M, LIG_DIAG_SLICE).  The number of record all-gathers depends on what the ranks hold, but only through numbers every
+// rank has received: every rank issues the same schedule.
+// Scratch: 8 (n_terms + 1) marks and positions over the local terms, 48 m_r collected records, (W + 1) header blocks, 48 P (send) +
+// 48 W P (receive), 16 W P per piece for the heads, 32 sum m_r unordered values + 4 sum m_r permutation, 44 sum m_r ordered terms, asked
+// positions and values, 4 per local row, 8 W, 16 n_asked, and the records: 88 n_asked + 84 min(sum m_r, term_cap).  Every send buffer is an
+// allocation of its own; v.forget runs before any of them is freed.
+int lig_internal_shard_explain_attached(lig_ctx* c, const lig_diag_shard& v, const lig_linear* att, bool alone, const uint32_t* asked, uint64_t n_asked,
+                                        lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info) {
+    static const char* const who = "lig_shard_rows_explain_attached";
+    hipStream_t s = c->stream;
+    const lig_linear_view a = lig_internal_linear_view(att);
+    const uint32_t NA = (uint32_t)n_asked, W = v.world, l = c->l, k = c->k, NT = (uint32_t)a.n_terms, NR = (uint32_t)a.n_rhs;
+    const uint64_t rows_local = v.grow->size();
+    // what the kernels index with: the local slots tile the rank's rows, a slot of the whole trace fits 32 bits
+    if (!a.sharded || a.rows_local != rows_local || (uint64_t)a.n_slots != rows_local * l || v.rows_global * (uint64_t)l > (1ull << 32) || a.n_terms >= (1ull << 32) ||
+        (NT && !rows_local) || v.rank >= W || (alone && W != 1))
+        FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: the attached structure is not this rank's share of the sharded trace");
+    for (size_t lr = 0; lr < rows_local; lr++)
+        if ((*v.grow)[lr] >= v.rows_global) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: a local row lies outside the trace");
+    // (sources and targets of queued copies: declared before the scratch, whose destructor drains the stream)
+    std::vector<uint32_t> grow32(v.grow->begin(), v.grow->end()), hdr_all, heads, m32, off32, rhs_index, rhs_coef, holder, perm, first32, ask;
+    std::vector<uint64_t> m_of, first;
+    std::vector<lig::ExplainItem> items;
+    std::vector<lig_lin_term> ordered;
+    DiagScratch sc(c);
+    void* scan_tmp = nullptr; size_t scan_cap = 0;
+    bool used_comm = false;
+    const DiagWait wait = [&v]() -> int { return v.drain(who); };
+    const auto gather = [&](const void* src, void* dst, size_t bytes, const char* what) -> int {
+        if (alone) { HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s)); return LIG_OK; }
+        used_comm = true;
+        return v.all_gather(src, dst, bytes, what);
+    };
+    const bool trace_on = lig::knobs().trace;
+    enum { APH_SELECT, APH_EXCHANGE, APH_MERGE, APH_RECORDS, APH_N };
+    double ph[APH_N] = {0, 0, 0, 0};
+    auto t_mark = clk::now();
+    const auto mark = [&](int p) -> int {
+        if (!trace_on) return LIG_OK;
+        TRY(wait());
+        ph[p] += ms_since(t_mark);
+        t_mark = clk::now();
+        return LIG_OK;
+    };
+    uint32_t total = 0, rep = 0;
+
+    auto body = [&]() -> int {
+        // 1. select: mark, scan, the right-hand sides this rank holds, the header block
+        const size_t hw = (size_t)lig::explain_header_words(NA);
+        uint32_t *d_asked = nullptr, *d_mark = nullptr, *d_pos = nullptr, *d_grow = nullptr, *d_hdr = nullptr, *d_hdr_all = nullptr;
+        TRY(sc.alloc((void**)&d_asked, (size_t)NA * 4));
+        TRY(sc.alloc((void**)&d_mark, ((size_t)NT + 1) * 4));
+        TRY(sc.alloc((void**)&d_pos, ((size_t)NT + 1) * 4));
+        TRY(sc.alloc((void**)&d_grow, (size_t)rows_local * 4));
+        TRY(sc.alloc((void**)&d_hdr, hw * 4));
+        TRY(sc.alloc((void**)&d_hdr_all, (size_t)W * hw * 4));
+        HIP_TRY(c, hipMemcpyAsync(d_asked, asked, (size_t)NA * 4, hipMemcpyHostToDevice, s));
+        if (rows_local) HIP_TRY(c, hipMemcpyAsync(d_grow, grow32.data(), (size_t)rows_local * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemsetAsync(d_mark + NT, 0, 4, s));
+        HIP_TRY(c, hipMemsetAsync(d_hdr, 0, hw * 4, s));
+        if (NT) hipLaunchKernelGGL(lig::k_explain_mark, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, a.ent, NT, a.need, d_asked, NA, d_mark);
+        if (NR) hipLaunchKernelGGL(lig::k_explain_rhs_held, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, a.rhs_c, a.rhs_coef, NR, a.need, d_asked, NA,
+                                   reinterpret_cast<uint2*>(d_hdr + lig::explain_header_held(0)));
+        HIP_TRY(c, hipGetLastError());
+        uint32_t m_own = 0;
+        TRY(diag_scan(c, sc, wait, rocprim::make_transform_iterator((const uint32_t*)d_mark, lig::ExplainMarked{}), d_pos, NT, &scan_tmp, &scan_cap, &m_own));
+        if (m_own > NT) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: counted more asked terms than the rank's share holds");
+        HIP_TRY(c, hipMemcpyAsync(d_hdr, d_pos + NT, 4, hipMemcpyDeviceToDevice, s));
+        lig::ExplainRecord* d_rec = nullptr;
+        TRY(sc.alloc((void**)&d_rec, (size_t)m_own * sizeof(lig::ExplainRecord)));
+        if (m_own) hipLaunchKernelGGL(lig::k_explain_collect_values, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, a.ent, NT, a.begin, a.n_slots, d_mark, d_pos, d_grow, v.msgs,
+                                      l, k, diag_reciprocal(l), d_rec);
+        HIP_TRY(c, hipGetLastError());
+        TRY(mark(APH_SELECT));
+        // 2. the headers: every m_r, the holder of every b_c
+        TRY(gather(d_hdr, d_hdr_all, hw * 4, "all_gather(counts and right-hand sides of the asked constraints)"));
+        hdr_all.resize((size_t)W * hw);
+        HIP_TRY(c, hipMemcpyAsync(hdr_all.data(), d_hdr_all, (size_t)W * hw * 4, hipMemcpyDeviceToHost, s));
+        TRY(wait());
+        if (!lig::explain_header_merge(hdr_all.data(), W, NA, m_of, rhs_index, rhs_coef, holder) || m_of[v.rank] != m_own)
+            FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: a rank's header block is malformed");
+        const lig::ExplainRecordSchedule x = lig::explain_record_schedule(m_of, v.slice);
+        if ((uint64_t)W * x.P >= (1ull << 32)) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: a piece of the record exchange exceeds 2^32 records");
+        total = (uint32_t)x.off[W];
+        rep = (uint32_t)std::min<uint64_t>(total, term_cap);
+        TRY(mark(APH_EXCHANGE));
+        // 3. the records, in pieces of P per rank; the values stay on the device, the heads go to the host
+        const size_t WP = (size_t)W * x.P;
+        lig::ExplainRecord *d_send = nullptr, *d_recv = nullptr; uint4* d_heads = nullptr; fr *d_vals_in = nullptr, *d_vals = nullptr; uint32_t *d_m = nullptr, *d_off = nullptr;
+        TRY(sc.alloc((void**)&d_send, (size_t)x.P * sizeof(lig::ExplainRecord)));
+        TRY(sc.alloc((void**)&d_recv, WP * sizeof(lig::ExplainRecord)));
+        TRY(sc.alloc((void**)&d_heads, (size_t)x.pieces * WP * 16));
+        TRY(sc.alloc((void**)&d_vals_in, (size_t)total * 32));
+        TRY(sc.alloc((void**)&d_vals, (size_t)total * 32));
+        TRY(sc.alloc((void**)&d_m, (size_t)W * 4));
+        TRY(sc.alloc((void**)&d_off, (size_t)W * 4));
+        m32.assign(m_of.begin(), m_of.end());
+        off32.assign(x.off.begin(), x.off.begin() + W);
+        HIP_TRY(c, hipMemcpyAsync(d_m, m32.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_off, off32.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
+        for (uint64_t j = 0; j < x.pieces; j++) {
+            const uint64_t lo = std::min<uint64_t>(j * x.P, m_own), n = std::min<uint64_t>(x.P, m_own - lo);      // this rank's records of the piece
+            if (n) HIP_TRY(c, hipMemcpyAsync(d_send, d_rec + lo, (size_t)n * sizeof(lig::ExplainRecord), hipMemcpyDeviceToDevice, s));
+            if (n < x.P) HIP_TRY(c, hipMemsetAsync(d_send + n, 0, (size_t)(x.P - n) * sizeof(lig::ExplainRecord), s));
+            TRY(mark(APH_SELECT));
+            TRY(gather(d_send, d_recv, (size_t)x.P * sizeof(lig::ExplainRecord), "all_gather(the asked terms of every rank)"));
+            TRY(mark(APH_EXCHANGE));
+            hipLaunchKernelGGL(lig::k_explain_keep, dim3(diag_grid(WP)), dim3(lig::LIN_WG), 0, s, d_recv, W, (uint32_t)x.P, j, d_m, d_off, d_heads + j * WP, d_vals_in);
+            HIP_TRY(c, hipGetLastError());
+            TRY(mark(APH_MERGE));
+        }
+        // 4. merge and order on the host, permute the values, the records
+        heads.resize((size_t)x.pieces * WP * 4);
+        if (!heads.empty()) HIP_TRY(c, hipMemcpyAsync(heads.data(), d_heads, heads.size() * 4, hipMemcpyDeviceToHost, s));
+        TRY(wait());
+        if (!lig::explain_records_walk(heads.data(), W, x, m_of, NA, items)) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: a rank's record block is malformed");
+        if (!lig::explain_merge(items, NA, first, perm)) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: a term names no asked constraint");
+        ordered.resize(total);
+        ask.resize(rep);
+        first32.assign(first.begin(), first.end());
+        for (uint32_t i = 0; i < total; i++) { ordered[i].slot = items[i].slot; ordered[i].coef = items[i].coef; }
+        for (uint32_t i = 0; i < rep; i++) ask[i] = items[i].ask;
+        lig_lin_term* d_ordered = nullptr; uint32_t *d_perm = nullptr, *d_ask = nullptr, *d_first = nullptr, *d_rhs_index = nullptr, *d_rhs_coef = nullptr;
+        lig_explain_constraint* d_con = nullptr; lig_explain_term* d_out = nullptr;
+        TRY(sc.alloc((void**)&d_ordered, (size_t)total * sizeof(lig_lin_term)));
+        TRY(sc.alloc((void**)&d_perm, (size_t)total * 4));
+        TRY(sc.alloc((void**)&d_ask, (size_t)rep * 4));
+        TRY(sc.alloc((void**)&d_first, ((size_t)NA + 1) * 4));
+        TRY(sc.alloc((void**)&d_rhs_index, (size_t)NA * 4));
+        TRY(sc.alloc((void**)&d_rhs_coef, (size_t)NA * 4));
+        TRY(sc.alloc((void**)&d_con, (size_t)NA * sizeof(lig_explain_constraint)));
+        TRY(sc.alloc((void**)&d_out, (size_t)rep * sizeof(lig_explain_term)));
+        if (total) {
+            HIP_TRY(c, hipMemcpyAsync(d_ordered, ordered.data(), (size_t)total * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(d_perm, perm.data(), (size_t)total * 4, hipMemcpyHostToDevice, s));
+        }
+        if (rep) HIP_TRY(c, hipMemcpyAsync(d_ask, ask.data(), (size_t)rep * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_first, first32.data(), ((size_t)NA + 1) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_rhs_index, rhs_index.data(), (size_t)NA * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_rhs_coef, rhs_coef.data(), (size_t)NA * 4, hipMemcpyHostToDevice, s));
+        if (total) hipLaunchKernelGGL(lig::k_explain_permute, dim3(diag_grid(total)), dim3(lig::LIN_WG), 0, s, d_vals_in, d_perm, total, d_vals);
+        HIP_TRY(c, hipGetLastError());
+        TRY(mark(APH_MERGE));
+        // values set on the side stream (lig_shard_rows_set_linear_values): the table is read in place once its conversion has finished
+        if (a.coef_ready) HIP_TRY(c, hipStreamWaitEvent(s, a.coef_ready, 0));
+        const lig::ExplainFromValues wit{d_vals};
+        if (rep) hipLaunchKernelGGL(lig::k_explain_fill<lig::ExplainFromValues>, dim3(diag_grid(rep)), dim3(lig::LIN_WG), 0, s, d_ordered, d_ask, rep, d_asked, wit, a.coef, d_out);
+        hipLaunchKernelGGL(lig::k_explain_finish<lig::ExplainFromValues>, dim3(std::min<uint32_t>(NA, lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d_first, d_ordered, d_asked, NA,
+                           wit, a.coef, d_rhs_index, d_rhs_coef, d_con);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(con_out, d_con, (size_t)NA * sizeof(lig_explain_constraint), hipMemcpyDeviceToHost, s));
+        if (rep) HIP_TRY(c, hipMemcpyAsync(terms_out, d_out, (size_t)rep * sizeof(lig_explain_term), hipMemcpyDeviceToHost, s));
+        TRY(wait());
+        TRY(mark(APH_RECORDS));
+        return LIG_OK;
+    };
+    const int rc = body();
+    if (rc != LIG_OK && v.settle_failed()) { sc.abandon(); return rc; }      // poisoned: the scratch outlives the call
+    if (rc == LIG_OK) (void)wait();
+    if (used_comm) v.forget();                                                // before any send buffer is freed (lig_comm.forget)
+    if (rc != LIG_OK) return rc;
+    info->n_terms_total = total;
+    info->n_terms_reported = rep;
+    if (trace_on)
+        std::fprintf(stderr, "[lig_trace] shard_explain_attached rank %u: select %.3f exchange %.3f merge %.3f records %.3f ms\n", v.rank, ph[APH_SELECT], ph[APH_EXCHANGE],
+                     ph[APH_MERGE], ph[APH_RECORDS]);
     return LIG_OK;
 }
 

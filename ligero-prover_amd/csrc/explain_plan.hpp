@@ -1,9 +1,10 @@
 // explain_plan.hpp -- the host-side rules of lig_rows_explain / lig_rows_explain_attached (lig_hip.h): which asked lists are accepted,
 // the order of the term records, and where every asked constraint's records begin in that order; and of lig_shard_rows_explain /
 // lig_shard_rows_read_slots: the items and right-hand sides of the asked constraints from the caller's term list, the piece schedule of
-// the value exchange.
+// the value exchange; and of lig_shard_rows_explain_attached: the header block of a rank, the schedule of the record all-gathers, the
+// walk over the received records and their merge into the output order.
 // Host only: nothing but lig_hip.h and the standard library, so that a plain host compiler builds it (tests/cpp/explain_plan_prog.cpp,
-// tests/cpp/shard_explain_plan_prog.cpp).
+// tests/cpp/shard_explain_plan_prog.cpp, tests/cpp/shard_explain_attached_plan_prog.cpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -89,4 +90,86 @@ inline void explain_rhs_of(const lig_linear_system& sys, const uint32_t* asked, 
 inline uint64_t explain_piece_size(uint64_t m, uint64_t slice) { return std::min<uint64_t>(m, std::max<uint64_t>(slice, 1)); }
 inline uint64_t explain_piece_count(uint64_t m, uint64_t P) { return m ? (m + P - 1) / P : 0; }
 inline uint64_t explain_piece_len(uint64_t m, uint64_t P, uint64_t j) { return std::min<uint64_t>(P, m - j * P); }
+
+// ---- lig_shard_rows_explain_attached: a rank selects the asked terms of its OWN share on its device and every rank receives all of them.
+// One collected term, as it crosses the ranks: the item, valid = 1 (a zeroed record, valid = 0, pads a rank's block), the canonical
+// committed w of the slot.  `slot` is a slot of the WHOLE trace.
+struct ExplainRecord { uint32_t ask, slot, coef, valid; uint32_t value[8]; };
+static_assert(sizeof(ExplainRecord) == 48, "k_explain_collect_values writes these 48 bytes with three 16-byte stores");
+// The header block of one rank, in 32-bit words (a multiple of four: 16-byte aligned blocks): word 0 = m_r, the terms the rank collected;
+// words 1 .. 3 zero; then per asked constraint a the pair {held, coef}: held = 1 when the rank's slice of the right-hand sides holds b_c
+// of that constraint, coef = its coefficient index then (LIG_COEF_ONE is 0xFFFFFFFF: presence cannot be folded into the index).
+inline uint64_t explain_header_words(uint64_t n_asked) { return 4 + 2 * ((n_asked + 1) & ~(uint64_t)1); }
+inline uint64_t explain_header_held(uint64_t a) { return 4 + 2 * a; }
+// The W gathered header blocks (block g from rank g) -> m[g]; rhs_index / rhs_coef as explain_rhs_of makes them; holder[a] = the rank that
+// holds b_c of asked constraint a, W when no rank does.  false, a malformed block: a non-zero reserved word, held not 0 / 1, a coefficient
+// index without held, two holders of one right-hand side, sum m_r >= 2^32.
+inline bool explain_header_merge(const uint32_t* blocks, uint32_t W, uint64_t n_asked, std::vector<uint64_t>& m, std::vector<uint32_t>& rhs_index,
+                                 std::vector<uint32_t>& rhs_coef, std::vector<uint32_t>& holder) {
+    const uint64_t words = explain_header_words(n_asked);
+    m.assign(W, 0);
+    rhs_index.assign(n_asked, 0);
+    rhs_coef.assign(n_asked, 0);
+    holder.assign(n_asked, W);
+    uint64_t total = 0;
+    for (uint32_t g = 0; g < W; g++) {
+        const uint32_t* b = blocks + (size_t)g * words;
+        if (b[1] | b[2] | b[3]) return false;
+        m[g] = b[0];
+        total += b[0];
+        for (uint64_t a = 0; a < n_asked; a++) {
+            const uint32_t held = b[explain_header_held(a)], coef = b[explain_header_held(a) + 1];
+            if (held > 1 || (!held && coef)) return false;
+            if (!held) continue;
+            if (holder[a] != W) return false;
+            holder[a] = g; rhs_index[a] = (uint32_t)a + 1; rhs_coef[a] = coef;
+        }
+        for (uint64_t w = explain_header_held(n_asked); w < words; w++) if (b[w]) return false;
+    }
+    return total < (1ull << 32);
+}
+// The record all-gathers: with M = max m_r and P = explain_piece_size(M, slice) there are explain_piece_count(M, P) of them, each of P
+// records per rank, whatever a rank holds itself (a rank pads with zeroed records).  off[g] = the records of the ranks before g,
+// off[W] = sum m_r: record i of rank g (piece i / P, entry i % P of its block) is term off[g] + i of the unordered list.
+struct ExplainRecordSchedule { uint64_t M = 0, P = 0, pieces = 0; std::vector<uint64_t> off; };
+inline ExplainRecordSchedule explain_record_schedule(const std::vector<uint64_t>& m, uint64_t slice) {
+    ExplainRecordSchedule x;
+    x.off.assign(m.size() + 1, 0);
+    for (size_t g = 0; g < m.size(); g++) { x.M = std::max(x.M, m[g]); x.off[g + 1] = x.off[g] + m[g]; }
+    x.P = explain_piece_size(x.M, slice);
+    x.pieces = explain_piece_count(x.M, x.P);
+    return x;
+}
+// The walk over the received records: heads = the first 16 bytes {ask, slot, coef, valid} of every record, pieces x W x P of them, piece
+// major, then rank, then entry.  -> items[off[g] + i] = record i of rank g: the invalid tails are dropped.  false, a malformed block:
+// a record before m_r that is not valid or names no asked constraint, a valid record past m_r.
+inline bool explain_records_walk(const uint32_t* heads, uint32_t W, const ExplainRecordSchedule& x, const std::vector<uint64_t>& m, uint64_t n_asked,
+                                 std::vector<ExplainItem>& items) {
+    items.assign((size_t)x.off[W], ExplainItem{0, 0, 0});
+    for (uint64_t j = 0; j < x.pieces; j++)
+        for (uint32_t g = 0; g < W; g++)
+            for (uint64_t r = 0; r < x.P; r++) {
+                const uint32_t* h = heads + ((j * W + g) * x.P + r) * 4;
+                const uint64_t i = j * x.P + r;
+                if (i >= m[g]) { if (h[3]) return false; continue; }
+                if (h[3] != 1 || h[0] >= n_asked) return false;
+                items[(size_t)(x.off[g] + i)] = ExplainItem{h[0], h[1], h[2]};
+            }
+    return true;
+}
+// items (the unordered list of the walk) -> the output order (explain_order) and perm: the term at position i of the output order is term
+// perm[i] of the unordered list -- where its value lies on the device.  Items that compare equal are the same term held twice: the same
+// slot, hence the same value, whichever of them perm names.
+inline bool explain_merge(std::vector<ExplainItem>& items, uint64_t n_asked, std::vector<uint64_t>& first, std::vector<uint32_t>& perm) {
+    const std::vector<ExplainItem> src = items;
+    if (!explain_order(items, n_asked, first)) return false;
+    perm.resize(src.size());
+    for (size_t i = 0; i < src.size(); i++) perm[i] = (uint32_t)i;
+    std::sort(perm.begin(), perm.end(), [&src](uint32_t a, uint32_t b) {
+        if (explain_item_less(src[a], src[b])) return true;
+        if (explain_item_less(src[b], src[a])) return false;
+        return a < b;
+    });
+    return true;
+}
 }  // namespace lig

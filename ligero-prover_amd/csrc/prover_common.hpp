@@ -518,6 +518,11 @@ int lig_internal_shard_diagnose_attached(lig_ctx* c, const lig_diag_shard& v, co
 int lig_internal_shard_explain(lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, const uint32_t* asked, uint64_t n_asked,
                                lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info);
 int lig_internal_shard_read_slots(lig_ctx* c, const lig_diag_shard& v, const uint32_t* slots, uint64_t n_slots, uint8_t* values);
+// lig_shard_rows_explain_attached: the asked constraints from the rank's share ATTACHED to the shard (`att`: sharded) -- selected on the
+// device, the records gathered whole; asked has passed explain_asked_ok against the global constraint count, n_asked > 0.  alone: one rank
+// without the forced exchange -- the same passes without a collective.
+int lig_internal_shard_explain_attached(lig_ctx* c, const lig_diag_shard& v, const lig_linear* att, bool alone, const uint32_t* asked, uint64_t n_asked,
+                                        lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info);
 
 // the batch program of a job on the device: committed rows are written to rows_out in program order (prover.hip)
 int lig_run_batch_program(lig_ctx* c, const lig_synth_job& job, fr* rows_out);

@@ -1031,6 +1031,33 @@ int lig_shard_rows_explain(lig_shard* S, const lig_linear_system* sys, const uin
     info->ms_total = ms_since(t_begin);
     return LIG_OK;
 }
+// lig_shard_rows_explain against the share of the system ATTACHED to the shard (lig_shard_rows_set_linear), with the values of
+// lig_shard_rows_set_linear_values in force: no term list, no host pass over it (diagnose.hip).  Window, refusals and poisoning as above;
+// one rank alone runs the same passes over its share (compactly numbered through need[] all the same) without a collective.
+int lig_shard_rows_explain_attached(lig_shard* S, const uint32_t* asked, uint64_t n_asked, lig_explain_constraint* con_out, lig_explain_term* terms_out,
+                                    uint64_t term_cap, lig_explain_info* info) {
+    if (!S || !info || info->struct_bytes < sizeof(lig_explain_info)) return LIG_E_ARG;
+    if ((n_asked && (!con_out || !asked)) || (term_cap && !terms_out)) return LIG_E_ARG;
+    const auto t_begin = clk::now();
+    SHARD_COMMON;
+    (void)n;
+    CHECK_CTX(c);
+    if (S->poisoned) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: the shard is poisoned (work queued behind a failed collective never drained): destroy it");
+    if (!S->from_rows) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: not a rows shard (lig_shard_rows_begin)");
+    if (!S->diag_ok) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: no committed matrix (between lig_shard_rows_commit and the next lig_shard_rows_restart)");
+    if (!S->linear) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: no linear system is set (lig_shard_rows_set_linear)");
+    if (!lig::explain_asked_ok(asked, n_asked, lig_internal_linear_view(S->linear).n_constraints))
+        FAIL(c, LIG_E_ARG, "lig_shard_rows_explain_attached: the asked constraints must be strictly ascending and below n_constraints");
+    const uint32_t struct_bytes = info->struct_bytes;
+    std::memset(info, 0, sizeof *info);
+    info->struct_bytes = struct_bytes;
+    if (!n_asked) return LIG_OK;
+    ShardDebugScope dbg(S, "explain_attached", nullptr);
+    SHARD_DIAG_VIEW(v);
+    TRY(lig_internal_shard_explain_attached(c, v, S->linear, W == 1 && !S->exchange_even_alone, asked, n_asked, con_out, terms_out, term_cap, info));
+    info->ms_total = ms_since(t_begin);
+    return LIG_OK;
+}
 int lig_shard_rows_read_slots(lig_shard* S, const uint32_t* slots, uint64_t n_slots, uint8_t* values) {
     if (!S || (n_slots && (!slots || !values))) return LIG_E_ARG;
     SHARD_COMMON;
