@@ -588,6 +588,80 @@ int lig_rows_explain_attached(lig_trace *trace, const uint32_t *constraints, uin
                               lig_explain_constraint *con_out, lig_explain_term *terms_out, uint64_t term_cap, lig_explain_info *info);
 int lig_rows_read_slots(lig_trace *trace, const uint32_t *slots, uint64_t n_slots, uint8_t *values /* n_slots x 32 */);
 
+/* ---- explain a slot: the constraints that touch it; and the witness slots no constraint touches  (csrc/diagnose.hip)
+ * lig_rows_explain* start from a constraint and show its slots; these entries start from a SLOT.  "Constraint 17 fails and names slots 123,
+ * 700 and 2500: which other constraints use slot 700, and do they hold?"  -- if all of them hold, the wrong value is elsewhere in
+ * constraint 17; if several fail, slot 700 is the culprit.  The program keeps the terms grouped by slot (begin[], ent[] of
+ * csrc/linear.hip), so the constraints through a slot are one contiguous segment of it and nothing is regrouped.
+ *   slots        n_asked slot numbers row * l + column, STRICTLY ASCENDING, each < rows * l, over the committed rows of any kind (masks
+ *                excluded); anything else is LIG_E_ARG.  A slot of a batch-kind row has no term (lig_linear_check admits none there).
+ *   slot_out     n_asked records (required when n_asked > 0), record i for asked slot i:
+ *                  row_kind    the kind of its row, LIG_ROW_DRAW_PAD masked off
+ *                  value       the canonical committed w[slot]: the 32 bytes lig_rows_read_slots returns -- on a derived row the product
+ *                              the device formed, on a record slot of a mixed row the record's value
+ *                  n_terms     ALL terms of the statement on that slot, reported or not
+ *                  first_term  the index of its first term in the full output order below (may be >= term_cap)
+ *   terms_out    the first term_cap records of the full order: ascending asked slot, then ascending constraint, then ascending coef_index
+ *                as an unsigned number (LIG_COEF_NEG_ONE, LIG_COEF_ONE come last).  A term the statement holds twice appears twice.
+ *                  coef              the canonical value the index stands for: 1, p - 1, or the table entry IN FORCE
+ *                  constraint_terms  the number of terms of that constraint (on all slots)
+ *                  residual          sum a * w - b_c of that constraint, canonical: the 32 bytes lig_rows_explain* write for it, zero
+ *                                    when it holds
+ *                Records that compare equal in this order are byte-identical: no output byte depends on an atomic, on scheduling, or on
+ *                which lig_linear_prepare of the same system made the program.  NULL with term_cap = 0 gives the counts and slot_out only.
+ *   info         n_terms_total = the terms of all asked slots, n_terms_reported = min(n_terms_total, term_cap), n_constraints_distinct =
+ *                the distinct constraints over all asked slots; ms_total = the whole call.
+ * lig_rows_explain_slots_attached uses what lig_rows_set_linear / lig_rows_attach_linear attached, with the table of
+ * lig_rows_set_linear_values in force if one is set (a conversion still running on the side stream is waited for with its event);
+ * nothing attached: LIG_E_STATE.  lig_rows_explain_slots takes `sys` AS PASSED: it goes through lig_linear_check against the trace's
+ * kinds first (LIG_E_ARG; sys == NULL is LIG_E_ARG), is regrouped by slot into a temporary program (the prepare of lig_linear_prepare:
+ * 8 n_terms + 4 rows * l device bytes and as much again in scratch) that is released before the call returns; what is attached to the
+ * trace is neither used nor modified.  For the same statement the two calls return the same bytes.
+ * How: the segment lengths of the asked slots, an exclusive scan, one lane per (constraint, coef_index) item -- whole workgroups for a
+ * slot with more than 2048 terms --, no atomic; the m 12-byte items are ordered on the host; the residuals and sizes of the distinct
+ * constraints come from the selection pass of lig_rows_explain_attached itself (no second evaluator), the values from the gather of
+ * lig_rows_read_slots.  Scratch on top of that pass: 8 n_asked + 36 n_asked for slots, lengths and values, 12 m for the items,
+ * 88 distinct + 96 min(m, term_cap) for the records.
+ *
+ * lig_rows_untouched_slots*: the slots row * l + column, column < l, of the rows of kind LINEAR / QX / QY / QZ that NO term of the
+ * statement touches -- an under-constrained witness, the classic defect of a statement recorded by hand --, in ascending order, the
+ * first `cap` of them, each with its row kind and committed value.  nonzero_only != 0 restricts the list and n_reported to the slots
+ * whose committed value is not zero (the zero fill of a short row drops out); n_untouched and n_untouched_nonzero always count all of
+ * them.  cap = 0 (`out` may then be NULL) gives the counts only; NULL with cap > 0 is LIG_E_ARG.  The flags (segment empty; value
+ * nonzero, read with 16-byte loads) go through one scan that carries both counts, then a compaction: no atomic.  The slots are processed
+ * in slices of 2^22 (16 bytes of scratch per slot of a slice, 40 per reported record); counts and offsets are carried on the host.
+ * The _attached / `sys` variants differ as above.
+ *
+ * WHEN, blocking, streams and scratch exactly as for lig_rows_explain*: inside the window of lig_rows_diagnose (LIG_E_STATE outside, and
+ * for a lig_synth_prepare trace), work enqueued on the context stream alone, scratch allocated per call and freed before it returns.
+ * Nothing a proof depends on is written (the envelope of a trace that was asked is byte-identical to that of one that was not), nothing
+ * the program or the attachment owns is written.  LIG_E_ARG: a NULL trace, a NULL or too small *info, slots == NULL or slot_out == NULL
+ * with n_asked > 0, terms_out == NULL with term_cap > 0, out == NULL with cap > 0, and the range and order errors above -- all decided
+ * on the host before anything is launched: an index out of range never reaches a kernel.  n_asked = 0 is LIG_OK and launches nothing.
+ * The new structs version themselves with struct_bytes; they are not part of lig_abi_sizes (LIG_ABI_STRUCTS stays 6).
+ * Not covered here: the sharded entry (a rank's share numbers its slots locally and holds only the terms of its rows) -- the next
+ * change, as after every one-GPU step of this line; a share of a sharded trace attached here is LIG_E_STATE. */
+typedef struct { uint32_t slot, row_kind; uint64_t n_terms, first_term; uint8_t value[32]; } lig_slot_record;                /* 56 bytes */
+typedef struct { uint32_t slot, constraint, coef_index, constraint_terms; uint8_t coef[32]; uint8_t residual[32]; } lig_slot_term; /* 80 bytes */
+typedef struct {
+    uint32_t struct_bytes, reserved;     /* sizeof(lig_slot_info) as the caller sees it; smaller than the library's: LIG_E_ARG */
+    uint64_t n_terms_total, n_terms_reported, n_constraints_distinct;
+    double   ms_total;                   /* wall time of the call */
+} lig_slot_info;                                                                                                                /* 40 bytes */
+int lig_rows_explain_slots_attached(lig_trace *trace, const uint32_t *slots, uint64_t n_asked,
+                                    lig_slot_record *slot_out, lig_slot_term *terms_out, uint64_t term_cap, lig_slot_info *info);
+int lig_rows_explain_slots(lig_trace *trace, const lig_linear_system *sys, const uint32_t *slots, uint64_t n_asked,
+                           lig_slot_record *slot_out, lig_slot_term *terms_out, uint64_t term_cap, lig_slot_info *info);
+typedef struct { uint32_t slot, row_kind; uint8_t value[32]; } lig_slot_value;                                                 /* 40 bytes */
+typedef struct {
+    uint32_t struct_bytes, reserved;     /* sizeof(lig_untouched_info) as the caller sees it; smaller than the library's: LIG_E_ARG */
+    uint64_t n_untouched, n_untouched_nonzero, n_reported;
+    double   ms_total;                   /* wall time of the call */
+} lig_untouched_info;                                                                                                           /* 40 bytes */
+int lig_rows_untouched_slots_attached(lig_trace *trace, int nonzero_only, lig_slot_value *out, uint64_t cap, lig_untouched_info *info);
+int lig_rows_untouched_slots(lig_trace *trace, const lig_linear_system *sys, int nonzero_only, lig_slot_value *out, uint64_t cap,
+                             lig_untouched_info *info);
+
 /* ==== proof file framing (src/webgpu_prover.cpp:437-457 writes gzip(level 6) of the serialized envelope with
  * Boost.iostreams; src/webgpu_verifier.cpp:249-253 reads it back).  Host-only helpers on zlib: the output is a standard
  * gzip member that any gzip reader (the reference's gzip_decompressor included) accepts; compressed BYTES depend on the

@@ -403,6 +403,46 @@ public:
         }
         check(lig_rows_read_slots(trace_, slots, n_slots, values), "lig_rows_read_slots");
     }
+    // ---- explain() starts from a constraint; these start from a SLOT: the constraints through each asked slot with their sizes,
+    // coefficient values and residuals, and the witness slots of the LINEAR / QX / QY / QZ rows that no constraint touches
+    // (lig_rows_explain_slots*, lig_rows_untouched_slots*, lig_hip.h).  slots: n_asked numbers row * l + column, strictly ascending;
+    // slot_out: n_asked records; terms_out: the first term_cap term records in ascending (slot, constraint, coef_index) order (NULL with
+    // term_cap = 0: slot_out and the counts only).  untouched_slots*: the first `cap` such slots in ascending order (NULL with cap = 0:
+    // the counts only), nonzero_only: those with a nonzero committed value.
+    // explain_slots() / untouched_slots(): the system given to set_linear_system, with the table of set_linear_values if one was set -- as
+    // explain() does; a batcher with a prepared program or without a system has no term list: std::logic_error (the _attached forms).
+    // explain_slots_attached() / untouched_slots_attached(): the statement attached to the trace, as explain_attached().
+    // All after commit(), before or after prove(), until the next commit(); the same bytes for the same statement.  std::logic_error
+    // before commit(), and on a batcher with shard_over(): a rank's share holds only the terms of its rows.
+    void explain_slots(const uint32_t* slots, uint64_t n_asked, lig_slot_record* slot_out, lig_slot_term* terms_out, uint64_t term_cap, lig_slot_info* info) {
+        slots_ready("explain_slots", false);
+        if (!info) throw std::invalid_argument("hip_row_batcher::explain_slots: null info");
+        lig_linear_system sys = *linear_.get();
+        if (values_set_) { sys.coefs = values_.data(); sys.n_coefs = values_.size() / 32; }
+        info->struct_bytes = sizeof(lig_slot_info);
+        check(lig_rows_explain_slots(trace_, &sys, slots, n_asked, slot_out, terms_out, term_cap, info), "lig_rows_explain_slots");
+    }
+    void explain_slots_attached(const uint32_t* slots, uint64_t n_asked, lig_slot_record* slot_out, lig_slot_term* terms_out, uint64_t term_cap,
+                                lig_slot_info* info) {
+        slots_ready("explain_slots_attached", true);
+        if (!info) throw std::invalid_argument("hip_row_batcher::explain_slots_attached: null info");
+        info->struct_bytes = sizeof(lig_slot_info);
+        check(lig_rows_explain_slots_attached(trace_, slots, n_asked, slot_out, terms_out, term_cap, info), "lig_rows_explain_slots_attached");
+    }
+    void untouched_slots(bool nonzero_only, lig_slot_value* out, uint64_t cap, lig_untouched_info* info) {
+        slots_ready("untouched_slots", false);
+        if (!info) throw std::invalid_argument("hip_row_batcher::untouched_slots: null info");
+        lig_linear_system sys = *linear_.get();
+        if (values_set_) { sys.coefs = values_.data(); sys.n_coefs = values_.size() / 32; }
+        info->struct_bytes = sizeof(lig_untouched_info);
+        check(lig_rows_untouched_slots(trace_, &sys, nonzero_only ? 1 : 0, out, cap, info), "lig_rows_untouched_slots");
+    }
+    void untouched_slots_attached(bool nonzero_only, lig_slot_value* out, uint64_t cap, lig_untouched_info* info) {
+        slots_ready("untouched_slots_attached", true);
+        if (!info) throw std::invalid_argument("hip_row_batcher::untouched_slots_attached: null info");
+        info->struct_bytes = sizeof(lig_untouched_info);
+        check(lig_rows_untouched_slots_attached(trace_, nonzero_only ? 1 : 0, out, cap, info), "lig_rows_untouched_slots_attached");
+    }
     // the next proof with this batcher: staging and (for the same row kinds) every device buffer of the trace are kept
     void reset(const hip_proof_meta* meta = nullptr) {
         if (pass_ == 2) throw std::logic_error("hip_row_batcher::reset between commit and prove");
@@ -436,6 +476,14 @@ private:
     // randomness row are in the staging (packed) and go over the link; the library zero-fills the others on the device
     // (lig_rows_push_rands_sparse) -- batch rows never have one, quadratic rows often do not.
     bool has_linear() const { return linear_.is_set() || program_ != nullptr; }
+    // explain_slots* / untouched_slots*: not sharded, after commit(), with the statement the entry reads
+    void slots_ready(const char* what, bool attached) const {
+        const std::string w = std::string("hip_row_batcher::") + what;
+        if (sharded_) throw std::logic_error(w + ": not on a sharded batcher");
+        if (pass_ == 1 || !trace_) throw std::logic_error(w + " before commit");
+        if (attached && (!has_linear() || !linear_on_trace_)) throw std::logic_error(w + " without a linear system or program");
+        if (!attached && !linear_.is_set()) throw std::logic_error(w + " without a linear system (the _attached form)");
+    }
     void apply_linear() {
         if (!has_linear() || !(sharded_ ? (bool)shard_ : (bool)trace_)) return;
         if (!linear_on_trace_) {

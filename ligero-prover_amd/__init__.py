@@ -44,6 +44,7 @@ EXPORTS = [
     "lig_rows_set_linear_values", "lig_rows_verify_set_linear_values", "lig_linear_program_form",
     "lig_rows_diagnose", "lig_rows_diagnose_attached",
     "lig_rows_explain", "lig_rows_explain_attached", "lig_rows_read_slots",
+    "lig_rows_explain_slots", "lig_rows_explain_slots_attached", "lig_rows_untouched_slots", "lig_rows_untouched_slots_attached",
     "lig_shard_rows_explain", "lig_shard_rows_read_slots", "lig_shard_rows_explain_attached",
     "lig_shard_rows_set_linear_values", "lig_shard_rows_diagnose_attached",
 ]
@@ -231,6 +232,28 @@ EXPLAIN_CONSTRAINT = np.dtype([("constraint", "<u4"), ("reserved", "<u4"), ("n_t
                                ("residual", "u1", (32,))])
 
 
+class SlotInfo(C.Structure):
+    """lig_slot_info: n_terms_total covers every term on the asked slots, n_terms_reported what fitted term_cap, n_constraints_distinct the
+    distinct constraints over all asked slots"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("reserved", C.c_uint32), ("n_terms_total", C.c_uint64), ("n_terms_reported", C.c_uint64),
+                ("n_constraints_distinct", C.c_uint64), ("ms_total", C.c_double)]
+
+
+class UntouchedInfo(C.Structure):
+    """lig_untouched_info: n_untouched / n_untouched_nonzero count every LINEAR .. QZ slot no term touches (with a nonzero committed value),
+    n_reported what fitted cap"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("reserved", C.c_uint32), ("n_untouched", C.c_uint64), ("n_untouched_nonzero", C.c_uint64),
+                ("n_reported", C.c_uint64), ("ms_total", C.c_double)]
+
+
+# lig_slot_record (56 bytes) / lig_slot_term (80 bytes) / lig_slot_value (40 bytes) as numpy records; value, coef, residual = 32 little-endian
+# bytes, canonical
+SLOT_RECORD = np.dtype([("slot", "<u4"), ("row_kind", "<u4"), ("n_terms", "<u8"), ("first_term", "<u8"), ("value", "u1", (32,))])
+SLOT_TERM = np.dtype([("slot", "<u4"), ("constraint", "<u4"), ("coef_index", "<u4"), ("constraint_terms", "<u4"), ("coef", "u1", (32,)),
+                      ("residual", "u1", (32,))])
+SLOT_VALUE = np.dtype([("slot", "<u4"), ("row_kind", "<u4"), ("value", "u1", (32,))])
+
+
 class ProofInfo(C.Structure):
     _fields_ = [("root", C.c_uint8 * 32), ("stage1_seed", C.c_uint8 * 32), ("stage2_seed", C.c_uint8 * 32),
                 ("const_sum", C.c_uint8 * 32), ("rows", C.c_uint64), ("valid_code", C.c_int32),
@@ -386,6 +409,10 @@ def load_library():
     L.lig_rows_explain.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
     L.lig_rows_explain_attached.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
     L.lig_rows_read_slots.argtypes = [vp, vp, u64, vp]
+    L.lig_rows_explain_slots.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, u64, C.POINTER(SlotInfo)]
+    L.lig_rows_explain_slots_attached.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(SlotInfo)]
+    L.lig_rows_untouched_slots.argtypes = [vp, C.POINTER(LinearSystem), C.c_int, vp, u64, C.POINTER(UntouchedInfo)]
+    L.lig_rows_untouched_slots_attached.argtypes = [vp, C.c_int, vp, u64, C.POINTER(UntouchedInfo)]
     L.lig_shard_rows_explain.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
     L.lig_shard_rows_read_slots.argtypes = [vp, vp, u64, vp]
     L.lig_shard_rows_explain_attached.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
@@ -1156,6 +1183,44 @@ class Context:
         out = np.zeros((len(sl), 8), dtype=np.uint32)
         self.check(self.L.lig_rows_read_slots(trace, _hptr(sl) if len(sl) else None, len(sl), _hptr(out) if len(sl) else None))
         return out
+
+    def _rows_explain_slots(self, call, head, slots, term_cap):
+        info = SlotInfo()
+        info.struct_bytes = C.sizeof(SlotInfo)
+        asked = np.ascontiguousarray(slots, dtype=np.uint32)
+        rec, terms = np.zeros(len(asked), dtype=SLOT_RECORD), np.zeros(term_cap, dtype=SLOT_TERM)
+        self.check(call(*head, _hptr(asked) if len(asked) else None, len(asked), _hptr(rec) if len(asked) else None,
+                        _hptr(terms) if term_cap else None, term_cap, C.byref(info)))
+        return info, rec, terms[:info.n_terms_reported]
+
+    def rows_explain_slots(self, trace, system, slots, term_cap=4096):
+        """lig_rows_explain_slots: the constraints of `system` through the slots `slots` (row * l + column, strictly ascending) ->
+        (SlotInfo, slot records, term records): numpy record arrays (SLOT_RECORD: row_kind, n_terms, first_term, committed value;
+        SLOT_TERM: constraint, coef_index, the constraint's term count, coefficient value, the constraint's residual), the first term_cap
+        terms in ascending (slot, constraint, coef_index) order; the counts cover all terms"""
+        return self._rows_explain_slots(self.L.lig_rows_explain_slots, (trace, C.byref(system) if system is not None else None), slots, term_cap)
+
+    def rows_explain_slots_attached(self, trace, slots, term_cap=4096):
+        """lig_rows_explain_slots_attached: rows_explain_slots against the statement attached to the trace (rows_set_linear /
+        rows_attach_linear, with the values of rows_set_linear_values in force): no term list is passed -> the same triple"""
+        return self._rows_explain_slots(self.L.lig_rows_explain_slots_attached, (trace,), slots, term_cap)
+
+    def _rows_untouched_slots(self, call, head, nonzero_only, cap):
+        info = UntouchedInfo()
+        info.struct_bytes = C.sizeof(UntouchedInfo)
+        out = np.zeros(cap, dtype=SLOT_VALUE)
+        self.check(call(*head, 1 if nonzero_only else 0, _hptr(out) if cap else None, cap, C.byref(info)))
+        return info, out[:info.n_reported]
+
+    def rows_untouched_slots(self, trace, system, nonzero_only=False, cap=1024):
+        """lig_rows_untouched_slots: the slots of the LINEAR / QX / QY / QZ rows that no term of `system` touches -> (UntouchedInfo, numpy
+        SLOT_VALUE records of the first `cap` of them in ascending order, each with its row kind and committed value); nonzero_only: only
+        those whose committed value is not zero.  The two counts in UntouchedInfo always cover all of them"""
+        return self._rows_untouched_slots(self.L.lig_rows_untouched_slots, (trace, C.byref(system) if system is not None else None), nonzero_only, cap)
+
+    def rows_untouched_slots_attached(self, trace, nonzero_only=False, cap=1024):
+        """lig_rows_untouched_slots_attached: rows_untouched_slots against the statement attached to the trace -> the same pair"""
+        return self._rows_untouched_slots(self.L.lig_rows_untouched_slots_attached, (trace,), nonzero_only, cap)
 
     def shard_rows_diagnose(self, shard, system=None, lin_cap=1024, quad_cap=1024):
         """lig_shard_rows_diagnose: rows_diagnose on a rows shard.  Collective: every rank passes the same `system` (of the WHOLE trace) and

@@ -14,7 +14,8 @@
 // (exact arithmetic mod p: no result depends on an order).  lig_shard_rows_diagnose_attached takes the partials from the rank's share
 // ATTACHED to the shard instead (k_diag_att_bounds, k_diag_att_part*: their header below) and lets the one holder of a right-hand side
 // subtract it there; the owner then only adds (k_diag_reduce<false>).
-// lig_rows_explain* / lig_rows_read_slots and their sharded counterparts (k_explain_*, k_read_slots) have a header of their own below.
+// lig_rows_explain* / lig_rows_read_slots and their sharded counterparts (k_explain_*, k_read_slots) have a header of their own below, and so
+// have lig_rows_explain_slots* / lig_rows_untouched_slots* (k_slot_*, k_untouched_*), which read the slot-major program as it stands.
 // Where the constraint-major list comes from is the only difference between the two one-GPU entries:
 //   lig_rows_diagnose            the caller's lig_linear_system, uploaded, with a scratch copy of its table in Montgomery form
 //   lig_rows_diagnose_attached   the statement ATTACHED to the trace.  Its program keeps the terms slot-major (linear.hip: begin[], ent[] =
@@ -516,6 +517,98 @@ __global__ void __launch_bounds__(LIN_WG) k_read_slots(const uint32_t* __restric
     for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG)
         fr_store(out + i, diag_witness(slots[i], msgs, l, k, l_recip));
 }
+
+// ---- lig_rows_explain_slots*: the constraints through the asked slots.  The program is slot-major, so the terms of asked slot a are the
+// segment ent[begin[slots[a]] .. begin[slots[a] + 1]) as it stands: nothing is marked, nothing regrouped.  An item is an ExplainItem whose
+// `slot` field carries the CONSTRAINT: {index in the asked list, constraint, coefficient index}, so that explain_order is the output order.
+//   k_slot_len            one lane per asked slot: len[a] = the length of its segment
+//   (rocPRIM exclusive scan -> pre[0 .. n_asked], the total m; downloaded: the host needs n_terms / first_term and the heavy list)
+//   k_slot_collect        one lane per item i < m: its asked slot by binary search over pre[] (diag_slot_of), the entry copied to items[i];
+//                         the items of a slot with more than HEAVY_MIN terms are left to
+//   k_slot_collect_heavy  one workgroup per such slot, the lanes striding its segment (one slot may carry 2^24 terms)
+//   k_slot_fill           one lane per reported record, over the items the host has ordered: the coefficient value in force
+//                         (diag_coef_value), size and residual of its constraint out of the record k_explain_finish wrote for it (con[cidx[i]]:
+//                         the distinct constraints went through explain_rows), 16-byte stores
+// No atomic.  Where an item lands inside items[pre[a] .. pre[a + 1]) follows the order inside the slot's segment, which the atomics of the
+// prepare decided: the host's sort on the whole 12 bytes removes it.  Every slots[a] < n_slots = rows * l and begin[] tiles [0, n_terms)
+// (the host has checked the asked list, and m <= n_terms before the collect is launched): every read of ent[] lies inside it.
+__global__ void __launch_bounds__(LIN_WG) k_slot_len(const uint32_t* __restrict__ slots, uint32_t n_asked, const uint32_t* __restrict__ begin, uint32_t* __restrict__ len) {
+    for (uint64_t a = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; a < n_asked; a += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t s = slots[a];
+        len[a] = begin[s + 1] - begin[s];
+    }
+}
+__global__ void __launch_bounds__(LIN_WG) k_slot_collect(const uint32_t* __restrict__ slots, uint32_t n_asked, const uint32_t* __restrict__ pre, uint32_t m,
+                                                         const uint32_t* __restrict__ begin, const uint2* __restrict__ ent, ExplainItem* __restrict__ items) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < m; i += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t a = diag_slot_of(pre, n_asked, (uint32_t)i), b = pre[a];
+        if (pre[a + 1] - b > HEAVY_MIN) continue;                             // k_slot_collect_heavy
+        const uint2 en = ent[begin[slots[a]] + ((uint32_t)i - b)];
+        ExplainItem it;
+        it.ask = a; it.slot = en.x; it.coef = en.y;
+        items[i] = it;
+    }
+}
+// workgroup -> heavy asked slot heavy[blockIdx.x + i * gridDim.x] (indices into the asked list, ascending)
+__global__ void __launch_bounds__(LIN_WG) k_slot_collect_heavy(const uint32_t* __restrict__ heavy, uint32_t n_heavy, const uint32_t* __restrict__ slots,
+                                                               const uint32_t* __restrict__ pre, const uint32_t* __restrict__ begin, const uint2* __restrict__ ent,
+                                                               ExplainItem* __restrict__ items) {
+    for (uint32_t h = blockIdx.x; h < n_heavy; h += gridDim.x) {
+        const uint32_t a = heavy[h], b = pre[a], n = pre[a + 1] - b, src = begin[slots[a]];
+        for (uint32_t j = threadIdx.x; j < n; j += LIN_WG) {
+            const uint2 en = ent[src + j];
+            ExplainItem it;
+            it.ask = a; it.slot = en.x; it.coef = en.y;
+            items[b + j] = it;
+        }
+    }
+}
+// record i = the i-th item of the output order; out is 16-byte aligned and a record has 80 bytes; a constraint record has 88, its residual
+// begins at byte 56: 8-byte loads
+__global__ void __launch_bounds__(LIN_WG) k_slot_fill(const ExplainItem* __restrict__ items, const uint32_t* __restrict__ cidx, uint32_t n,
+                                                      const uint32_t* __restrict__ slots, const lig_explain_constraint* __restrict__ con,
+                                                      const fr* __restrict__ coef_mont, lig_slot_term* __restrict__ out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG) {
+        const ExplainItem it = items[i];
+        const uint2* cr = reinterpret_cast<const uint2*>(con + cidx[i]);      // {constraint, 0}, n_terms, first_term, rhs x 4, residual x 4
+        uint4* o = reinterpret_cast<uint4*>(out + i);
+        o[0] = make_uint4(slots[it.ask], it.slot, it.coef, cr[1].x);
+        fr_store(reinterpret_cast<fr*>(o + 1), diag_coef_value(it.coef, coef_mont));
+        const uint2 r0 = cr[7], r1 = cr[8], r2 = cr[9], r3 = cr[10];
+        o[3] = make_uint4(r0.x, r0.y, r1.x, r1.y);
+        o[4] = make_uint4(r2.x, r2.y, r3.x, r3.y);
+    }
+}
+// ---- lig_rows_untouched_slots*: the slots of the LINEAR / QX / QY / QZ rows with an empty segment.  lrows = those rows ascending, {row, kind};
+// item i of a slice = column i % l of row lrows[first + i / l].
+//   k_untouched_flag     flag[i] = 1 when the segment of the slot is empty, + 2^32 when its committed element is not zero besides (fr_load:
+//                        two 16-byte loads) -- one 64-bit exclusive scan (rocPRIM) carries both counts, no atomic
+//   k_untouched_compact  the selected slots with a position below `cap` -> {slot, kind, value} in ascending order; a record has 40 bytes:
+//                        8-byte stores
+__global__ void __launch_bounds__(LIN_WG) k_untouched_flag(const uint2* __restrict__ lrows, uint32_t first, uint32_t n_items, const uint32_t* __restrict__ begin,
+                                                           const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip, uint64_t* __restrict__ flag) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n_items; i += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t t = diag_div((uint32_t)i, l_recip), col = (uint32_t)i - t * l, row = lrows[first + t].x, s = row * l + col;
+        uint64_t f = 0;
+        if (begin[s + 1] == begin[s]) f = fr_is_zero(fr_load(msgs + (size_t)row * k + col)) ? 1ull : 1ull | (1ull << 32);
+        flag[i] = f;
+    }
+}
+__global__ void __launch_bounds__(LIN_WG) k_untouched_compact(const uint64_t* __restrict__ flag, const uint64_t* __restrict__ pos, const uint2* __restrict__ lrows,
+                                                              uint32_t first, uint32_t n_items, const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip,
+                                                              uint32_t nonzero_only, uint32_t cap, lig_slot_value* __restrict__ out) {
+    const uint32_t shift = nonzero_only ? 32u : 0u;
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n_items; i += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t at = (uint32_t)(pos[i] >> shift);
+        if (!(uint32_t)(flag[i] >> shift) || at >= cap) continue;
+        const uint32_t t = diag_div((uint32_t)i, l_recip), col = (uint32_t)i - t * l;
+        const uint2 lr = lrows[first + t];
+        const fr w = fr_load(msgs + (size_t)lr.x * k + col);
+        uint2* o = reinterpret_cast<uint2*>(out + at);
+        o[0] = make_uint2(lr.x * l + col, lr.y);
+        for (int j = 0; j < 4; j++) o[1 + j] = make_uint2(w.v[2 * j], w.v[2 * j + 1]);
+    }
+}
 }  // namespace lig
 
 namespace {
@@ -888,6 +981,170 @@ int lig_internal_rows_read_slots(lig_ctx* c, const fr* msgs, uint64_t rows, cons
         HIP_TRY(c, hipMemcpyAsync(values + at * 32, d_val, (size_t)n * 32, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, lig_internal_wait_stream(s));
     }
+    return LIG_OK;
+}
+
+// lig_rows_explain_slots / lig_rows_explain_slots_attached (lig_hip.h; the kernels' header above).  v: the view of the trace's attachment, or
+// of the temporary program the caller made from its term list -- not sharded, over the rows x l slots of this trace (checked here).  kinds:
+// one per committed row.  Blocks for the prefix sums, for the items (ordered on the host), inside explain_rows for the distinct
+// constraints, and for the records.
+int lig_internal_rows_explain_slots(lig_ctx* c, const fr* msgs, const uint8_t* kinds, uint64_t rows, const lig_linear_view& v, const uint32_t* slots, uint64_t n_asked,
+                                    lig_slot_record* slot_out, lig_slot_term* terms_out, uint64_t term_cap, lig_slot_info* info) {
+    if (v.sharded) FAIL(c, LIG_E_STATE, "lig_rows_explain_slots: the attached structure is one rank's share of a sharded trace");
+    if ((uint64_t)v.n_slots != rows * (uint64_t)c->l) FAIL(c, LIG_E_STATE, "lig_rows_explain_slots: the program does not cover the slots of this trace");
+    if (!lig::explain_slots_ok(slots, n_asked, rows, c->l)) FAIL(c, LIG_E_ARG, "lig_rows_explain_slots: a slot is not below rows * l");
+    for (uint64_t i = 1; i < n_asked; i++) if (slots[i] <= slots[i - 1]) FAIL(c, LIG_E_ARG, "lig_rows_explain_slots: the asked slots must be strictly ascending");
+    if (!n_asked) return LIG_OK;
+    hipStream_t s = c->stream;
+    const uint32_t l = c->l, k = c->k, NA = (uint32_t)n_asked, NT = (uint32_t)v.n_terms;
+    const uint64_t l_recip = diag_reciprocal(l);
+    // (sources and targets of queued copies: declared before the scratch, whose destructor drains the stream)
+    std::vector<uint32_t> pre((size_t)NA + 1), heavy, distinct, cidx;
+    std::vector<lig::ExplainItem> items;
+    std::vector<uint64_t> first;
+    std::vector<lig_explain_constraint> con;
+    std::vector<fr> vals(NA);
+    DiagScratch sc(c);
+    void* scan_tmp = nullptr; size_t scan_cap = 0;
+    const DiagWait wait = [c, s]() -> int { HIP_TRY(c, lig_internal_wait_stream(s)); return LIG_OK; };
+
+    uint32_t *d_slots = nullptr, *d_len = nullptr, *d_pre = nullptr; fr* d_val = nullptr;
+    TRY(sc.alloc((void**)&d_slots, (size_t)NA * 4));
+    TRY(sc.alloc((void**)&d_len, ((size_t)NA + 1) * 4));
+    TRY(sc.alloc((void**)&d_pre, ((size_t)NA + 1) * 4));
+    TRY(sc.alloc((void**)&d_val, (size_t)NA * 32));
+    HIP_TRY(c, hipMemcpyAsync(d_slots, slots, (size_t)NA * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(d_len + NA, 0, 4, s));
+    hipLaunchKernelGGL(lig::k_slot_len, dim3(diag_grid(NA)), dim3(lig::LIN_WG), 0, s, d_slots, NA, v.begin, d_len);
+    hipLaunchKernelGGL(lig::k_read_slots, dim3(diag_grid(NA)), dim3(lig::LIN_WG), 0, s, d_slots, NA, msgs, l, k, l_recip, d_val);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(vals.data(), d_val, (size_t)NA * 32, hipMemcpyDeviceToHost, s));
+    uint32_t m = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_cap, d_len, d_pre, 0u, (size_t)NA + 1, rocprim::plus<uint32_t>(), s));
+    TRY(sc.alloc(&scan_tmp, scan_cap));
+    HIP_TRY(c, rocprim::exclusive_scan(scan_tmp, scan_cap, d_len, d_pre, 0u, (size_t)NA + 1, rocprim::plus<uint32_t>(), s));
+    HIP_TRY(c, hipMemcpyAsync(pre.data(), d_pre, ((size_t)NA + 1) * 4, hipMemcpyDeviceToHost, s));
+    TRY(wait());
+    m = pre[NA];
+    // distinct slots own disjoint segments: the lengths add up to at most n_terms, every prefix sum is exact in 32 bits
+    if (m > NT || !std::is_sorted(pre.begin(), pre.end())) FAIL(c, LIG_E_STATE, "lig_rows_explain_slots: the program's index does not add up to its term count");
+    for (uint32_t a = 0; a < NA; a++) if (pre[a + 1] - pre[a] > lig::HEAVY_MIN) heavy.push_back(a);
+
+    lig::ExplainItem* d_items = nullptr;
+    TRY(sc.alloc((void**)&d_items, (size_t)m * sizeof(lig::ExplainItem)));
+    if (m) hipLaunchKernelGGL(lig::k_slot_collect, dim3(diag_grid(m)), dim3(lig::LIN_WG), 0, s, d_slots, NA, d_pre, m, v.begin, v.ent, d_items);
+    if (!heavy.empty()) {
+        uint32_t* d_heavy = nullptr;
+        TRY(sc.alloc((void**)&d_heavy, heavy.size() * 4));
+        HIP_TRY(c, hipMemcpyAsync(d_heavy, heavy.data(), heavy.size() * 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(lig::k_slot_collect_heavy, dim3(std::min<uint32_t>((uint32_t)heavy.size(), lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d_heavy,
+                           (uint32_t)heavy.size(), d_slots, d_pre, v.begin, v.ent, d_items);
+    }
+    HIP_TRY(c, hipGetLastError());
+    items.resize(m);
+    if (m) HIP_TRY(c, hipMemcpyAsync(items.data(), d_items, (size_t)m * sizeof(lig::ExplainItem), hipMemcpyDeviceToHost, s));
+    TRY(wait());
+    // the m items -> the output order (asked slot, constraint, coefficient index), on the host; the distinct constraints, ascending
+    if (!lig::explain_order(items, NA, first)) FAIL(c, LIG_E_STATE, "lig_rows_explain_slots: a collected term names no asked slot");
+    distinct.resize(m);
+    for (uint32_t i = 0; i < m; i++) {
+        if (items[i].slot >= v.n_constraints) FAIL(c, LIG_E_STATE, "lig_rows_explain_slots: an entry of the program names no constraint");
+        distinct[i] = items[i].slot;
+    }
+    std::sort(distinct.begin(), distinct.end());
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    const uint32_t ND = (uint32_t)distinct.size(), rep = (uint32_t)std::min<uint64_t>(m, term_cap);
+    // their sizes and residuals: the attached selection pass itself, asked for the constraint records alone
+    con.resize(ND);
+    if (ND) {
+        lig_explain_info einfo;
+        std::memset(&einfo, 0, sizeof einfo);
+        TRY(explain_rows(c, msgs, nullptr, &v, distinct.data(), ND, con.data(), nullptr, 0, &einfo));
+    }
+    if (rep) {
+        cidx.resize(rep);
+        for (uint32_t i = 0; i < rep; i++) cidx[i] = (uint32_t)(std::lower_bound(distinct.begin(), distinct.end(), items[i].slot) - distinct.begin());
+        uint32_t* d_cidx = nullptr; lig_explain_constraint* d_con = nullptr; lig_slot_term* d_out = nullptr;
+        TRY(sc.alloc((void**)&d_cidx, (size_t)rep * 4));
+        TRY(sc.alloc((void**)&d_con, (size_t)ND * sizeof(lig_explain_constraint)));
+        TRY(sc.alloc((void**)&d_out, (size_t)rep * sizeof(lig_slot_term)));
+        HIP_TRY(c, hipMemcpyAsync(d_items, items.data(), (size_t)rep * sizeof(lig::ExplainItem), hipMemcpyHostToDevice, s));      // the ordered ones over the collected
+        HIP_TRY(c, hipMemcpyAsync(d_cidx, cidx.data(), (size_t)rep * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_con, con.data(), (size_t)ND * sizeof(lig_explain_constraint), hipMemcpyHostToDevice, s));
+        // values set on the side stream (lig_rows_set_linear_values): the table is read once its conversion has finished
+        if (v.coef_ready) HIP_TRY(c, hipStreamWaitEvent(s, v.coef_ready, 0));
+        hipLaunchKernelGGL(lig::k_slot_fill, dim3(diag_grid(rep)), dim3(lig::LIN_WG), 0, s, d_items, d_cidx, rep, d_slots, d_con, v.coef, d_out);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(terms_out, d_out, (size_t)rep * sizeof(lig_slot_term), hipMemcpyDeviceToHost, s));
+        TRY(wait());
+    }
+    for (uint32_t a = 0; a < NA; a++) {
+        lig_slot_record& r = slot_out[a];
+        std::memset(&r, 0, sizeof r);
+        r.slot = slots[a]; r.row_kind = kinds[slots[a] / l] & 0x7fu;
+        r.n_terms = pre[a + 1] - pre[a]; r.first_term = first[a];
+        std::memcpy(r.value, vals[a].v, 32);
+    }
+    info->n_terms_total = m;
+    info->n_terms_reported = rep;
+    info->n_constraints_distinct = ND;
+    return LIG_OK;
+}
+
+// lig_rows_untouched_slots / lig_rows_untouched_slots_attached (lig_hip.h; the kernels' header above): v and kinds as for
+// lig_internal_rows_explain_slots.  The slots of the LINEAR .. QZ rows in slices of UNTOUCHED_ITEMS; blocks once per slice for the two
+// counts, and once more for the records of a slice that reports some.
+int lig_internal_rows_untouched_slots(lig_ctx* c, const fr* msgs, const uint8_t* kinds, uint64_t rows, const lig_linear_view& v, int nonzero_only, lig_slot_value* out,
+                                      uint64_t cap, lig_untouched_info* info) {
+    static constexpr uint64_t UNTOUCHED_ITEMS = 1ull << 22;      // scratch budget: slots per slice (16 bytes each)
+    if (v.sharded) FAIL(c, LIG_E_STATE, "lig_rows_untouched_slots: the attached structure is one rank's share of a sharded trace");
+    if ((uint64_t)v.n_slots != rows * (uint64_t)c->l) FAIL(c, LIG_E_STATE, "lig_rows_untouched_slots: the program does not cover the slots of this trace");
+    hipStream_t s = c->stream;
+    const uint32_t l = c->l, k = c->k;
+    const uint64_t l_recip = diag_reciprocal(l);
+    std::vector<uint2> lrows;      // (source of a queued copy: declared before the scratch)
+    for (uint64_t r = 0; r < rows; r++) if ((kinds[r] & 0x7fu) <= LIG_ROW_QZ) lrows.push_back(make_uint2((uint32_t)r, kinds[r] & 0x7fu));
+    const uint64_t NL = lrows.size();
+    if (!NL) return LIG_OK;
+    DiagScratch sc(c);
+    const uint64_t per = std::max<uint64_t>(UNTOUCHED_ITEMS / l, 1);      // rows per slice: per * l < 2^32 (rows * l < 2^32: lig_linear_check)
+    const uint64_t slice_items = std::min(per, NL) * l, out_cap = std::min<uint64_t>(cap, slice_items);
+    uint2* d_lrows = nullptr; uint64_t *d_flag = nullptr, *d_pos = nullptr; lig_slot_value* d_out = nullptr; void* scan_tmp = nullptr;
+    TRY(sc.alloc((void**)&d_lrows, (size_t)NL * sizeof(uint2)));
+    TRY(sc.alloc((void**)&d_flag, ((size_t)slice_items + 1) * 8));
+    TRY(sc.alloc((void**)&d_pos, ((size_t)slice_items + 1) * 8));
+    if (out_cap) TRY(sc.alloc((void**)&d_out, (size_t)out_cap * sizeof(lig_slot_value)));
+    size_t scan_cap = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_cap, d_flag, d_pos, (uint64_t)0, (size_t)slice_items + 1, rocprim::plus<uint64_t>(), s));
+    TRY(sc.alloc(&scan_tmp, scan_cap));
+    HIP_TRY(c, hipMemcpyAsync(d_lrows, lrows.data(), (size_t)NL * sizeof(uint2), hipMemcpyHostToDevice, s));
+    uint64_t n_untouched = 0, n_nonzero = 0, reported = 0;
+    for (uint64_t r0 = 0; r0 < NL; r0 += per) {
+        const uint32_t items = (uint32_t)(std::min(per, NL - r0) * l);
+        HIP_TRY(c, hipMemsetAsync(d_flag + items, 0, 8, s));
+        hipLaunchKernelGGL(lig::k_untouched_flag, dim3(diag_grid(items)), dim3(lig::LIN_WG), 0, s, d_lrows, (uint32_t)r0, items, v.begin, msgs, l, k, l_recip, d_flag);
+        HIP_TRY(c, hipGetLastError());
+        size_t tmp = scan_cap;
+        HIP_TRY(c, rocprim::exclusive_scan(scan_tmp, tmp, d_flag, d_pos, (uint64_t)0, (size_t)items + 1, rocprim::plus<uint64_t>(), s));
+        uint64_t both = 0;
+        HIP_TRY(c, hipMemcpyAsync(&both, d_pos + items, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, lig_internal_wait_stream(s));
+        const uint32_t un = (uint32_t)both, nz = (uint32_t)(both >> 32);
+        if (un > items || nz > un) FAIL(c, LIG_E_STATE, "lig_rows_untouched_slots: counted more slots than the slice holds");
+        n_untouched += un; n_nonzero += nz;
+        const uint32_t rep = (uint32_t)std::min<uint64_t>(nonzero_only ? nz : un, cap - reported);
+        if (rep) {
+            hipLaunchKernelGGL(lig::k_untouched_compact, dim3(diag_grid(items)), dim3(lig::LIN_WG), 0, s, d_flag, d_pos, d_lrows, (uint32_t)r0, items, msgs, l, k, l_recip,
+                               nonzero_only ? 1u : 0u, rep, d_out);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipMemcpyAsync(out + reported, d_out, (size_t)rep * sizeof(lig_slot_value), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, lig_internal_wait_stream(s));
+            reported += rep;
+        }
+    }
+    info->n_untouched = n_untouched;
+    info->n_untouched_nonzero = n_nonzero;
+    info->n_reported = reported;
     return LIG_OK;
 }
 

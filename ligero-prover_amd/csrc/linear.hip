@@ -514,14 +514,19 @@ int lig_internal_linear_set_values(lig_ctx* c, lig_linear* L, const uint8_t* coe
 }
 // what lig_rows_diagnose_attached / lig_shard_rows_diagnose_attached (diagnose.hip) read of an attachment; nothing of it is written through the view
 lig_linear_view lig_internal_linear_view(const lig_linear* L) {
-    const lig_linear_program* P = L->P;
+    lig_linear_view v = lig_internal_linear_program_view(L->P);
+    v.coef = L->coef;
+    v.coef_ready = L->coef == L->vals && L->vals ? L->ev_mont : nullptr;
+    return v;
+}
+// a program nobody is attached to (the temporary one of lig_rows_explain_slots / lig_rows_untouched_slots): its own table is in force
+lig_linear_view lig_internal_linear_program_view(const lig_linear_program* P) {
     lig_linear_view v;
     v.sharded = P->sharded;
     v.n_constraints = P->n_constraints; v.n_terms = P->n_terms; v.n_rhs = P->n_rhs; v.n_slots = P->n_slots;
     v.begin = P->begin; v.ent = P->ent; v.rhs_c = P->rhs_c; v.rhs_coef = P->rhs_coef;
     v.need = P->need; v.n_need = P->n_need; v.rows_local = P->sharded ? P->rows : 0;
-    v.coef = L->coef;
-    v.coef_ready = L->coef == L->vals && L->vals ? L->ev_mont : nullptr;
+    v.coef = P->coef_mont;
     return v;
 }
 

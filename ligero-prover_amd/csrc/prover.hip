@@ -1129,6 +1129,83 @@ int lig_rows_read_slots(lig_trace* T, const uint32_t* slots, uint64_t n_slots, u
     return lig_internal_rows_read_slots(c, T->msgs, T->R, slots, n_slots, values);
 }
 
+// the constraints through the asked slots, and the witness slots no term touches (diagnose.hip); the window, blocking and streams of
+// lig_rows_diagnose.  Both read the slot-major index of a program: the one attached to the trace (att), or a temporary one prepared from
+// sys -- lig_linear_check first, nothing is launched for a system it rejects -- and released before the call returns.
+struct TempProgram {
+    lig_linear_program* P = nullptr;
+    ~TempProgram() { lig_linear_program_release(P); }
+};
+using SlotsRun = std::function<int(lig_ctx*, const uint8_t*, const lig_linear_view&)>;
+// the checks the four entries share (args_ok: the entry's own host check of its arguments), then `run` on the view of the statement
+static int rows_slots_call(const char* which, bool att, lig_trace* T, const lig_linear_system* sys, const std::function<bool()>& args_ok, bool nothing_to_do,
+                           const SlotsRun& run) {
+    lig_ctx* c = T->c;
+    CHECK_CTX(c);
+    const std::string w(which);
+    if (!T->from_rows) FAIL(c, LIG_E_STATE, w + ": not a rows trace");
+    if (!T->diag_ok) FAIL(c, LIG_E_STATE, w + ": no committed matrix (between lig_rows_commit and the next commit, or a lig_rows_restart after lig_rows_prove)");
+    if (att && !T->linear) FAIL(c, LIG_E_STATE, w + ": nothing is attached (lig_rows_set_linear, lig_rows_attach_linear)");
+    if (!att && !sys) FAIL(c, LIG_E_ARG, w + ": null linear system");
+    const std::vector<uint8_t> kinds = kinds_of(T->rows);
+    // (the prepare below runs lig_linear_check itself)
+    if (!att && nothing_to_do && lig_linear_check(sys, kinds.data(), T->R, c->l) != LIG_OK) FAIL(c, LIG_E_ARG, w + ": linear system rejected by lig_linear_check");
+    if (!args_ok()) FAIL(c, LIG_E_ARG, w + ": the asked slots must be strictly ascending and below rows * l");
+    if (nothing_to_do) return LIG_OK;      // (an empty request launches nothing: no prepare either)
+    if (att) return run(c, kinds.data(), lig_internal_linear_view(T->linear));
+    TempProgram tmp;
+    TRY(lig_internal_linear_prepare(c, sys, kinds.data(), T->R, &tmp.P));
+    return run(c, kinds.data(), lig_internal_linear_program_view(tmp.P));
+}
+static int rows_explain_slots(const char* which, bool att, lig_trace* T, const lig_linear_system* sys, const uint32_t* slots, uint64_t n_asked, lig_slot_record* slot_out,
+                              lig_slot_term* terms_out, uint64_t term_cap, lig_slot_info* info) {
+    if (!T || !info || info->struct_bytes < sizeof(lig_slot_info)) return LIG_E_ARG;
+    if ((n_asked && (!slot_out || !slots)) || (term_cap && !terms_out)) return LIG_E_ARG;
+    const auto t_begin = clk::now();
+    const uint32_t struct_bytes = info->struct_bytes;
+    // (the asked list before the prepare of the term-list entry: a refused list launches nothing)
+    const auto args_ok = [&]() -> bool {
+        for (uint64_t i = 0; i < n_asked; i++) if (slots[i] >= T->R * (uint64_t)T->c->l || (i && slots[i] <= slots[i - 1])) return false;
+        return true;
+    };
+    TRY(rows_slots_call(which, att, T, sys, args_ok, !n_asked, [&](lig_ctx* c, const uint8_t* kinds, const lig_linear_view& v) -> int {
+        std::memset(info, 0, sizeof *info);
+        info->struct_bytes = struct_bytes;
+        return lig_internal_rows_explain_slots(c, T->msgs, kinds, T->R, v, slots, n_asked, slot_out, terms_out, term_cap, info);
+    }));
+    if (!n_asked) { std::memset(info, 0, sizeof *info); info->struct_bytes = struct_bytes; }
+    info->ms_total = ms_since(t_begin);
+    return LIG_OK;
+}
+static int rows_untouched_slots(const char* which, bool att, lig_trace* T, const lig_linear_system* sys, int nonzero_only, lig_slot_value* out, uint64_t cap,
+                                lig_untouched_info* info) {
+    if (!T || !info || info->struct_bytes < sizeof(lig_untouched_info)) return LIG_E_ARG;
+    if (cap && !out) return LIG_E_ARG;
+    const auto t_begin = clk::now();
+    const uint32_t struct_bytes = info->struct_bytes;
+    TRY(rows_slots_call(which, att, T, sys, []() -> bool { return true; }, false, [&](lig_ctx* c, const uint8_t* kinds, const lig_linear_view& v) -> int {
+        std::memset(info, 0, sizeof *info);
+        info->struct_bytes = struct_bytes;
+        return lig_internal_rows_untouched_slots(c, T->msgs, kinds, T->R, v, nonzero_only, out, cap, info);
+    }));
+    info->ms_total = ms_since(t_begin);
+    return LIG_OK;
+}
+int lig_rows_explain_slots_attached(lig_trace* T, const uint32_t* slots, uint64_t n_asked, lig_slot_record* slot_out, lig_slot_term* terms_out, uint64_t term_cap,
+                                    lig_slot_info* info) {
+    return rows_explain_slots("lig_rows_explain_slots_attached", true, T, nullptr, slots, n_asked, slot_out, terms_out, term_cap, info);
+}
+int lig_rows_explain_slots(lig_trace* T, const lig_linear_system* sys, const uint32_t* slots, uint64_t n_asked, lig_slot_record* slot_out, lig_slot_term* terms_out,
+                           uint64_t term_cap, lig_slot_info* info) {
+    return rows_explain_slots("lig_rows_explain_slots", false, T, sys, slots, n_asked, slot_out, terms_out, term_cap, info);
+}
+int lig_rows_untouched_slots_attached(lig_trace* T, int nonzero_only, lig_slot_value* out, uint64_t cap, lig_untouched_info* info) {
+    return rows_untouched_slots("lig_rows_untouched_slots_attached", true, T, nullptr, nonzero_only, out, cap, info);
+}
+int lig_rows_untouched_slots(lig_trace* T, const lig_linear_system* sys, int nonzero_only, lig_slot_value* out, uint64_t cap, lig_untouched_info* info) {
+    return rows_untouched_slots("lig_rows_untouched_slots", false, T, sys, nonzero_only, out, cap, info);
+}
+
 int lig_rows_push_rands(lig_trace* T, uint64_t first_row, uint64_t n_rows, const void* host_rows) {
     return lig_rows_push_rands_sparse(T, first_row, n_rows, nullptr, host_rows);
 }

@@ -488,6 +488,15 @@ int lig_internal_rows_explain(lig_ctx* c, const fr* msgs, const lig_linear_syste
 int lig_internal_rows_explain_attached(lig_ctx* c, const fr* msgs, const lig_linear* att, const uint32_t* asked, uint64_t n_asked, lig_explain_constraint* con_out,
                                        lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info);
 int lig_internal_rows_read_slots(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* slots, uint64_t n_slots, uint8_t* values);
+// lig_rows_explain_slots* / lig_rows_untouched_slots* (diagnose.hip): the constraints through the asked slots, and the LINEAR .. QZ slots no term
+// touches, straight from the slot-major index of `v` -- the view of the trace's attachment, or lig_internal_linear_program_view of a program
+// prepared from the caller's term list (its own table in force).  kinds: one per committed row.  The asked slots are checked here, on the
+// host, before anything is launched (LIG_E_ARG); a sharded view is LIG_E_STATE.  Blocking, main stream only, scratch per call.
+lig_linear_view lig_internal_linear_program_view(const lig_linear_program* P);
+int lig_internal_rows_explain_slots(lig_ctx* c, const fr* msgs, const uint8_t* kinds, uint64_t rows, const lig_linear_view& v, const uint32_t* slots, uint64_t n_asked,
+                                    lig_slot_record* slot_out, lig_slot_term* terms_out, uint64_t term_cap, lig_slot_info* info);
+int lig_internal_rows_untouched_slots(lig_ctx* c, const fr* msgs, const uint8_t* kinds, uint64_t rows, const lig_linear_view& v, int nonzero_only, lig_slot_value* out,
+                                      uint64_t cap, lig_untouched_info* info);
 hipError_t lig_internal_wait_stream(hipStream_t st);
 // lig_shard_rows_diagnose (diagnose.hip): what one rank of a sharded rows job holds, and the shard's collectives and waits (shard.hip).
 // all_to_all / all_gather run on the context's main stream (stream-ordered forms) or after it has drained (host-synchronous callbacks);
