@@ -37,6 +37,8 @@
 // Everything is allocated inside the call and freed before it returns (off the proving path); all work is ENQUEUED on the context's
 // main stream only -- the side stream, the uploader and the copy stream may be carrying the prefetch of the next trace.  Freeing the
 // scratch (hipFree) waits for the whole device, though: with a prefetch in flight the call returns after that transfer (lig_hip.h says so).
+// Host side: every entry works through one DiagFrame (scratch, typed allocation and copies, the two launch shapes, the scan, the wait);
+// an entry of a sharded rows job through a DiagShardFrame, which adds the collectives, the LIG_TRACE phases and the one end of call.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
@@ -636,18 +638,62 @@ struct DiagScratch {
     }
 };
 
-// flag[0 .. n] (flag[n] = 0) -> pos[0 .. n] = exclusive scan; *count = pos[n] = the number of set flags.  Blocks until it is known.
-template <class Flags>      // const uint32_t*, or an iterator over them (the marks of k_explain_mark read as 0 / 1)
-int diag_scan(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, Flags flag, uint32_t* pos, size_t n, void** scan_tmp, size_t* scan_cap, uint32_t* count) {
-    hipStream_t s = c->stream;
-    size_t need = 0;
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, need, flag, pos, 0u, n + 1, rocprim::plus<uint32_t>(), s));
-    if (need > *scan_cap || !*scan_tmp) { TRY(sc.alloc(scan_tmp, need)); *scan_cap = need; }
-    need = *scan_cap;
-    HIP_TRY(c, rocprim::exclusive_scan(*scan_tmp, need, flag, pos, 0u, n + 1, rocprim::plus<uint32_t>(), s));
-    HIP_TRY(c, hipMemcpyAsync(count, pos + n, 4, hipMemcpyDeviceToHost, s));
-    return wait();
-}
+// What every entry of this file sets up: the context's main stream and shape, the scratch, the temp of the scans and the way the call
+// waits -- as a proof does (one GPU), or the bounded poll of a shard (DiagShardFrame).  Sizes are in ELEMENTS.  A host buffer that is the
+// source or the target of a queued copy is declared BEFORE the frame: the scratch drains the stream when the frame goes.
+struct DiagFrame {
+    lig_ctx* const c;
+    const hipStream_t s;
+    const uint32_t l, k;
+    const uint64_t l_recip;
+    const DiagWait wait;
+    DiagScratch sc;
+    void* scan_tmp = nullptr;
+    size_t scan_cap = 0;
+    explicit DiagFrame(lig_ctx* c_) : DiagFrame(c_, [c = c_, s = c_->stream]() -> int { HIP_TRY(c, lig_internal_wait_stream(s)); return LIG_OK; }) {}
+    DiagFrame(lig_ctx* c_, DiagWait w) : c(c_), s(c_->stream), l(c_->l), k(c_->k), l_recip(diag_reciprocal(c_->l)), wait(std::move(w)), sc(c_) {}
+
+    template <class T> int alloc(T*& p, size_t n) { return sc.alloc((void**)&p, n * sizeof(T)); }
+    template <class T> int upload(T*& p, const T* host, size_t n) {
+        TRY(alloc(p, n));
+        if (n) HIP_TRY(c, hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
+        return LIG_OK;
+    }
+    template <class T> int download(void* host, const T* dev, size_t n) {
+        if (n) HIP_TRY(c, hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, s));
+        return LIG_OK;
+    }
+    template <class T> int fetch(void* host, const T* dev, size_t n) { TRY(download(host, dev, n)); return wait(); }      // ... and blocks until it is there
+    template <class T> int zero(T* p, size_t n) { HIP_TRY(c, hipMemsetAsync(p, 0, n * sizeof(T), s)); return LIG_OK; }
+    // grid-stride over `items`: diag_grid(items) workgroups of LIN_WG lanes
+    template <class... P, class... A> int launch(void (*kernel)(P...), uint64_t items, A... a) {
+        hipLaunchKernelGGL(kernel, dim3(diag_grid(items)), dim3(lig::LIN_WG), 0, s, a...);
+        HIP_TRY(c, hipGetLastError());
+        return LIG_OK;
+    }
+    // one workgroup per item (the heavy walks, k_explain_finish), at most DIAG_MAX_BLOCKS of them
+    template <class... P, class... A> int launch_blocks(void (*kernel)(P...), uint32_t n, A... a) {
+        hipLaunchKernelGGL(kernel, dim3(std::min(n, lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, a...);
+        HIP_TRY(c, hipGetLastError());
+        return LIG_OK;
+    }
+    // flag[0 .. n] (flag[n] = 0) -> pos[0 .. n] = exclusive scan, enqueued; the temp grows to what the largest scan of the call asks for.
+    // Flags: const V*, or an iterator over them (the marks of k_explain_mark read as 0 / 1).  V: uint32_t, or two packed counts in 64 bits.
+    template <class Flags, class V> int scan_enqueue(Flags flag, V* pos, size_t n) {
+        size_t need = 0;
+        HIP_TRY(c, rocprim::exclusive_scan(nullptr, need, flag, pos, V(0), n + 1, rocprim::plus<V>(), s));
+        if (need > scan_cap || !scan_tmp) { TRY(sc.alloc(&scan_tmp, need)); scan_cap = need; }
+        need = scan_cap;
+        HIP_TRY(c, rocprim::exclusive_scan(scan_tmp, need, flag, pos, V(0), n + 1, rocprim::plus<V>(), s));
+        return LIG_OK;
+    }
+    // ... and *count = pos[n] = the number of set flags.  Blocks until it is known.
+    template <class Flags, class V> int scan(Flags flag, V* pos, size_t n, V* count) {
+        TRY(scan_enqueue(flag, pos, n));
+        TRY(download(count, pos + n, 1));
+        return wait();
+    }
+};
 
 // a system on the device, as the linear passes consume it: a constraint-major term list, rhs_index, the constraints with more than HEAVY_MIN
 // terms (ascending), the right-hand-side coefficients and a table in Montgomery form.
@@ -663,34 +709,27 @@ struct DiagSystem {
     lig_lin_term* terms = nullptr;
     const fr* coef = nullptr;
 };
-int diag_upload_system(lig_ctx* c, DiagScratch& sc, const lig_linear_system* sys, DiagSystem& d) {
-    hipStream_t s = c->stream;
+// the caller's coefficient table -> scratch, converted to Montgomery form there
+int diag_upload_table(DiagFrame& f, const lig_linear_system* sys, fr*& d_coef) {
+    TRY(f.upload(d_coef, reinterpret_cast<const fr*>(sys->coefs), sys->n_coefs));
+    lig::launch_lin_coefs_mont(f.s, d_coef, sys->n_coefs);
+    HIP_TRY(f.c, hipGetLastError());
+    return LIG_OK;
+}
+int diag_upload_system(DiagFrame& f, const lig_linear_system* sys, DiagSystem& d) {
     const uint32_t NC = d.NC = (uint32_t)sys->n_constraints, NT = (uint32_t)sys->n_terms, NR = (uint32_t)sys->n_rhs;
     for (uint32_t cn = 0; cn < NC; cn++) if (sys->term_begin[cn + 1] - sys->term_begin[cn] > lig::HEAVY_MIN) d.heavy.push_back(cn);
     uint32_t *d_rhs_c = nullptr, *d_rhs_coef = nullptr; fr* d_coef = nullptr;
-    TRY(sc.alloc((void**)&d.tb, ((size_t)NC + 1) * 4));
-    TRY(sc.alloc((void**)&d.terms, (size_t)NT * sizeof(lig_lin_term)));
-    TRY(sc.alloc((void**)&d_rhs_c, (size_t)NR * 4));
-    TRY(sc.alloc((void**)&d_rhs_coef, (size_t)NR * 4));
-    TRY(sc.alloc((void**)&d.rhs_index, (size_t)NC * 4));
-    TRY(sc.alloc((void**)&d.heavy_dev, d.heavy.size() * 4));
-    TRY(sc.alloc((void**)&d_coef, (size_t)sys->n_coefs * 32));
+    TRY(f.upload(d.tb, sys->term_begin, (size_t)NC + 1));
+    TRY(f.upload(d.terms, sys->terms, NT));
+    TRY(f.upload(d_rhs_c, sys->rhs_constraint, NR));
+    TRY(f.upload(d_rhs_coef, sys->rhs_coef, NR));
+    TRY(f.alloc(d.rhs_index, NC));
+    TRY(f.upload(d.heavy_dev, d.heavy.data(), d.heavy.size()));
+    TRY(diag_upload_table(f, sys, d_coef));
     d.rhs_coef = d_rhs_coef; d.coef = d_coef;
-    HIP_TRY(c, hipMemcpyAsync(d.tb, sys->term_begin, ((size_t)NC + 1) * 4, hipMemcpyHostToDevice, s));
-    if (NT) HIP_TRY(c, hipMemcpyAsync(d.terms, sys->terms, (size_t)NT * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
-    if (NR) {
-        HIP_TRY(c, hipMemcpyAsync(d_rhs_c, sys->rhs_constraint, (size_t)NR * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_rhs_coef, sys->rhs_coef, (size_t)NR * 4, hipMemcpyHostToDevice, s));
-    }
-    if (!d.heavy.empty()) HIP_TRY(c, hipMemcpyAsync(d.heavy_dev, d.heavy.data(), d.heavy.size() * 4, hipMemcpyHostToDevice, s));
-    if (sys->n_coefs) HIP_TRY(c, hipMemcpyAsync(d_coef, sys->coefs, (size_t)sys->n_coefs * 32, hipMemcpyHostToDevice, s));
-    lig::launch_lin_coefs_mont(s, d_coef, sys->n_coefs);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemsetAsync(d.rhs_index, 0, (size_t)NC * 4, s));
-    if (NR) {
-        hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, d_rhs_c, NR, nullptr, d.rhs_index);
-        HIP_TRY(c, hipGetLastError());
-    }
+    TRY(f.zero(d.rhs_index, NC));
+    if (NR) TRY(f.launch(lig::k_diag_rhs_index, NR, d_rhs_c, NR, nullptr, d.rhs_index));
     return LIG_OK;
 }
 // The statement attached to the trace (v: prover_common.hpp) -> constraint-major, in scratch: count, scan, scatter (file header).
@@ -699,85 +738,75 @@ int diag_upload_system(lig_ctx* c, DiagScratch& sc, const lig_linear_system* sys
 // One rank's share of a sharded trace (v.sharded): compact = false numbers the segments as the whole trace does, through need[] -- for the
 // rank that holds every row, whose local slots are the trace's; compact = true keeps the rank's own numbers: d.NC = n_need segments, d.tb,
 // d.rhs_index and d.heavy all over i < n_need, local slots (lig_shard_rows_diagnose_attached).
-int diag_regroup_system(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, void** scan_tmp, size_t* scan_cap, const lig_linear_view& v, bool compact, DiagSystem& d) {
-    hipStream_t s = c->stream;
+int diag_regroup_system(DiagFrame& f, const lig_linear_view& v, bool compact, DiagSystem& d) {
+    lig_ctx* c = f.c;
+    hipStream_t s = f.s;
     const uint32_t NC = d.NC = (uint32_t)(compact ? v.n_need : v.n_constraints), NT = (uint32_t)v.n_terms, NR = (uint32_t)v.n_rhs;
     const uint32_t* number = v.sharded && !compact ? v.need : nullptr;
     const uint32_t heavy_cap = NT / (lig::HEAVY_MIN + 1) + 1;
     uint32_t *d_cursor = nullptr, *d_nheavy = nullptr;
-    TRY(sc.alloc((void**)&d.tb, ((size_t)NC + 1) * 4));
-    TRY(sc.alloc((void**)&d_cursor, ((size_t)NC + 1) * 4));
-    TRY(sc.alloc((void**)&d.terms, (size_t)NT * sizeof(lig_lin_term)));
-    TRY(sc.alloc((void**)&d.rhs_index, (size_t)NC * 4));
-    TRY(sc.alloc((void**)&d.heavy_dev, (size_t)heavy_cap * 4));
-    TRY(sc.alloc((void**)&d_nheavy, 4));
+    TRY(f.alloc(d.tb, (size_t)NC + 1));
+    TRY(f.alloc(d_cursor, (size_t)NC + 1));
+    TRY(f.alloc(d.terms, NT));
+    TRY(f.alloc(d.rhs_index, NC));
+    TRY(f.alloc(d.heavy_dev, heavy_cap));
+    TRY(f.alloc(d_nheavy, 1));
     d.rhs_coef = v.rhs_coef; d.coef = v.coef;
     // values set on the side stream (lig_rows_set_linear_values): the passes below read the table once its conversion has finished
     if (v.coef_ready) HIP_TRY(c, hipStreamWaitEvent(s, v.coef_ready, 0));
-    HIP_TRY(c, hipMemsetAsync(d_cursor, 0, ((size_t)NC + 1) * 4, s));
-    HIP_TRY(c, hipMemsetAsync(d_nheavy, 0, 4, s));
-    if (NT) hipLaunchKernelGGL(lig::k_diag_att_count, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, number, d_cursor);
-    hipLaunchKernelGGL(lig::k_diag_att_classify, dim3(diag_grid(NC)), dim3(lig::LIN_WG), 0, s, d_cursor, NC, d.heavy_dev, heavy_cap, d_nheavy);
-    HIP_TRY(c, hipGetLastError());
+    TRY(f.zero(d_cursor, (size_t)NC + 1));
+    TRY(f.zero(d_nheavy, 1));
+    if (NT) TRY(f.launch(lig::k_diag_att_count, NT, v.ent, NT, number, d_cursor));
+    TRY(f.launch(lig::k_diag_att_classify, NC, d_cursor, NC, d.heavy_dev, heavy_cap, d_nheavy));
     uint32_t total = 0, n_heavy = 0;
-    HIP_TRY(c, hipMemcpyAsync(&n_heavy, d_nheavy, 4, hipMemcpyDeviceToHost, s));
-    const int rc = diag_scan(c, sc, wait, d_cursor, d.tb, NC, scan_tmp, scan_cap, &total);
-    if (rc != LIG_OK) { (void)wait(); return rc; }      // (the copy into n_heavy may still be queued)
+    TRY(f.download(&n_heavy, d_nheavy, 1));
+    const int rc = f.scan(d_cursor, d.tb, NC, &total);
+    if (rc != LIG_OK) { (void)f.wait(); return rc; }      // (the copy into n_heavy may still be queued)
     if (total != NT || n_heavy > heavy_cap) FAIL(c, LIG_E_STATE, "lig_rows_diagnose_attached: the attached program's index does not add up to its term count");
     if (n_heavy) {      // ascending: the same launch geometry whatever order the atomics appended them in
         d.heavy.resize(n_heavy);
-        HIP_TRY(c, hipMemcpyAsync(d.heavy.data(), d.heavy_dev, (size_t)n_heavy * 4, hipMemcpyDeviceToHost, s));
-        TRY(wait());
+        TRY(f.fetch(d.heavy.data(), d.heavy_dev, n_heavy));
         std::sort(d.heavy.begin(), d.heavy.end());
         HIP_TRY(c, hipMemcpyAsync(d.heavy_dev, d.heavy.data(), (size_t)n_heavy * 4, hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(c, hipMemsetAsync(d_cursor, 0, ((size_t)NC + 1) * 4, s));
-    if (NT) hipLaunchKernelGGL(lig::k_diag_att_scatter, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, v.begin, v.n_slots, number, d.tb, d_cursor, d.terms);
-    HIP_TRY(c, hipMemsetAsync(d.rhs_index, 0, (size_t)NC * 4, s));
-    if (NR) hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, v.rhs_c, NR, number, d.rhs_index);
-    HIP_TRY(c, hipGetLastError());
+    TRY(f.zero(d_cursor, (size_t)NC + 1));
+    if (NT) TRY(f.launch(lig::k_diag_att_scatter, NT, v.ent, NT, v.begin, v.n_slots, number, d.tb, d_cursor, d.terms));
+    TRY(f.zero(d.rhs_index, NC));
+    if (NR) TRY(f.launch(lig::k_diag_rhs_index, NR, v.rhs_c, NR, number, d.rhs_index));
     return LIG_OK;
 }
 
 // The quadratic terms tri_dev[0 .. n_terms) over `msgs`, in slices of at most DIAG_QUAD_ITEMS items; the running count and the output offset
 // are carried on the host.  The first `cap` records go to host_out slice by slice (one GPU), or -- host_out == NULL -- stay on the device in
 // dev_out[0 .. cap) with the terms' ordinals in ord_out (a rank of a shard: rows through grow_dev, ordinals from ord_dev).
-int diag_quad_pass(lig_ctx* c, DiagScratch& sc, const DiagWait& wait, void** scan_tmp, size_t* scan_cap, const fr* msgs, const uint32_t* tri_dev, uint64_t n_terms,
-                   uint64_t cap, lig_diag_quad* host_out, lig_diag_quad* dev_out, const uint32_t* grow_dev, const uint32_t* ord_dev, uint32_t* ord_out,
-                   uint64_t* bad_total_out, uint64_t* reported_out) {
-    hipStream_t s = c->stream;
-    const uint32_t l = c->l, k = c->k;
-    const uint64_t l_recip = diag_reciprocal(l);
+int diag_quad_pass(DiagFrame& f, const fr* msgs, const uint32_t* tri_dev, uint64_t n_terms, uint64_t cap, lig_diag_quad* host_out, lig_diag_quad* dev_out,
+                   const uint32_t* grow_dev, const uint32_t* ord_dev, uint32_t* ord_out, uint64_t* bad_total_out, uint64_t* reported_out) {
+    const uint32_t l = f.l;
     const uint64_t per = std::max<uint64_t>(lig::DIAG_QUAD_ITEMS / l, 1);        // terms per slice: per * l < 2^32 (l < 2^32, and per = 1 beyond the budget)
     const uint64_t slice_items = std::min(per, n_terms) * l;
     uint32_t *d_flag = nullptr, *d_pos = nullptr; fr* d_res = nullptr;
-    TRY(sc.alloc((void**)&d_res, (size_t)slice_items * 32));
-    TRY(sc.alloc((void**)&d_flag, ((size_t)slice_items + 1) * 4));
-    TRY(sc.alloc((void**)&d_pos, ((size_t)slice_items + 1) * 4));
+    TRY(f.alloc(d_res, slice_items));
+    TRY(f.alloc(d_flag, (size_t)slice_items + 1));
+    TRY(f.alloc(d_pos, (size_t)slice_items + 1));
     if (host_out || !dev_out) {
         const uint64_t out_cap = std::min<uint64_t>(cap, slice_items);
-        if (out_cap) TRY(sc.alloc((void**)&dev_out, (size_t)out_cap * sizeof(lig_diag_quad)));
+        if (out_cap) TRY(f.alloc(dev_out, out_cap));
     }
     uint64_t bad_total = 0, reported = 0;
     for (uint64_t t0 = 0; t0 < n_terms; t0 += per) {
         const uint32_t items = (uint32_t)(std::min(per, n_terms - t0) * l);
-        HIP_TRY(c, hipMemsetAsync(d_flag + items, 0, 4, s));
-        hipLaunchKernelGGL(lig::k_diag_quad, dim3(diag_grid(items)), dim3(lig::LIN_WG), 0, s, tri_dev, (uint32_t)t0, items, msgs, l, k, l_recip, d_res, d_flag);
-        HIP_TRY(c, hipGetLastError());
+        TRY(f.zero(d_flag + items, 1));
+        TRY(f.launch(lig::k_diag_quad, items, tri_dev, (uint32_t)t0, items, msgs, l, f.k, f.l_recip, d_res, d_flag));
         uint32_t bad = 0;
-        TRY(diag_scan(c, sc, wait, d_flag, d_pos, items, scan_tmp, scan_cap, &bad));
-        if (bad > items) FAIL(c, LIG_E_STATE, "lig_rows_diagnose: counted more violated items than the slice holds");
+        TRY(f.scan(d_flag, d_pos, items, &bad));
+        if (bad > items) FAIL(f.c, LIG_E_STATE, "lig_rows_diagnose: counted more violated items than the slice holds");
         bad_total += bad;
         const uint32_t rep = (uint32_t)std::min<uint64_t>(bad, cap - reported);
         if (rep) {
             const uint64_t at = host_out ? 0 : reported;
-            hipLaunchKernelGGL(lig::k_diag_scatter_quad, dim3(diag_grid(items)), dim3(lig::LIN_WG), 0, s, d_flag, d_pos, d_res, tri_dev, (uint32_t)t0, items, l, l_recip,
-                               rep, dev_out + at, grow_dev, ord_dev, ord_out ? ord_out + at : nullptr);
-            HIP_TRY(c, hipGetLastError());
-            if (host_out) {
-                HIP_TRY(c, hipMemcpyAsync(host_out + reported, dev_out, (size_t)rep * sizeof(lig_diag_quad), hipMemcpyDeviceToHost, s));
-                TRY(wait());
-            }
+            TRY(f.launch(lig::k_diag_scatter_quad, items, d_flag, d_pos, d_res, tri_dev, (uint32_t)t0, items, l, f.l_recip, rep, dev_out + at, grow_dev, ord_dev,
+                         ord_out ? ord_out + at : nullptr));
+            if (host_out) TRY(f.fetch(host_out + reported, dev_out, rep));
             reported += rep;
         }
     }
@@ -794,51 +823,39 @@ namespace {
 // spin, then the blocking wait).
 int diag_rows(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* tri_dev, uint64_t n_quad_terms, const lig_linear_system* sys, const lig_linear_view* att,
               lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
-    hipStream_t s = c->stream;
-    const uint32_t l = c->l, k = c->k;
-    const uint64_t l_recip = diag_reciprocal(l);
-    DiagScratch sc(c);
-    void* scan_tmp = nullptr; size_t scan_cap = 0;
-    const DiagWait wait = [c, s]() -> int { HIP_TRY(c, lig_internal_wait_stream(s)); return LIG_OK; };
+    DiagFrame f(c);
+    const uint32_t l = f.l, k = f.k;
 
     // ---------------------------------------------------------------- linear constraints
     if (sys ? sys->n_constraints : att ? att->n_constraints : 0) {
         DiagSystem d;
-        if (sys) TRY(diag_upload_system(c, sc, sys, d));
-        else TRY(diag_regroup_system(c, sc, wait, &scan_tmp, &scan_cap, *att, false, d));
-        const uint32_t NC = d.NC;
+        if (sys) TRY(diag_upload_system(f, sys, d));
+        else TRY(diag_regroup_system(f, *att, false, d));
+        const uint32_t NC = d.NC, NH = (uint32_t)d.heavy.size();
         uint32_t *d_flag = nullptr, *d_pos = nullptr; fr* d_res = nullptr;
-        TRY(sc.alloc((void**)&d_res, (size_t)NC * 32));
-        TRY(sc.alloc((void**)&d_flag, ((size_t)NC + 1) * 4));
-        TRY(sc.alloc((void**)&d_pos, ((size_t)NC + 1) * 4));
-        HIP_TRY(c, hipMemsetAsync(d_flag, 0, ((size_t)NC + 1) * 4, s));
-        hipLaunchKernelGGL(lig::k_diag_lin, dim3(diag_grid(NC)), dim3(lig::LIN_WG), 0, s, d.tb, d.terms, NC, msgs, l, k, l_recip, d.coef, d.rhs_index, d.rhs_coef, d_res, d_flag);
-        HIP_TRY(c, hipGetLastError());
-        if (!d.heavy.empty()) {
-            hipLaunchKernelGGL(lig::k_diag_lin_heavy, dim3(std::min<uint32_t>((uint32_t)d.heavy.size(), lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d.heavy_dev,
-                               (uint32_t)d.heavy.size(), d.tb, d.terms, msgs, l, k, l_recip, d.coef, d.rhs_index, d.rhs_coef, d_res, d_flag);
-            HIP_TRY(c, hipGetLastError());
-        }
+        TRY(f.alloc(d_res, NC));
+        TRY(f.alloc(d_flag, (size_t)NC + 1));
+        TRY(f.alloc(d_pos, (size_t)NC + 1));
+        TRY(f.zero(d_flag, (size_t)NC + 1));
+        TRY(f.launch(lig::k_diag_lin, NC, d.tb, d.terms, NC, msgs, l, k, f.l_recip, d.coef, d.rhs_index, d.rhs_coef, d_res, d_flag));
+        if (NH) TRY(f.launch_blocks(lig::k_diag_lin_heavy, NH, d.heavy_dev, NH, d.tb, d.terms, msgs, l, k, f.l_recip, d.coef, d.rhs_index, d.rhs_coef, d_res, d_flag));
         uint32_t bad = 0;
-        TRY(diag_scan(c, sc, wait, d_flag, d_pos, NC, &scan_tmp, &scan_cap, &bad));
+        TRY(f.scan(d_flag, d_pos, NC, &bad));
         if (bad > NC) FAIL(c, LIG_E_STATE, "lig_rows_diagnose: counted more violated constraints than the system holds");
         info->n_linear_bad = bad;
         const uint32_t rep = (uint32_t)std::min<uint64_t>(bad, lin_cap);
         if (rep) {
             lig_diag_linear* d_out = nullptr;
-            TRY(sc.alloc((void**)&d_out, (size_t)rep * sizeof(lig_diag_linear)));
-            hipLaunchKernelGGL(lig::k_diag_scatter_lin, dim3(diag_grid(NC)), dim3(lig::LIN_WG), 0, s, d_flag, d_pos, d_res, NC, 0u, rep, d_out);
-            HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipMemcpyAsync(lin_out, d_out, (size_t)rep * sizeof(lig_diag_linear), hipMemcpyDeviceToHost, s));
-            TRY(wait());
+            TRY(f.alloc(d_out, rep));
+            TRY(f.launch(lig::k_diag_scatter_lin, NC, d_flag, d_pos, d_res, NC, 0u, rep, d_out));
+            TRY(f.fetch(lin_out, d_out, rep));
         }
         info->n_linear_reported = rep;
     }
 
     // ---------------------------------------------------------------- quadratic terms
     if (n_quad_terms && rows)
-        TRY(diag_quad_pass(c, sc, wait, &scan_tmp, &scan_cap, msgs, tri_dev, n_quad_terms, quad_cap, quad_out, nullptr, nullptr, nullptr, nullptr, &info->n_quad_bad,
-                           &info->n_quad_reported));
+        TRY(diag_quad_pass(f, msgs, tri_dev, n_quad_terms, quad_cap, quad_out, nullptr, nullptr, nullptr, nullptr, &info->n_quad_bad, &info->n_quad_reported));
     return LIG_OK;
 }
 }  // namespace
@@ -856,90 +873,95 @@ int lig_internal_rows_diagnose_attached(lig_ctx* c, const fr* msgs, uint64_t row
 }
 
 namespace {
+// The tail every explain entry ends with: the items in output order (explain_order / explain_merge) -> the two record arrays.
+//   explain_upload    the m ordered terms, the asked index of the first `rep` of them and first[0 .. NA] -> scratch.  o holds the sources of
+//                     the queued uploads: it is declared before the frame.
+//   explain_records   k_explain_fill / k_explain_finish over them with the witness source `wit`, both arrays to the host.  Blocks once.
+//                     terms_out may be NULL when rep = 0 (lig_internal_rows_explain_slots asks for the constraint records alone).
+// What lies between the two stays with the entry (the value exchange of a shard, which reads d_ordered).
+struct ExplainOrdered {
+    std::vector<lig_lin_term> ordered;
+    std::vector<uint32_t> ask, first32;
+    uint32_t m = 0, rep = 0, NA = 0;
+    lig_lin_term* d_ordered = nullptr; uint32_t *d_ask = nullptr, *d_first = nullptr;
+};
+int explain_upload(DiagFrame& f, const std::vector<lig::ExplainItem>& items, const std::vector<uint64_t>& first, uint32_t NA, uint32_t rep, ExplainOrdered& o) {
+    o.m = (uint32_t)items.size(); o.rep = rep; o.NA = NA;
+    o.ordered.resize(o.m);
+    o.ask.resize(rep);
+    o.first32.assign(first.begin(), first.end());
+    for (uint32_t i = 0; i < o.m; i++) { o.ordered[i].slot = items[i].slot; o.ordered[i].coef = items[i].coef; }
+    for (uint32_t i = 0; i < rep; i++) o.ask[i] = items[i].ask;
+    TRY(f.upload(o.d_ordered, o.ordered.data(), o.m));
+    TRY(f.upload(o.d_ask, o.ask.data(), rep));
+    return f.upload(o.d_first, o.first32.data(), (size_t)NA + 1);
+}
+template <class Wit>
+int explain_records(DiagFrame& f, const ExplainOrdered& o, const uint32_t* d_asked, const Wit& wit, const fr* coef, const uint32_t* rhs_index, const uint32_t* rhs_coef,
+                    lig_explain_constraint* con_out, lig_explain_term* terms_out) {
+    lig_explain_constraint* d_con = nullptr; lig_explain_term* d_out = nullptr;
+    TRY(f.alloc(d_con, o.NA));
+    TRY(f.alloc(d_out, o.rep));
+    if (o.rep) TRY(f.launch(lig::k_explain_fill<Wit>, o.rep, o.d_ordered, o.d_ask, o.rep, d_asked, wit, coef, d_out));
+    TRY(f.launch_blocks(lig::k_explain_finish<Wit>, o.NA, o.d_first, o.d_ordered, d_asked, o.NA, wit, coef, rhs_index, rhs_coef, d_con));
+    TRY(f.download(con_out, d_con, o.NA));
+    TRY(f.download(terms_out, d_out, o.rep));
+    return f.wait();
+}
+
 // The two explain entries (lig_hip.h).  The statement is `sys` (it has passed lig_linear_check against the trace's kinds) or `att` (the view of
 // the trace's attachment, not sharded), exactly one of them; asked[0 .. n_asked) has passed explain_asked_ok against its constraint count and
 // n_asked > 0.  Where the unordered items come from is all that differs (the kernels' header above).  Blocks twice: for the items (ordered on
 // the host), and for the records.
 int explain_rows(lig_ctx* c, const fr* msgs, const lig_linear_system* sys, const lig_linear_view* att, const uint32_t* asked, uint64_t n_asked,
                  lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info) {
-    hipStream_t s = c->stream;
-    const uint32_t l = c->l, k = c->k, NA = (uint32_t)n_asked;
-    const uint64_t l_recip = diag_reciprocal(l);
-    // (sources and targets of queued copies: declared before the scratch, whose destructor drains the stream)
+    const uint32_t NA = (uint32_t)n_asked;
+    // (sources and targets of queued copies: declared before the frame, whose scratch drains the stream when it goes)
     std::vector<lig::ExplainItem> items;
     std::vector<uint64_t> first;
-    std::vector<uint32_t> pre, first32, ask;
-    std::vector<lig_lin_term> ordered;
-    DiagScratch sc(c);
-    void* scan_tmp = nullptr; size_t scan_cap = 0;
-    const DiagWait wait = [c, s]() -> int { HIP_TRY(c, lig_internal_wait_stream(s)); return LIG_OK; };
+    std::vector<uint32_t> pre;
+    ExplainOrdered o;
+    DiagFrame f(c);
 
     uint32_t* d_asked = nullptr; lig::ExplainItem* d_items = nullptr;
-    TRY(sc.alloc((void**)&d_asked, (size_t)NA * 4));
-    HIP_TRY(c, hipMemcpyAsync(d_asked, asked, (size_t)NA * 4, hipMemcpyHostToDevice, s));
+    TRY(f.upload(d_asked, asked, NA));
     DiagSystem d;
     uint32_t m = 0;
     if (sys) {
-        TRY(diag_upload_system(c, sc, sys, d));
+        TRY(diag_upload_system(f, sys, d));
         pre.assign((size_t)NA + 1, 0);
         for (uint32_t a = 0; a < NA; a++) pre[a + 1] = pre[a] + (sys->term_begin[asked[a] + 1] - sys->term_begin[asked[a]]);      // <= n_terms < 2^32: the asked are distinct
         m = pre[NA];
         uint32_t* d_pre = nullptr;
-        TRY(sc.alloc((void**)&d_pre, ((size_t)NA + 1) * 4));
-        TRY(sc.alloc((void**)&d_items, (size_t)m * sizeof(lig::ExplainItem)));
-        HIP_TRY(c, hipMemcpyAsync(d_pre, pre.data(), ((size_t)NA + 1) * 4, hipMemcpyHostToDevice, s));
-        if (m) hipLaunchKernelGGL(lig::k_explain_gather, dim3(diag_grid(m)), dim3(lig::LIN_WG), 0, s, d.tb, d.terms, d_asked, NA, d_pre, m, d_items);
-        HIP_TRY(c, hipGetLastError());
+        TRY(f.upload(d_pre, pre.data(), (size_t)NA + 1));
+        TRY(f.alloc(d_items, m));
+        if (m) TRY(f.launch(lig::k_explain_gather, m, d.tb, d.terms, d_asked, NA, d_pre, m, d_items));
     } else {
         const lig_linear_view& v = *att;
         const uint32_t NC = d.NC = (uint32_t)v.n_constraints, NT = (uint32_t)v.n_terms, NR = (uint32_t)v.n_rhs;
         uint32_t *d_mark = nullptr, *d_pos = nullptr;
-        TRY(sc.alloc((void**)&d_mark, ((size_t)NT + 1) * 4));
-        TRY(sc.alloc((void**)&d_pos, ((size_t)NT + 1) * 4));
-        TRY(sc.alloc((void**)&d.rhs_index, (size_t)NC * 4));
+        TRY(f.alloc(d_mark, (size_t)NT + 1));
+        TRY(f.alloc(d_pos, (size_t)NT + 1));
+        TRY(f.alloc(d.rhs_index, NC));
         d.rhs_coef = v.rhs_coef; d.coef = v.coef;
         // values set on the side stream (lig_rows_set_linear_values): the table is read once its conversion has finished
-        if (v.coef_ready) HIP_TRY(c, hipStreamWaitEvent(s, v.coef_ready, 0));
-        HIP_TRY(c, hipMemsetAsync(d_mark + NT, 0, 4, s));
-        if (NT) hipLaunchKernelGGL(lig::k_explain_mark, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, nullptr, d_asked, NA, d_mark);
-        HIP_TRY(c, hipGetLastError());
-        TRY(diag_scan(c, sc, wait, rocprim::make_transform_iterator((const uint32_t*)d_mark, lig::ExplainMarked{}), d_pos, NT, &scan_tmp, &scan_cap, &m));
+        if (v.coef_ready) HIP_TRY(c, hipStreamWaitEvent(f.s, v.coef_ready, 0));
+        TRY(f.zero(d_mark + NT, 1));
+        if (NT) TRY(f.launch(lig::k_explain_mark, NT, v.ent, NT, nullptr, d_asked, NA, d_mark));
+        TRY(f.scan(rocprim::make_transform_iterator((const uint32_t*)d_mark, lig::ExplainMarked{}), d_pos, NT, &m));
         if (m > NT) FAIL(c, LIG_E_STATE, "lig_rows_explain_attached: counted more asked terms than the attached program holds");
-        TRY(sc.alloc((void**)&d_items, (size_t)m * sizeof(lig::ExplainItem)));
-        if (m) hipLaunchKernelGGL(lig::k_explain_collect, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, v.ent, NT, v.begin, v.n_slots, d_mark, d_pos, d_items);
-        HIP_TRY(c, hipMemsetAsync(d.rhs_index, 0, (size_t)NC * 4, s));
-        if (NR) hipLaunchKernelGGL(lig::k_diag_rhs_index, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, v.rhs_c, NR, nullptr, d.rhs_index);
-        HIP_TRY(c, hipGetLastError());
+        TRY(f.alloc(d_items, m));
+        if (m) TRY(f.launch(lig::k_explain_collect, NT, v.ent, NT, v.begin, v.n_slots, d_mark, d_pos, d_items));
+        TRY(f.zero(d.rhs_index, NC));
+        if (NR) TRY(f.launch(lig::k_diag_rhs_index, NR, v.rhs_c, NR, nullptr, d.rhs_index));
     }
     // the m items -> the output order, on the host (explain_plan.hpp)
     items.resize(m);
-    if (m) HIP_TRY(c, hipMemcpyAsync(items.data(), d_items, (size_t)m * sizeof(lig::ExplainItem), hipMemcpyDeviceToHost, s));
-    TRY(wait());
+    TRY(f.fetch(items.data(), d_items, m));
     if (!lig::explain_order(items, NA, first)) FAIL(c, LIG_E_STATE, "lig_rows_explain: a collected term names no asked constraint");
     const uint32_t rep = (uint32_t)std::min<uint64_t>(m, term_cap);
-    ordered.resize(m);
-    ask.resize(rep);
-    first32.assign(first.begin(), first.end());
-    for (uint32_t i = 0; i < m; i++) { ordered[i].slot = items[i].slot; ordered[i].coef = items[i].coef; }
-    for (uint32_t i = 0; i < rep; i++) ask[i] = items[i].ask;
-    lig_lin_term* d_ordered = nullptr; uint32_t *d_ask = nullptr, *d_first = nullptr;
-    lig_explain_constraint* d_con = nullptr; lig_explain_term* d_out = nullptr;
-    TRY(sc.alloc((void**)&d_ordered, (size_t)m * sizeof(lig_lin_term)));
-    TRY(sc.alloc((void**)&d_ask, (size_t)rep * 4));
-    TRY(sc.alloc((void**)&d_first, ((size_t)NA + 1) * 4));
-    TRY(sc.alloc((void**)&d_con, (size_t)NA * sizeof(lig_explain_constraint)));
-    TRY(sc.alloc((void**)&d_out, (size_t)rep * sizeof(lig_explain_term)));
-    if (m) HIP_TRY(c, hipMemcpyAsync(d_ordered, ordered.data(), (size_t)m * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
-    if (rep) HIP_TRY(c, hipMemcpyAsync(d_ask, ask.data(), (size_t)rep * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_first, first32.data(), ((size_t)NA + 1) * 4, hipMemcpyHostToDevice, s));
-    const lig::ExplainFromMatrix wit{msgs, l, k, l_recip};
-    if (rep) hipLaunchKernelGGL(lig::k_explain_fill<lig::ExplainFromMatrix>, dim3(diag_grid(rep)), dim3(lig::LIN_WG), 0, s, d_ordered, d_ask, rep, d_asked, wit, d.coef, d_out);
-    hipLaunchKernelGGL(lig::k_explain_finish<lig::ExplainFromMatrix>, dim3(std::min<uint32_t>(NA, lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d_first, d_ordered, d_asked, NA,
-                       wit, d.coef, d.rhs_index, d.rhs_coef, d_con);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(con_out, d_con, (size_t)NA * sizeof(lig_explain_constraint), hipMemcpyDeviceToHost, s));
-    if (rep) HIP_TRY(c, hipMemcpyAsync(terms_out, d_out, (size_t)rep * sizeof(lig_explain_term), hipMemcpyDeviceToHost, s));
-    TRY(wait());
+    TRY(explain_upload(f, items, first, NA, rep, o));
+    TRY(explain_records(f, o, d_asked, lig::ExplainFromMatrix{msgs, f.l, f.k, f.l_recip}, d.coef, d.rhs_index, d.rhs_coef, con_out, terms_out));
     info->n_terms_total = m;
     info->n_terms_reported = rep;
     return LIG_OK;
@@ -967,19 +989,16 @@ int lig_internal_rows_explain_attached(lig_ctx* c, const fr* msgs, const lig_lin
 int lig_internal_rows_read_slots(lig_ctx* c, const fr* msgs, uint64_t rows, const uint32_t* slots, uint64_t n_slots, uint8_t* values) {
     if (!lig::explain_slots_ok(slots, n_slots, rows, c->l)) FAIL(c, LIG_E_ARG, "lig_rows_read_slots: a slot is not below rows * l");
     if (!n_slots) return LIG_OK;
-    hipStream_t s = c->stream;
-    const uint64_t l_recip = diag_reciprocal(c->l), piece = std::min<uint64_t>(n_slots, 1ull << 24);
-    DiagScratch sc(c);
+    const uint64_t piece = std::min<uint64_t>(n_slots, 1ull << 24);
+    DiagFrame f(c);
     uint32_t* d_slots = nullptr; fr* d_val = nullptr;
-    TRY(sc.alloc((void**)&d_slots, (size_t)piece * 4));
-    TRY(sc.alloc((void**)&d_val, (size_t)piece * 32));
+    TRY(f.alloc(d_slots, piece));
+    TRY(f.alloc(d_val, piece));
     for (uint64_t at = 0; at < n_slots; at += piece) {
         const uint32_t n = (uint32_t)std::min(piece, n_slots - at);
-        HIP_TRY(c, hipMemcpyAsync(d_slots, slots + at, (size_t)n * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(lig::k_read_slots, dim3(diag_grid(n)), dim3(lig::LIN_WG), 0, s, d_slots, n, msgs, c->l, c->k, l_recip, d_val);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(values + at * 32, d_val, (size_t)n * 32, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, lig_internal_wait_stream(s));
+        HIP_TRY(c, hipMemcpyAsync(d_slots, slots + at, (size_t)n * 4, hipMemcpyHostToDevice, f.s));
+        TRY(f.launch(lig::k_read_slots, n, d_slots, n, msgs, f.l, f.k, f.l_recip, d_val));
+        TRY(f.fetch(values + at * 32, d_val, n));
     }
     return LIG_OK;
 }
@@ -995,55 +1014,41 @@ int lig_internal_rows_explain_slots(lig_ctx* c, const fr* msgs, const uint8_t* k
     if (!lig::explain_slots_ok(slots, n_asked, rows, c->l)) FAIL(c, LIG_E_ARG, "lig_rows_explain_slots: a slot is not below rows * l");
     for (uint64_t i = 1; i < n_asked; i++) if (slots[i] <= slots[i - 1]) FAIL(c, LIG_E_ARG, "lig_rows_explain_slots: the asked slots must be strictly ascending");
     if (!n_asked) return LIG_OK;
-    hipStream_t s = c->stream;
-    const uint32_t l = c->l, k = c->k, NA = (uint32_t)n_asked, NT = (uint32_t)v.n_terms;
-    const uint64_t l_recip = diag_reciprocal(l);
-    // (sources and targets of queued copies: declared before the scratch, whose destructor drains the stream)
+    const uint32_t l = c->l, NA = (uint32_t)n_asked, NT = (uint32_t)v.n_terms;
+    // (sources and targets of queued copies: declared before the frame, whose scratch drains the stream when it goes)
     std::vector<uint32_t> pre((size_t)NA + 1), heavy, distinct, cidx;
     std::vector<lig::ExplainItem> items;
     std::vector<uint64_t> first;
     std::vector<lig_explain_constraint> con;
     std::vector<fr> vals(NA);
-    DiagScratch sc(c);
-    void* scan_tmp = nullptr; size_t scan_cap = 0;
-    const DiagWait wait = [c, s]() -> int { HIP_TRY(c, lig_internal_wait_stream(s)); return LIG_OK; };
+    DiagFrame f(c);
 
     uint32_t *d_slots = nullptr, *d_len = nullptr, *d_pre = nullptr; fr* d_val = nullptr;
-    TRY(sc.alloc((void**)&d_slots, (size_t)NA * 4));
-    TRY(sc.alloc((void**)&d_len, ((size_t)NA + 1) * 4));
-    TRY(sc.alloc((void**)&d_pre, ((size_t)NA + 1) * 4));
-    TRY(sc.alloc((void**)&d_val, (size_t)NA * 32));
-    HIP_TRY(c, hipMemcpyAsync(d_slots, slots, (size_t)NA * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(d_len + NA, 0, 4, s));
-    hipLaunchKernelGGL(lig::k_slot_len, dim3(diag_grid(NA)), dim3(lig::LIN_WG), 0, s, d_slots, NA, v.begin, d_len);
-    hipLaunchKernelGGL(lig::k_read_slots, dim3(diag_grid(NA)), dim3(lig::LIN_WG), 0, s, d_slots, NA, msgs, l, k, l_recip, d_val);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(vals.data(), d_val, (size_t)NA * 32, hipMemcpyDeviceToHost, s));
-    uint32_t m = 0;
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_cap, d_len, d_pre, 0u, (size_t)NA + 1, rocprim::plus<uint32_t>(), s));
-    TRY(sc.alloc(&scan_tmp, scan_cap));
-    HIP_TRY(c, rocprim::exclusive_scan(scan_tmp, scan_cap, d_len, d_pre, 0u, (size_t)NA + 1, rocprim::plus<uint32_t>(), s));
-    HIP_TRY(c, hipMemcpyAsync(pre.data(), d_pre, ((size_t)NA + 1) * 4, hipMemcpyDeviceToHost, s));
-    TRY(wait());
-    m = pre[NA];
+    TRY(f.upload(d_slots, slots, NA));
+    TRY(f.alloc(d_len, (size_t)NA + 1));
+    TRY(f.alloc(d_pre, (size_t)NA + 1));
+    TRY(f.alloc(d_val, NA));
+    TRY(f.zero(d_len + NA, 1));
+    TRY(f.launch(lig::k_slot_len, NA, d_slots, NA, v.begin, d_len));
+    TRY(f.launch(lig::k_read_slots, NA, d_slots, NA, msgs, l, f.k, f.l_recip, d_val));
+    TRY(f.download(vals.data(), d_val, NA));
+    TRY(f.scan_enqueue(d_len, d_pre, NA));
+    TRY(f.fetch(pre.data(), d_pre, (size_t)NA + 1));
+    const uint32_t m = pre[NA];
     // distinct slots own disjoint segments: the lengths add up to at most n_terms, every prefix sum is exact in 32 bits
     if (m > NT || !std::is_sorted(pre.begin(), pre.end())) FAIL(c, LIG_E_STATE, "lig_rows_explain_slots: the program's index does not add up to its term count");
     for (uint32_t a = 0; a < NA; a++) if (pre[a + 1] - pre[a] > lig::HEAVY_MIN) heavy.push_back(a);
 
     lig::ExplainItem* d_items = nullptr;
-    TRY(sc.alloc((void**)&d_items, (size_t)m * sizeof(lig::ExplainItem)));
-    if (m) hipLaunchKernelGGL(lig::k_slot_collect, dim3(diag_grid(m)), dim3(lig::LIN_WG), 0, s, d_slots, NA, d_pre, m, v.begin, v.ent, d_items);
+    TRY(f.alloc(d_items, m));
+    if (m) TRY(f.launch(lig::k_slot_collect, m, d_slots, NA, d_pre, m, v.begin, v.ent, d_items));
     if (!heavy.empty()) {
         uint32_t* d_heavy = nullptr;
-        TRY(sc.alloc((void**)&d_heavy, heavy.size() * 4));
-        HIP_TRY(c, hipMemcpyAsync(d_heavy, heavy.data(), heavy.size() * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(lig::k_slot_collect_heavy, dim3(std::min<uint32_t>((uint32_t)heavy.size(), lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d_heavy,
-                           (uint32_t)heavy.size(), d_slots, d_pre, v.begin, v.ent, d_items);
+        TRY(f.upload(d_heavy, heavy.data(), heavy.size()));
+        TRY(f.launch_blocks(lig::k_slot_collect_heavy, (uint32_t)heavy.size(), d_heavy, (uint32_t)heavy.size(), d_slots, d_pre, v.begin, v.ent, d_items));
     }
-    HIP_TRY(c, hipGetLastError());
     items.resize(m);
-    if (m) HIP_TRY(c, hipMemcpyAsync(items.data(), d_items, (size_t)m * sizeof(lig::ExplainItem), hipMemcpyDeviceToHost, s));
-    TRY(wait());
+    TRY(f.fetch(items.data(), d_items, m));
     // the m items -> the output order (asked slot, constraint, coefficient index), on the host; the distinct constraints, ascending
     if (!lig::explain_order(items, NA, first)) FAIL(c, LIG_E_STATE, "lig_rows_explain_slots: a collected term names no asked slot");
     distinct.resize(m);
@@ -1065,18 +1070,14 @@ int lig_internal_rows_explain_slots(lig_ctx* c, const fr* msgs, const uint8_t* k
         cidx.resize(rep);
         for (uint32_t i = 0; i < rep; i++) cidx[i] = (uint32_t)(std::lower_bound(distinct.begin(), distinct.end(), items[i].slot) - distinct.begin());
         uint32_t* d_cidx = nullptr; lig_explain_constraint* d_con = nullptr; lig_slot_term* d_out = nullptr;
-        TRY(sc.alloc((void**)&d_cidx, (size_t)rep * 4));
-        TRY(sc.alloc((void**)&d_con, (size_t)ND * sizeof(lig_explain_constraint)));
-        TRY(sc.alloc((void**)&d_out, (size_t)rep * sizeof(lig_slot_term)));
-        HIP_TRY(c, hipMemcpyAsync(d_items, items.data(), (size_t)rep * sizeof(lig::ExplainItem), hipMemcpyHostToDevice, s));      // the ordered ones over the collected
-        HIP_TRY(c, hipMemcpyAsync(d_cidx, cidx.data(), (size_t)rep * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_con, con.data(), (size_t)ND * sizeof(lig_explain_constraint), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_items, items.data(), (size_t)rep * sizeof(lig::ExplainItem), hipMemcpyHostToDevice, f.s));      // the ordered ones over the collected
+        TRY(f.upload(d_cidx, cidx.data(), rep));
+        TRY(f.upload(d_con, con.data(), ND));
+        TRY(f.alloc(d_out, rep));
         // values set on the side stream (lig_rows_set_linear_values): the table is read once its conversion has finished
-        if (v.coef_ready) HIP_TRY(c, hipStreamWaitEvent(s, v.coef_ready, 0));
-        hipLaunchKernelGGL(lig::k_slot_fill, dim3(diag_grid(rep)), dim3(lig::LIN_WG), 0, s, d_items, d_cidx, rep, d_slots, d_con, v.coef, d_out);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(terms_out, d_out, (size_t)rep * sizeof(lig_slot_term), hipMemcpyDeviceToHost, s));
-        TRY(wait());
+        if (v.coef_ready) HIP_TRY(c, hipStreamWaitEvent(f.s, v.coef_ready, 0));
+        TRY(f.launch(lig::k_slot_fill, rep, d_items, d_cidx, rep, d_slots, d_con, v.coef, d_out));
+        TRY(f.fetch(terms_out, d_out, rep));
     }
     for (uint32_t a = 0; a < NA; a++) {
         lig_slot_record& r = slot_out[a];
@@ -1099,46 +1100,33 @@ int lig_internal_rows_untouched_slots(lig_ctx* c, const fr* msgs, const uint8_t*
     static constexpr uint64_t UNTOUCHED_ITEMS = 1ull << 22;      // scratch budget: slots per slice (16 bytes each)
     if (v.sharded) FAIL(c, LIG_E_STATE, "lig_rows_untouched_slots: the attached structure is one rank's share of a sharded trace");
     if ((uint64_t)v.n_slots != rows * (uint64_t)c->l) FAIL(c, LIG_E_STATE, "lig_rows_untouched_slots: the program does not cover the slots of this trace");
-    hipStream_t s = c->stream;
-    const uint32_t l = c->l, k = c->k;
-    const uint64_t l_recip = diag_reciprocal(l);
-    std::vector<uint2> lrows;      // (source of a queued copy: declared before the scratch)
+    const uint32_t l = c->l;
+    std::vector<uint2> lrows;      // (source of a queued copy: declared before the frame)
     for (uint64_t r = 0; r < rows; r++) if ((kinds[r] & 0x7fu) <= LIG_ROW_QZ) lrows.push_back(make_uint2((uint32_t)r, kinds[r] & 0x7fu));
     const uint64_t NL = lrows.size();
     if (!NL) return LIG_OK;
-    DiagScratch sc(c);
+    DiagFrame f(c);
     const uint64_t per = std::max<uint64_t>(UNTOUCHED_ITEMS / l, 1);      // rows per slice: per * l < 2^32 (rows * l < 2^32: lig_linear_check)
     const uint64_t slice_items = std::min(per, NL) * l, out_cap = std::min<uint64_t>(cap, slice_items);
-    uint2* d_lrows = nullptr; uint64_t *d_flag = nullptr, *d_pos = nullptr; lig_slot_value* d_out = nullptr; void* scan_tmp = nullptr;
-    TRY(sc.alloc((void**)&d_lrows, (size_t)NL * sizeof(uint2)));
-    TRY(sc.alloc((void**)&d_flag, ((size_t)slice_items + 1) * 8));
-    TRY(sc.alloc((void**)&d_pos, ((size_t)slice_items + 1) * 8));
-    if (out_cap) TRY(sc.alloc((void**)&d_out, (size_t)out_cap * sizeof(lig_slot_value)));
-    size_t scan_cap = 0;
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, scan_cap, d_flag, d_pos, (uint64_t)0, (size_t)slice_items + 1, rocprim::plus<uint64_t>(), s));
-    TRY(sc.alloc(&scan_tmp, scan_cap));
-    HIP_TRY(c, hipMemcpyAsync(d_lrows, lrows.data(), (size_t)NL * sizeof(uint2), hipMemcpyHostToDevice, s));
+    uint2* d_lrows = nullptr; uint64_t *d_flag = nullptr, *d_pos = nullptr; lig_slot_value* d_out = nullptr;
+    TRY(f.upload(d_lrows, lrows.data(), NL));
+    TRY(f.alloc(d_flag, (size_t)slice_items + 1));
+    TRY(f.alloc(d_pos, (size_t)slice_items + 1));
+    if (out_cap) TRY(f.alloc(d_out, out_cap));
     uint64_t n_untouched = 0, n_nonzero = 0, reported = 0;
-    for (uint64_t r0 = 0; r0 < NL; r0 += per) {
+    for (uint64_t r0 = 0; r0 < NL; r0 += per) {      // (the first slice is the largest: its scan sizes the temp for all of them)
         const uint32_t items = (uint32_t)(std::min(per, NL - r0) * l);
-        HIP_TRY(c, hipMemsetAsync(d_flag + items, 0, 8, s));
-        hipLaunchKernelGGL(lig::k_untouched_flag, dim3(diag_grid(items)), dim3(lig::LIN_WG), 0, s, d_lrows, (uint32_t)r0, items, v.begin, msgs, l, k, l_recip, d_flag);
-        HIP_TRY(c, hipGetLastError());
-        size_t tmp = scan_cap;
-        HIP_TRY(c, rocprim::exclusive_scan(scan_tmp, tmp, d_flag, d_pos, (uint64_t)0, (size_t)items + 1, rocprim::plus<uint64_t>(), s));
-        uint64_t both = 0;
-        HIP_TRY(c, hipMemcpyAsync(&both, d_pos + items, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, lig_internal_wait_stream(s));
+        TRY(f.zero(d_flag + items, 1));
+        TRY(f.launch(lig::k_untouched_flag, items, d_lrows, (uint32_t)r0, items, v.begin, msgs, l, f.k, f.l_recip, d_flag));
+        uint64_t both = 0;      // the two counts of the slice, packed
+        TRY(f.scan(d_flag, d_pos, items, &both));
         const uint32_t un = (uint32_t)both, nz = (uint32_t)(both >> 32);
         if (un > items || nz > un) FAIL(c, LIG_E_STATE, "lig_rows_untouched_slots: counted more slots than the slice holds");
         n_untouched += un; n_nonzero += nz;
         const uint32_t rep = (uint32_t)std::min<uint64_t>(nonzero_only ? nz : un, cap - reported);
         if (rep) {
-            hipLaunchKernelGGL(lig::k_untouched_compact, dim3(diag_grid(items)), dim3(lig::LIN_WG), 0, s, d_flag, d_pos, d_lrows, (uint32_t)r0, items, msgs, l, k, l_recip,
-                               nonzero_only ? 1u : 0u, rep, d_out);
-            HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipMemcpyAsync(out + reported, d_out, (size_t)rep * sizeof(lig_slot_value), hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, lig_internal_wait_stream(s));
+            TRY(f.launch(lig::k_untouched_compact, items, d_flag, d_pos, d_lrows, (uint32_t)r0, items, msgs, l, f.k, f.l_recip, nonzero_only ? 1u : 0u, rep, d_out));
+            TRY(f.fetch(out + reported, d_out, rep));
             reported += rep;
         }
     }
@@ -1147,6 +1135,62 @@ int lig_internal_rows_untouched_slots(lig_ctx* c, const fr* msgs, const uint8_t*
     info->n_reported = reported;
     return LIG_OK;
 }
+
+namespace {
+// The frame of one rank's call on a sharded rows job (v: prover_common.hpp): it waits with v.drain(who), the bounded poll, issues the
+// collectives and holds the rule every such entry ends by -- run(): a poisoned shard abandons its scratch; otherwise the stream drains and
+// v.forget runs BEFORE the frame goes and frees a send buffer (lig_comm.forget).  Every send buffer is an allocation of its own.
+// LIG_TRACE: mark(p) closes phase p with a wait, a synchronised split of the call on stderr, one line per successful call:
+//   [lig_trace] <name> rank <r>: <phase> <ms> ... ms
+// alone (lig_shard_rows_explain_attached): the one rank of its world -- a device copy in place of every all-gather, no collective.
+struct DiagShardFrame : DiagFrame {
+    const lig_diag_shard& v;
+    const char* const name;
+    const std::vector<const char*> phases;
+    const bool alone, trace_on = lig::knobs().trace;
+    bool used_comm = false;
+    std::vector<double> ph;
+    clk::time_point t_mark = clk::now();
+    DiagShardFrame(lig_ctx* c_, const lig_diag_shard& v_, const char* who, const char* name_, std::initializer_list<const char*> phases_, bool alone_ = false)
+        : DiagFrame(c_, [&v_, who]() -> int { return v_.drain(who); }), v(v_), name(name_), phases(phases_), alone(alone_), ph(phases_.size(), 0.0) {}
+
+    int mark(int p) {
+        if (!trace_on) return LIG_OK;
+        TRY(wait());
+        ph[p] += ms_since(t_mark);
+        t_mark = clk::now();
+        return LIG_OK;
+    }
+    int all_to_all(const void* src, void* dst, size_t bytes, const char* what) {
+        used_comm = true;
+        return v.all_to_all(src, dst, bytes, what);
+    }
+    int all_gather(const void* src, void* dst, size_t bytes, const char* what) {
+        if (alone) { HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s)); return LIG_OK; }
+        used_comm = true;
+        return v.all_gather(src, dst, bytes, what);
+    }
+    template <class Body> int run(Body body) {
+        const int rc = body();
+        if (rc != LIG_OK && v.settle_failed()) { sc.abandon(); return rc; }      // poisoned: the scratch outlives the call
+        if (rc == LIG_OK) (void)wait();
+        if (used_comm) v.forget();                                                // before any send buffer is freed
+        if (trace_on && rc == LIG_OK) {
+            char num[32];
+            std::string line = std::string("[lig_trace] ") + name + " rank " + std::to_string(v.rank) + ":";
+            for (size_t p = 0; p < phases.size(); p++) { std::snprintf(num, sizeof num, " %.3f", ph[p]); line += std::string(" ") + phases[p] + num; }
+            std::fprintf(stderr, "%s ms\n", line.c_str());
+        }
+        return rc;
+    }
+};
+// the rank's global -> local row table (LIN_NOT_LOCAL: another rank holds that row) -> scratch; local_of is the source of the queued upload
+int diag_row_table(DiagFrame& f, const lig_diag_shard& v, std::vector<uint32_t>& local_of, uint32_t*& d_local) {
+    local_of.assign(v.rows_global, lig::LIN_NOT_LOCAL);
+    for (size_t lr = 0; lr < v.grow->size(); lr++) local_of[(*v.grow)[lr]] = (uint32_t)lr;
+    return f.upload(d_local, local_of.data(), local_of.size());
+}
+}  // namespace
 
 // One rank of a sharded rows job (lig_shard_rows_diagnose, lig_hip.h; v: prover_common.hpp).  Collective: whether a collective is issued,
 // how many and of which size depends on sys' sizes, the caps, the world size and the slice knob alone -- never on what this rank holds.
@@ -1167,44 +1211,29 @@ int lig_internal_rows_untouched_slots(lig_ctx* c, const fr* msgs, const uint8_t*
 namespace {
 int shard_diagnose(const char* who, lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, const lig_linear_view* att, lig_diag_linear* lin_out,
                    uint64_t lin_cap, lig_diag_quad* quad_out, uint64_t quad_cap, lig_diag_info* info) {
-    hipStream_t s = c->stream;
-    const uint32_t l = c->l, k = c->k, W = v.world;
-    const uint64_t l_recip = diag_reciprocal(l);
-    DiagScratch sc(c);
-    void* scan_tmp = nullptr; size_t scan_cap = 0;
-    bool used_comm = false;
-    const DiagWait wait = [&v, who]() -> int { return v.drain(who); };
-    // LIG_TRACE: a synchronised split of the call into its phases on stderr
-    const bool trace_on = lig::knobs().trace;
-    enum { PH_PARTIAL, PH_EXCHANGE, PH_REDUCE, PH_RECORDS, PH_QUAD, PH_N };
-    double ph[PH_N] = {0, 0, 0, 0, 0};
-    auto t_mark = clk::now();
-    auto mark = [&](int p) -> int {
-        if (!trace_on) return LIG_OK;
-        TRY(wait());
-        ph[p] += ms_since(t_mark);
-        t_mark = clk::now();
-        return LIG_OK;
-    };
-    std::vector<uint32_t> local_of, grow32, ord32, heavy_global;      // (sources / targets of queued copies: they live until the call returns)
+    const uint32_t W = v.world;
+    // (sources and targets of queued copies: declared before the frame, whose scratch drains the stream when it goes)
+    std::vector<uint32_t> local_of, grow32, ord32, heavy_global;
     std::vector<uint8_t> gathered;
     uint64_t header[2] = {0, 0}, qheader[2] = {0, 0};
+    enum { PH_PARTIAL, PH_EXCHANGE, PH_REDUCE, PH_RECORDS, PH_QUAD };
+    DiagShardFrame f(c, v, who, att ? "shard_diagnose_attached" : "shard_diagnose", {"partial", "exchange", "reduce", "records", "quadratic"});
+    hipStream_t s = f.s;
+    const uint32_t l = f.l, k = f.k;
+    const uint64_t l_recip = f.l_recip;
 
-    auto body = [&]() -> int {
+    return f.run([&]() -> int {
         // ---------------------------------------------------------------- linear constraints
         if (sys ? sys->n_constraints : att ? att->n_constraints : 0) {
             DiagSystem d;
             const uint32_t NC = (uint32_t)(sys ? sys->n_constraints : att->n_constraints);      // constraints of the WHOLE trace
             uint32_t *d_local = nullptr, *d_bound = nullptr;
             if (sys) {
-                TRY(diag_upload_system(c, sc, sys, d));
-                local_of.assign(v.rows_global, lig::LIN_NOT_LOCAL);
-                for (size_t lr = 0; lr < v.grow->size(); lr++) local_of[(*v.grow)[lr]] = (uint32_t)lr;
-                TRY(sc.alloc((void**)&d_local, local_of.size() * 4));
-                if (!local_of.empty()) HIP_TRY(c, hipMemcpyAsync(d_local, local_of.data(), local_of.size() * 4, hipMemcpyHostToDevice, s));
+                TRY(diag_upload_system(f, sys, d));
+                TRY(diag_row_table(f, v, local_of, d_local));
             } else {
                 if (att->rows_local != v.grow->size()) FAIL(c, LIG_E_STATE, std::string(who) + ": the attached share was made for another deal");
-                TRY(diag_regroup_system(c, sc, wait, &scan_tmp, &scan_cap, *att, true, d));
+                TRY(diag_regroup_system(f, *att, true, d));
             }
             const uint64_t SL = std::max<uint64_t>(v.slice, 1);
             const uint32_t B = (uint32_t)(NC <= SL ? ((uint64_t)NC + W - 1) / W : std::max<uint64_t>(SL / W, 1));      // constraints per sub-block
@@ -1212,90 +1241,72 @@ int shard_diagnose(const char* who, lig_ctx* c, const lig_diag_shard& v, const l
             const uint64_t rec_cap = std::min<uint64_t>(lin_cap, n_slices * B);                                          // no owner has more to report
             const size_t blk = 16 + (size_t)rec_cap * sizeof(lig_diag_linear);
             fr *d_send = nullptr, *d_recv = nullptr, *d_res = nullptr; uint32_t *d_flag = nullptr, *d_pos = nullptr; uint8_t *d_gsend = nullptr, *d_grecv = nullptr;
-            TRY(sc.alloc((void**)&d_send, (size_t)SE * 32));
-            TRY(sc.alloc((void**)&d_recv, (size_t)SE * 32));
-            TRY(sc.alloc((void**)&d_res, (size_t)B * 32));
-            TRY(sc.alloc((void**)&d_flag, ((size_t)B + 1) * 4));
-            TRY(sc.alloc((void**)&d_pos, ((size_t)B + 1) * 4));
-            TRY(sc.alloc((void**)&d_gsend, blk));
-            TRY(sc.alloc((void**)&d_grecv, (size_t)W * blk));
-            HIP_TRY(c, hipMemsetAsync(d_flag, 0, ((size_t)B + 1) * 4, s));
+            TRY(f.alloc(d_send, SE));
+            TRY(f.alloc(d_recv, SE));
+            TRY(f.alloc(d_res, B));
+            TRY(f.alloc(d_flag, (size_t)B + 1));
+            TRY(f.alloc(d_pos, (size_t)B + 1));
+            TRY(f.alloc(d_gsend, blk));
+            TRY(f.alloc(d_grecv, (size_t)W * blk));
+            TRY(f.zero(d_flag, (size_t)B + 1));
             lig_diag_linear* d_rec = reinterpret_cast<lig_diag_linear*>(d_gsend + 16);
             uint64_t bad_mine = 0, rep_mine = 0;
             // the heavy constraints by their numbers of the whole trace, ascending: the uploaded list's own, or need[] of the compact ones
             const std::vector<uint32_t>* heavy_c = &d.heavy;
             if (att) {
-                TRY(sc.alloc((void**)&d_bound, ((size_t)n_slices + 1) * 4));
-                hipLaunchKernelGGL(lig::k_diag_att_bounds, dim3(diag_grid(n_slices + 1)), dim3(lig::LIN_WG), 0, s, att->need, d.NC, SE, (uint32_t)n_slices, (uint64_t)NC, d_bound);
-                HIP_TRY(c, hipGetLastError());
+                TRY(f.alloc(d_bound, (size_t)n_slices + 1));
+                TRY(f.launch(lig::k_diag_att_bounds, n_slices + 1, att->need, d.NC, SE, (uint32_t)n_slices, (uint64_t)NC, d_bound));
                 if (!d.heavy.empty()) {
                     const uint32_t NH = (uint32_t)d.heavy.size();
                     uint32_t* d_hg = nullptr;
-                    TRY(sc.alloc((void**)&d_hg, (size_t)NH * 4));
+                    TRY(f.alloc(d_hg, NH));
                     heavy_global.resize(NH);
-                    hipLaunchKernelGGL(lig::k_diag_att_heavy_global, dim3(diag_grid(NH)), dim3(lig::LIN_WG), 0, s, d.heavy_dev, NH, att->need, d_hg);
-                    HIP_TRY(c, hipGetLastError());
-                    HIP_TRY(c, hipMemcpyAsync(heavy_global.data(), d_hg, (size_t)NH * 4, hipMemcpyDeviceToHost, s));
-                    TRY(wait());
+                    TRY(f.launch(lig::k_diag_att_heavy_global, NH, d.heavy_dev, NH, att->need, d_hg));
+                    TRY(f.fetch(heavy_global.data(), d_hg, NH));
                     if (!std::is_sorted(heavy_global.begin(), heavy_global.end())) FAIL(c, LIG_E_STATE, std::string(who) + ": the attached share's need list is not ascending");
                 }
                 heavy_c = &heavy_global;
             }
-            TRY(mark(PH_RECORDS));      // (uploads, table conversion; regrouping)
+            TRY(f.mark(PH_RECORDS));      // (uploads, table conversion; regrouping)
             for (uint64_t j = 0; j < n_slices; j++) {
                 const uint32_t c0 = (uint32_t)(j * SE), n = (uint32_t)std::min<uint64_t>(SE, NC - c0);
                 const size_t h0 = std::lower_bound(heavy_c->begin(), heavy_c->end(), c0) - heavy_c->begin();
-                const size_t h1 = std::lower_bound(heavy_c->begin(), heavy_c->end(), c0 + n) - heavy_c->begin();
+                const uint32_t nh = (uint32_t)(std::lower_bound(heavy_c->begin(), heavy_c->end(), c0 + n) - heavy_c->begin() - h0);
                 if (sys) {
-                    if (n < SE) HIP_TRY(c, hipMemsetAsync(d_send + n, 0, (size_t)(SE - n) * 32, s));       // beyond the end of the system: zero partials
-                    hipLaunchKernelGGL(lig::k_diag_lin_part, dim3(diag_grid(n)), dim3(lig::LIN_WG), 0, s, d.tb, d.terms, c0, n, v.msgs, l, k, l_recip, d.coef, d_local, d_send);
-                    HIP_TRY(c, hipGetLastError());
-                    if (h1 > h0) {
-                        hipLaunchKernelGGL(lig::k_diag_lin_part_heavy, dim3(std::min<uint32_t>((uint32_t)(h1 - h0), lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d.heavy_dev + h0,
-                                           (uint32_t)(h1 - h0), d.tb, d.terms, c0, v.msgs, l, k, l_recip, d.coef, d_local, d_send);
-                        HIP_TRY(c, hipGetLastError());
-                    }
+                    if (n < SE) TRY(f.zero(d_send + n, SE - n));       // beyond the end of the system: zero partials
+                    TRY(f.launch(lig::k_diag_lin_part, n, d.tb, d.terms, c0, n, v.msgs, l, k, l_recip, d.coef, d_local, d_send));
+                    if (nh) TRY(f.launch_blocks(lig::k_diag_lin_part_heavy, nh, d.heavy_dev + h0, nh, d.tb, d.terms, c0, v.msgs, l, k, l_recip, d.coef, d_local, d_send));
                 } else {
-                    HIP_TRY(c, hipMemsetAsync(d_send, 0, (size_t)SE * 32, s));      // the constraints this rank does not need, and those beyond the end
-                    hipLaunchKernelGGL(lig::k_diag_att_part, dim3(diag_grid(std::min<uint64_t>(n, d.NC))), dim3(lig::LIN_WG), 0, s, d_bound + j, d.tb, d.terms, att->need, c0, n,
-                                       v.msgs, l, k, l_recip, d.coef, d.rhs_index, d.rhs_coef, d_send);
-                    HIP_TRY(c, hipGetLastError());
-                    if (h1 > h0) {
-                        hipLaunchKernelGGL(lig::k_diag_att_part_heavy, dim3(std::min<uint32_t>((uint32_t)(h1 - h0), lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s,
-                                           d.heavy_dev + h0, (uint32_t)(h1 - h0), d.tb, d.terms, att->need, c0, n, v.msgs, l, k, l_recip, d.coef, d.rhs_index, d.rhs_coef, d_send);
-                        HIP_TRY(c, hipGetLastError());
-                    }
+                    TRY(f.zero(d_send, SE));      // the constraints this rank does not need, and those beyond the end
+                    TRY(f.launch(lig::k_diag_att_part, std::min<uint64_t>(n, d.NC), d_bound + j, d.tb, d.terms, att->need, c0, n, v.msgs, l, k, l_recip, d.coef, d.rhs_index,
+                                 d.rhs_coef, d_send));
+                    if (nh) TRY(f.launch_blocks(lig::k_diag_att_part_heavy, nh, d.heavy_dev + h0, nh, d.tb, d.terms, att->need, c0, n, v.msgs, l, k, l_recip, d.coef, d.rhs_index,
+                                                d.rhs_coef, d_send));
                 }
-                TRY(mark(PH_PARTIAL));
-                used_comm = true;
-                TRY(v.all_to_all(d_send, d_recv, (size_t)B * 32, "all_to_all(partial constraint sums)"));
-                TRY(mark(PH_EXCHANGE));
+                TRY(f.mark(PH_PARTIAL));
+                TRY(f.all_to_all(d_send, d_recv, (size_t)B * 32, "all_to_all(partial constraint sums)"));
+                TRY(f.mark(PH_EXCHANGE));
                 const uint64_t first = (uint64_t)c0 + (uint64_t)v.rank * B;                             // my sub-block of this slice
-                const uint32_t n_valid = first < NC ? (uint32_t)std::min<uint64_t>(B, NC - first) : 0u;
-                if (sys) hipLaunchKernelGGL(lig::k_diag_reduce<true>, dim3(diag_grid(B)), dim3(lig::LIN_WG), 0, s, d_recv, W, B, n_valid, (uint32_t)std::min<uint64_t>(first, NC),
-                                            d.rhs_index, d.rhs_coef, d.coef, d_res, d_flag);
-                else hipLaunchKernelGGL(lig::k_diag_reduce<false>, dim3(diag_grid(B)), dim3(lig::LIN_WG), 0, s, d_recv, W, B, n_valid, (uint32_t)std::min<uint64_t>(first, NC),
-                                        (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const fr*)nullptr, d_res, d_flag);
-                HIP_TRY(c, hipGetLastError());
-                TRY(mark(PH_REDUCE));
+                const uint32_t n_valid = first < NC ? (uint32_t)std::min<uint64_t>(B, NC - first) : 0u, first_c = (uint32_t)std::min<uint64_t>(first, NC);
+                if (sys) TRY(f.launch(lig::k_diag_reduce<true>, B, d_recv, W, B, n_valid, first_c, d.rhs_index, d.rhs_coef, d.coef, d_res, d_flag));
+                else TRY(f.launch(lig::k_diag_reduce<false>, B, d_recv, W, B, n_valid, first_c, nullptr, nullptr, nullptr, d_res, d_flag));
+                TRY(f.mark(PH_REDUCE));
                 uint32_t bad = 0;
-                TRY(diag_scan(c, sc, wait, d_flag, d_pos, B, &scan_tmp, &scan_cap, &bad));
+                TRY(f.scan(d_flag, d_pos, B, &bad));
                 if (bad > n_valid) FAIL(c, LIG_E_STATE, "lig_shard_rows_diagnose: counted more violated constraints than the sub-block holds");
                 bad_mine += bad;
                 const uint32_t rep = (uint32_t)std::min<uint64_t>(bad, rec_cap - rep_mine);
                 if (rep) {
-                    hipLaunchKernelGGL(lig::k_diag_scatter_lin, dim3(diag_grid(B)), dim3(lig::LIN_WG), 0, s, d_flag, d_pos, d_res, B, (uint32_t)first, rep, d_rec + rep_mine);
-                    HIP_TRY(c, hipGetLastError());
+                    TRY(f.launch(lig::k_diag_scatter_lin, B, d_flag, d_pos, d_res, B, (uint32_t)first, rep, d_rec + rep_mine));
                     rep_mine += rep;
                 }
-                TRY(mark(PH_RECORDS));
+                TRY(f.mark(PH_RECORDS));
             }
             header[0] = bad_mine; header[1] = rep_mine;
             HIP_TRY(c, hipMemcpyAsync(d_gsend, header, 16, hipMemcpyHostToDevice, s));
-            TRY(v.all_gather(d_gsend, d_grecv, blk, "all_gather(violated constraints)"));
+            TRY(f.all_gather(d_gsend, d_grecv, blk, "all_gather(violated constraints)"));
             gathered.resize((size_t)W * blk);
-            HIP_TRY(c, hipMemcpyAsync(gathered.data(), d_grecv, gathered.size(), hipMemcpyDeviceToHost, s));
-            TRY(wait());
+            TRY(f.fetch(gathered.data(), d_grecv, gathered.size()));
             // every rank: W ascending lists -> ascending constraint order, cut at lin_cap
             std::vector<lig_diag_linear> all;
             uint64_t bad_total = 0;
@@ -1313,7 +1324,7 @@ int shard_diagnose(const char* who, lig_ctx* c, const lig_diag_shard& v, const l
             if (rep) std::memcpy(lin_out, all.data(), rep * sizeof(lig_diag_linear));
             info->n_linear_bad = bad_total;
             info->n_linear_reported = rep;
-            TRY(mark(PH_RECORDS));
+            TRY(f.mark(PH_RECORDS));
         }
 
         // ---------------------------------------------------------------- quadratic terms: every term is local to one rank
@@ -1322,27 +1333,23 @@ int shard_diagnose(const char* who, lig_ctx* c, const lig_diag_shard& v, const l
             const uint64_t rec_cap = std::min<uint64_t>(quad_cap, v.n_terms_global * l);
             const size_t blk = 16 + (size_t)rec_cap * (sizeof(lig_diag_quad) + 4);                     // [count, kept | records | ordinals]
             uint8_t *d_gsend = nullptr, *d_grecv = nullptr; uint32_t *d_grow = nullptr, *d_ord = nullptr;
-            TRY(sc.alloc((void**)&d_gsend, blk));
-            TRY(sc.alloc((void**)&d_grecv, (size_t)W * blk));
+            TRY(f.alloc(d_gsend, blk));
+            TRY(f.alloc(d_grecv, (size_t)W * blk));
             lig_diag_quad* d_rec = reinterpret_cast<lig_diag_quad*>(d_gsend + 16);
             uint32_t* d_rec_ord = reinterpret_cast<uint32_t*>(d_gsend + 16 + (size_t)rec_cap * sizeof(lig_diag_quad));
             uint64_t bad_mine = 0, rep_mine = 0;
             if (NTl) {
                 grow32.assign(v.grow->begin(), v.grow->end());
                 ord32.assign(v.triple_ord->begin(), v.triple_ord->end());
-                TRY(sc.alloc((void**)&d_grow, grow32.size() * 4));
-                TRY(sc.alloc((void**)&d_ord, ord32.size() * 4));
-                HIP_TRY(c, hipMemcpyAsync(d_grow, grow32.data(), grow32.size() * 4, hipMemcpyHostToDevice, s));
-                HIP_TRY(c, hipMemcpyAsync(d_ord, ord32.data(), ord32.size() * 4, hipMemcpyHostToDevice, s));
-                TRY(diag_quad_pass(c, sc, wait, &scan_tmp, &scan_cap, v.msgs, v.tri_dev, NTl, rec_cap, nullptr, d_rec, d_grow, d_ord, d_rec_ord, &bad_mine, &rep_mine));
+                TRY(f.upload(d_grow, grow32.data(), grow32.size()));
+                TRY(f.upload(d_ord, ord32.data(), ord32.size()));
+                TRY(diag_quad_pass(f, v.msgs, v.tri_dev, NTl, rec_cap, nullptr, d_rec, d_grow, d_ord, d_rec_ord, &bad_mine, &rep_mine));
             }
             qheader[0] = bad_mine; qheader[1] = rep_mine;
             HIP_TRY(c, hipMemcpyAsync(d_gsend, qheader, 16, hipMemcpyHostToDevice, s));
-            used_comm = true;
-            TRY(v.all_gather(d_gsend, d_grecv, blk, "all_gather(violated quadratic terms)"));
+            TRY(f.all_gather(d_gsend, d_grecv, blk, "all_gather(violated quadratic terms)"));
             gathered.resize((size_t)W * blk);
-            HIP_TRY(c, hipMemcpyAsync(gathered.data(), d_grecv, gathered.size(), hipMemcpyDeviceToHost, s));
-            TRY(wait());
+            TRY(f.fetch(gathered.data(), d_grecv, gathered.size()));
             struct Item { uint32_t ord; lig_diag_quad rec; };
             std::vector<Item> all;
             uint64_t bad_total = 0;
@@ -1364,18 +1371,10 @@ int shard_diagnose(const char* who, lig_ctx* c, const lig_diag_shard& v, const l
             for (uint64_t i = 0; i < rep; i++) quad_out[i] = all[i].rec;
             info->n_quad_bad = bad_total;
             info->n_quad_reported = rep;
-            TRY(mark(PH_QUAD));
+            TRY(f.mark(PH_QUAD));
         }
         return LIG_OK;
-    };
-    const int rc = body();
-    if (rc != LIG_OK && v.settle_failed()) { sc.abandon(); return rc; }      // poisoned: the scratch outlives the call
-    if (rc == LIG_OK) (void)wait();
-    if (used_comm) v.forget();                                                // before any send buffer is freed (lig_comm.forget)
-    if (trace_on && rc == LIG_OK)
-        std::fprintf(stderr, "[lig_trace] shard_diagnose%s rank %u: partial %.3f exchange %.3f reduce %.3f records %.3f quadratic %.3f ms\n", att ? "_attached" : "", v.rank,
-                     ph[PH_PARTIAL], ph[PH_EXCHANGE], ph[PH_REDUCE], ph[PH_RECORDS], ph[PH_QUAD]);
-    return rc;
+    });
 }
 }  // namespace
 int lig_internal_shard_diagnose(lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, lig_diag_linear* lin_out, uint64_t lin_cap, lig_diag_quad* quad_out,
@@ -1398,31 +1397,23 @@ struct ExplainExchange {
     uint32_t* d_local = nullptr; fr *d_send = nullptr, *d_recv = nullptr;
     uint64_t P = 0;
 };
-enum { XPH_PART, XPH_EXCHANGE, XPH_SUM, XPH_RECORDS, XPH_N };
-int explain_exchange_alloc(lig_ctx* c, DiagScratch& sc, const lig_diag_shard& v, std::vector<uint32_t>& local_of, uint64_t n_items, ExplainExchange& x) {
-    x.P = lig::explain_piece_size(n_items, v.slice);
-    local_of.assign(v.rows_global, lig::LIN_NOT_LOCAL);
-    for (size_t lr = 0; lr < v.grow->size(); lr++) local_of[(*v.grow)[lr]] = (uint32_t)lr;
-    TRY(sc.alloc((void**)&x.d_local, local_of.size() * 4));
-    TRY(sc.alloc((void**)&x.d_send, (size_t)x.P * 32));
-    TRY(sc.alloc((void**)&x.d_recv, (size_t)v.world * x.P * 32));
-    if (!local_of.empty()) HIP_TRY(c, hipMemcpyAsync(x.d_local, local_of.data(), local_of.size() * 4, hipMemcpyHostToDevice, c->stream));
-    return LIG_OK;
+enum { XPH_PART, XPH_EXCHANGE, XPH_SUM, XPH_RECORDS };
+const std::initializer_list<const char*> XPH_NAMES = {"part", "exchange", "sum", "records"};
+int explain_exchange_alloc(DiagShardFrame& f, std::vector<uint32_t>& local_of, uint64_t n_items, ExplainExchange& x) {
+    x.P = lig::explain_piece_size(n_items, f.v.slice);
+    TRY(diag_row_table(f, f.v, local_of, x.d_local));
+    TRY(f.alloc(x.d_send, x.P));
+    return f.alloc(x.d_recv, (size_t)f.v.world * x.P);
 }
 // piece j of the n_items entries: d_slot points at the first slot of the piece, the sums go to d_out[0 .. n)
-int explain_exchange_piece(lig_ctx* c, const lig_diag_shard& v, const ExplainExchange& x, const uint32_t* d_slot, uint32_t stride, uint32_t n, fr* d_out,
-                           const std::function<int(int)>& mark, const char* what) {
-    hipStream_t s = c->stream;
-    if (n < x.P) HIP_TRY(c, hipMemsetAsync(x.d_send + n, 0, (size_t)(x.P - n) * 32, s));
-    hipLaunchKernelGGL(lig::k_explain_part, dim3(diag_grid(n)), dim3(lig::LIN_WG), 0, s, d_slot, stride, n, v.msgs, c->l, c->k, diag_reciprocal(c->l), x.d_local, x.d_send);
-    HIP_TRY(c, hipGetLastError());
-    TRY(mark(XPH_PART));
-    TRY(v.all_gather(x.d_send, x.d_recv, (size_t)x.P * 32, what));
-    TRY(mark(XPH_EXCHANGE));
-    hipLaunchKernelGGL(lig::k_explain_sum, dim3(diag_grid(n)), dim3(lig::LIN_WG), 0, s, x.d_recv, v.world, (uint32_t)x.P, n, d_out);
-    HIP_TRY(c, hipGetLastError());
-    TRY(mark(XPH_SUM));
-    return LIG_OK;
+int explain_exchange_piece(DiagShardFrame& f, const ExplainExchange& x, const uint32_t* d_slot, uint32_t stride, uint32_t n, fr* d_out, const char* what) {
+    if (n < x.P) TRY(f.zero(x.d_send + n, x.P - n));
+    TRY(f.launch(lig::k_explain_part, n, d_slot, stride, n, f.v.msgs, f.l, f.k, f.l_recip, x.d_local, x.d_send));
+    TRY(f.mark(XPH_PART));
+    TRY(f.all_gather(x.d_send, x.d_recv, (size_t)x.P * 32, what));
+    TRY(f.mark(XPH_EXCHANGE));
+    TRY(f.launch(lig::k_explain_sum, n, x.d_recv, f.v.world, (uint32_t)x.P, n, d_out));
+    return f.mark(XPH_SUM);
 }
 }  // namespace
 
@@ -1435,90 +1426,41 @@ int explain_exchange_piece(lig_ctx* c, const lig_diag_shard& v, const ExplainExc
 // the records: 88 n_asked + 84 min(m, term_cap).  Every send buffer is an allocation of its own; v.forget runs before any of them is freed.
 int lig_internal_shard_explain(lig_ctx* c, const lig_diag_shard& v, const lig_linear_system* sys, const uint32_t* asked, uint64_t n_asked,
                                lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info) {
-    hipStream_t s = c->stream;
     const uint32_t NA = (uint32_t)n_asked;
-    // (sources of queued uploads: declared before the scratch, whose destructor drains the stream)
+    // (sources of queued uploads: declared before the frame, whose scratch drains the stream when it goes)
     std::vector<lig::ExplainItem> items;
     std::vector<uint64_t> first;
-    std::vector<uint32_t> first32, ask, rhs_index, rhs_coef, local_of;
-    std::vector<lig_lin_term> ordered;
-    DiagScratch sc(c);
-    bool used_comm = false;
-    const DiagWait wait = [&v]() -> int { return v.drain("lig_shard_rows_explain"); };
-    const bool trace_on = lig::knobs().trace;
-    double ph[XPH_N] = {0, 0, 0, 0};
-    auto t_mark = clk::now();
-    const std::function<int(int)> mark = [&](int p) -> int {
-        if (!trace_on) return LIG_OK;
-        TRY(wait());
-        ph[p] += ms_since(t_mark);
-        t_mark = clk::now();
-        return LIG_OK;
-    };
+    std::vector<uint32_t> rhs_index, rhs_coef, local_of;
+    ExplainOrdered o;
+    DiagShardFrame f(c, v, "lig_shard_rows_explain", "shard_explain", XPH_NAMES);
     uint32_t m = 0, rep = 0;
 
-    auto body = [&]() -> int {
+    TRY(f.run([&]() -> int {
         m = (uint32_t)lig::explain_items_of(*sys, asked, n_asked, items);       // <= n_terms < 2^32: the asked are distinct
         if (!lig::explain_order(items, NA, first)) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain: a term names no asked constraint");
         rep = (uint32_t)std::min<uint64_t>(m, term_cap);
-        ordered.resize(m);
-        ask.resize(rep);
-        first32.assign(first.begin(), first.end());
-        for (uint32_t i = 0; i < m; i++) { ordered[i].slot = items[i].slot; ordered[i].coef = items[i].coef; }
-        for (uint32_t i = 0; i < rep; i++) ask[i] = items[i].ask;
         // b_c of asked constraint a: rhs_coef[rhs_index[a] - 1], rhs_index[a] = a + 1 when it has one, else 0 (rhs_constraint is ascending)
         lig::explain_rhs_of(*sys, asked, n_asked, rhs_index, rhs_coef);
-        lig_lin_term* d_ordered = nullptr; uint32_t *d_asked = nullptr, *d_ask = nullptr, *d_first = nullptr, *d_rhs_index = nullptr, *d_rhs_coef = nullptr;
-        fr *d_coef = nullptr, *d_vals = nullptr; lig_explain_constraint* d_con = nullptr; lig_explain_term* d_out = nullptr;
+        uint32_t *d_asked = nullptr, *d_rhs_index = nullptr, *d_rhs_coef = nullptr; fr *d_coef = nullptr, *d_vals = nullptr;
         ExplainExchange x;
-        TRY(sc.alloc((void**)&d_ordered, (size_t)m * sizeof(lig_lin_term)));
-        TRY(sc.alloc((void**)&d_asked, (size_t)NA * 4));
-        TRY(sc.alloc((void**)&d_ask, (size_t)rep * 4));
-        TRY(sc.alloc((void**)&d_first, ((size_t)NA + 1) * 4));
-        TRY(sc.alloc((void**)&d_rhs_index, (size_t)NA * 4));
-        TRY(sc.alloc((void**)&d_rhs_coef, (size_t)NA * 4));
-        TRY(sc.alloc((void**)&d_coef, (size_t)sys->n_coefs * 32));
-        TRY(sc.alloc((void**)&d_vals, (size_t)m * 32));
-        TRY(sc.alloc((void**)&d_con, (size_t)NA * sizeof(lig_explain_constraint)));
-        TRY(sc.alloc((void**)&d_out, (size_t)rep * sizeof(lig_explain_term)));
-        if (m) TRY(explain_exchange_alloc(c, sc, v, local_of, m, x));
-        if (m) HIP_TRY(c, hipMemcpyAsync(d_ordered, ordered.data(), (size_t)m * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_asked, asked, (size_t)NA * 4, hipMemcpyHostToDevice, s));
-        if (rep) HIP_TRY(c, hipMemcpyAsync(d_ask, ask.data(), (size_t)rep * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_first, first32.data(), ((size_t)NA + 1) * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_rhs_index, rhs_index.data(), (size_t)NA * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_rhs_coef, rhs_coef.data(), (size_t)NA * 4, hipMemcpyHostToDevice, s));
-        if (sys->n_coefs) HIP_TRY(c, hipMemcpyAsync(d_coef, sys->coefs, (size_t)sys->n_coefs * 32, hipMemcpyHostToDevice, s));
-        lig::launch_lin_coefs_mont(s, d_coef, sys->n_coefs);
-        HIP_TRY(c, hipGetLastError());
-        TRY(mark(XPH_RECORDS));      // (uploads, table conversion)
+        if (m) TRY(explain_exchange_alloc(f, local_of, m, x));
+        TRY(explain_upload(f, items, first, NA, rep, o));
+        TRY(f.upload(d_asked, asked, NA));
+        TRY(f.upload(d_rhs_index, rhs_index.data(), NA));
+        TRY(f.upload(d_rhs_coef, rhs_coef.data(), NA));
+        TRY(diag_upload_table(f, sys, d_coef));
+        TRY(f.alloc(d_vals, m));
+        TRY(f.mark(XPH_RECORDS));      // (uploads, table conversion)
         const uint64_t n_pieces = lig::explain_piece_count(m, x.P);
         for (uint64_t j = 0; j < n_pieces; j++) {
             const uint32_t n = (uint32_t)lig::explain_piece_len(m, x.P, j);
-            used_comm = true;
-            TRY(explain_exchange_piece(c, v, x, &d_ordered[j * x.P].slot, 2, n, d_vals + j * x.P, mark, "all_gather(witness values of the asked terms)"));
+            TRY(explain_exchange_piece(f, x, &o.d_ordered[j * x.P].slot, 2, n, d_vals + j * x.P, "all_gather(witness values of the asked terms)"));
         }
-        const lig::ExplainFromValues wit{d_vals};
-        if (rep) hipLaunchKernelGGL(lig::k_explain_fill<lig::ExplainFromValues>, dim3(diag_grid(rep)), dim3(lig::LIN_WG), 0, s, d_ordered, d_ask, rep, d_asked, wit, d_coef, d_out);
-        hipLaunchKernelGGL(lig::k_explain_finish<lig::ExplainFromValues>, dim3(std::min<uint32_t>(NA, lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d_first, d_ordered, d_asked, NA,
-                           wit, d_coef, d_rhs_index, d_rhs_coef, d_con);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(con_out, d_con, (size_t)NA * sizeof(lig_explain_constraint), hipMemcpyDeviceToHost, s));
-        if (rep) HIP_TRY(c, hipMemcpyAsync(terms_out, d_out, (size_t)rep * sizeof(lig_explain_term), hipMemcpyDeviceToHost, s));
-        TRY(wait());
-        TRY(mark(XPH_RECORDS));
-        return LIG_OK;
-    };
-    const int rc = body();
-    if (rc != LIG_OK && v.settle_failed()) { sc.abandon(); return rc; }      // poisoned: the scratch outlives the call
-    if (rc == LIG_OK) (void)wait();
-    if (used_comm) v.forget();                                                // before any send buffer is freed (lig_comm.forget)
-    if (rc != LIG_OK) return rc;
+        TRY(explain_records(f, o, d_asked, lig::ExplainFromValues{d_vals}, d_coef, d_rhs_index, d_rhs_coef, con_out, terms_out));
+        return f.mark(XPH_RECORDS);
+    }));
     info->n_terms_total = m;
     info->n_terms_reported = rep;
-    if (trace_on)
-        std::fprintf(stderr, "[lig_trace] shard_explain rank %u: part %.3f exchange %.3f sum %.3f records %.3f ms\n", v.rank, ph[XPH_PART], ph[XPH_EXCHANGE], ph[XPH_SUM],
-                     ph[XPH_RECORDS]);
     return LIG_OK;
 }
 
@@ -1535,8 +1477,6 @@ int lig_internal_shard_explain(lig_ctx* c, const lig_diag_shard& v, const lig_li
 // allocation of its own; v.forget runs before any of them is freed.
 int lig_internal_shard_explain_attached(lig_ctx* c, const lig_diag_shard& v, const lig_linear* att, bool alone, const uint32_t* asked, uint64_t n_asked,
                                         lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info) {
-    static const char* const who = "lig_shard_rows_explain_attached";
-    hipStream_t s = c->stream;
     const lig_linear_view a = lig_internal_linear_view(att);
     const uint32_t NA = (uint32_t)n_asked, W = v.world, l = c->l, k = c->k, NT = (uint32_t)a.n_terms, NR = (uint32_t)a.n_rhs;
     const uint64_t rows_local = v.grow->size();
@@ -1546,153 +1486,90 @@ int lig_internal_shard_explain_attached(lig_ctx* c, const lig_diag_shard& v, con
         FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: the attached structure is not this rank's share of the sharded trace");
     for (size_t lr = 0; lr < rows_local; lr++)
         if ((*v.grow)[lr] >= v.rows_global) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: a local row lies outside the trace");
-    // (sources and targets of queued copies: declared before the scratch, whose destructor drains the stream)
-    std::vector<uint32_t> grow32(v.grow->begin(), v.grow->end()), hdr_all, heads, m32, off32, rhs_index, rhs_coef, holder, perm, first32, ask;
+    // (sources and targets of queued copies: declared before the frame, whose scratch drains the stream when it goes)
+    std::vector<uint32_t> grow32(v.grow->begin(), v.grow->end()), hdr_all, heads, m32, off32, rhs_index, rhs_coef, holder, perm;
     std::vector<uint64_t> m_of, first;
     std::vector<lig::ExplainItem> items;
-    std::vector<lig_lin_term> ordered;
-    DiagScratch sc(c);
-    void* scan_tmp = nullptr; size_t scan_cap = 0;
-    bool used_comm = false;
-    const DiagWait wait = [&v]() -> int { return v.drain(who); };
-    const auto gather = [&](const void* src, void* dst, size_t bytes, const char* what) -> int {
-        if (alone) { HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s)); return LIG_OK; }
-        used_comm = true;
-        return v.all_gather(src, dst, bytes, what);
-    };
-    const bool trace_on = lig::knobs().trace;
-    enum { APH_SELECT, APH_EXCHANGE, APH_MERGE, APH_RECORDS, APH_N };
-    double ph[APH_N] = {0, 0, 0, 0};
-    auto t_mark = clk::now();
-    const auto mark = [&](int p) -> int {
-        if (!trace_on) return LIG_OK;
-        TRY(wait());
-        ph[p] += ms_since(t_mark);
-        t_mark = clk::now();
-        return LIG_OK;
-    };
+    ExplainOrdered o;
+    enum { APH_SELECT, APH_EXCHANGE, APH_MERGE, APH_RECORDS };
+    DiagShardFrame f(c, v, "lig_shard_rows_explain_attached", "shard_explain_attached", {"select", "exchange", "merge", "records"}, alone);
+    hipStream_t s = f.s;
     uint32_t total = 0, rep = 0;
 
-    auto body = [&]() -> int {
+    TRY(f.run([&]() -> int {
         // 1. select: mark, scan, the right-hand sides this rank holds, the header block
         const size_t hw = (size_t)lig::explain_header_words(NA);
         uint32_t *d_asked = nullptr, *d_mark = nullptr, *d_pos = nullptr, *d_grow = nullptr, *d_hdr = nullptr, *d_hdr_all = nullptr;
-        TRY(sc.alloc((void**)&d_asked, (size_t)NA * 4));
-        TRY(sc.alloc((void**)&d_mark, ((size_t)NT + 1) * 4));
-        TRY(sc.alloc((void**)&d_pos, ((size_t)NT + 1) * 4));
-        TRY(sc.alloc((void**)&d_grow, (size_t)rows_local * 4));
-        TRY(sc.alloc((void**)&d_hdr, hw * 4));
-        TRY(sc.alloc((void**)&d_hdr_all, (size_t)W * hw * 4));
-        HIP_TRY(c, hipMemcpyAsync(d_asked, asked, (size_t)NA * 4, hipMemcpyHostToDevice, s));
-        if (rows_local) HIP_TRY(c, hipMemcpyAsync(d_grow, grow32.data(), (size_t)rows_local * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemsetAsync(d_mark + NT, 0, 4, s));
-        HIP_TRY(c, hipMemsetAsync(d_hdr, 0, hw * 4, s));
-        if (NT) hipLaunchKernelGGL(lig::k_explain_mark, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, a.ent, NT, a.need, d_asked, NA, d_mark);
-        if (NR) hipLaunchKernelGGL(lig::k_explain_rhs_held, dim3(diag_grid(NR)), dim3(lig::LIN_WG), 0, s, a.rhs_c, a.rhs_coef, NR, a.need, d_asked, NA,
-                                   reinterpret_cast<uint2*>(d_hdr + lig::explain_header_held(0)));
-        HIP_TRY(c, hipGetLastError());
+        TRY(f.upload(d_asked, asked, NA));
+        TRY(f.upload(d_grow, grow32.data(), rows_local));
+        TRY(f.alloc(d_mark, (size_t)NT + 1));
+        TRY(f.alloc(d_pos, (size_t)NT + 1));
+        TRY(f.alloc(d_hdr, hw));
+        TRY(f.alloc(d_hdr_all, (size_t)W * hw));
+        TRY(f.zero(d_mark + NT, 1));
+        TRY(f.zero(d_hdr, hw));
+        if (NT) TRY(f.launch(lig::k_explain_mark, NT, a.ent, NT, a.need, d_asked, NA, d_mark));
+        if (NR) TRY(f.launch(lig::k_explain_rhs_held, NR, a.rhs_c, a.rhs_coef, NR, a.need, d_asked, NA, reinterpret_cast<uint2*>(d_hdr + lig::explain_header_held(0))));
         uint32_t m_own = 0;
-        TRY(diag_scan(c, sc, wait, rocprim::make_transform_iterator((const uint32_t*)d_mark, lig::ExplainMarked{}), d_pos, NT, &scan_tmp, &scan_cap, &m_own));
+        TRY(f.scan(rocprim::make_transform_iterator((const uint32_t*)d_mark, lig::ExplainMarked{}), d_pos, NT, &m_own));
         if (m_own > NT) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: counted more asked terms than the rank's share holds");
         HIP_TRY(c, hipMemcpyAsync(d_hdr, d_pos + NT, 4, hipMemcpyDeviceToDevice, s));
         lig::ExplainRecord* d_rec = nullptr;
-        TRY(sc.alloc((void**)&d_rec, (size_t)m_own * sizeof(lig::ExplainRecord)));
-        if (m_own) hipLaunchKernelGGL(lig::k_explain_collect_values, dim3(diag_grid(NT)), dim3(lig::LIN_WG), 0, s, a.ent, NT, a.begin, a.n_slots, d_mark, d_pos, d_grow, v.msgs,
-                                      l, k, diag_reciprocal(l), d_rec);
-        HIP_TRY(c, hipGetLastError());
-        TRY(mark(APH_SELECT));
+        TRY(f.alloc(d_rec, m_own));
+        if (m_own) TRY(f.launch(lig::k_explain_collect_values, NT, a.ent, NT, a.begin, a.n_slots, d_mark, d_pos, d_grow, v.msgs, l, k, f.l_recip, d_rec));
+        TRY(f.mark(APH_SELECT));
         // 2. the headers: every m_r, the holder of every b_c
-        TRY(gather(d_hdr, d_hdr_all, hw * 4, "all_gather(counts and right-hand sides of the asked constraints)"));
+        TRY(f.all_gather(d_hdr, d_hdr_all, hw * 4, "all_gather(counts and right-hand sides of the asked constraints)"));
         hdr_all.resize((size_t)W * hw);
-        HIP_TRY(c, hipMemcpyAsync(hdr_all.data(), d_hdr_all, (size_t)W * hw * 4, hipMemcpyDeviceToHost, s));
-        TRY(wait());
+        TRY(f.fetch(hdr_all.data(), d_hdr_all, (size_t)W * hw));
         if (!lig::explain_header_merge(hdr_all.data(), W, NA, m_of, rhs_index, rhs_coef, holder) || m_of[v.rank] != m_own)
             FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: a rank's header block is malformed");
         const lig::ExplainRecordSchedule x = lig::explain_record_schedule(m_of, v.slice);
         if ((uint64_t)W * x.P >= (1ull << 32)) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: a piece of the record exchange exceeds 2^32 records");
         total = (uint32_t)x.off[W];
         rep = (uint32_t)std::min<uint64_t>(total, term_cap);
-        TRY(mark(APH_EXCHANGE));
+        TRY(f.mark(APH_EXCHANGE));
         // 3. the records, in pieces of P per rank; the values stay on the device, the heads go to the host
         const size_t WP = (size_t)W * x.P;
         lig::ExplainRecord *d_send = nullptr, *d_recv = nullptr; uint4* d_heads = nullptr; fr *d_vals_in = nullptr, *d_vals = nullptr; uint32_t *d_m = nullptr, *d_off = nullptr;
-        TRY(sc.alloc((void**)&d_send, (size_t)x.P * sizeof(lig::ExplainRecord)));
-        TRY(sc.alloc((void**)&d_recv, WP * sizeof(lig::ExplainRecord)));
-        TRY(sc.alloc((void**)&d_heads, (size_t)x.pieces * WP * 16));
-        TRY(sc.alloc((void**)&d_vals_in, (size_t)total * 32));
-        TRY(sc.alloc((void**)&d_vals, (size_t)total * 32));
-        TRY(sc.alloc((void**)&d_m, (size_t)W * 4));
-        TRY(sc.alloc((void**)&d_off, (size_t)W * 4));
+        TRY(f.alloc(d_send, x.P));
+        TRY(f.alloc(d_recv, WP));
+        TRY(f.alloc(d_heads, (size_t)x.pieces * WP));
+        TRY(f.alloc(d_vals_in, total));
+        TRY(f.alloc(d_vals, total));
         m32.assign(m_of.begin(), m_of.end());
         off32.assign(x.off.begin(), x.off.begin() + W);
-        HIP_TRY(c, hipMemcpyAsync(d_m, m32.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_off, off32.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
+        TRY(f.upload(d_m, m32.data(), W));
+        TRY(f.upload(d_off, off32.data(), W));
         for (uint64_t j = 0; j < x.pieces; j++) {
             const uint64_t lo = std::min<uint64_t>(j * x.P, m_own), n = std::min<uint64_t>(x.P, m_own - lo);      // this rank's records of the piece
             if (n) HIP_TRY(c, hipMemcpyAsync(d_send, d_rec + lo, (size_t)n * sizeof(lig::ExplainRecord), hipMemcpyDeviceToDevice, s));
-            if (n < x.P) HIP_TRY(c, hipMemsetAsync(d_send + n, 0, (size_t)(x.P - n) * sizeof(lig::ExplainRecord), s));
-            TRY(mark(APH_SELECT));
-            TRY(gather(d_send, d_recv, (size_t)x.P * sizeof(lig::ExplainRecord), "all_gather(the asked terms of every rank)"));
-            TRY(mark(APH_EXCHANGE));
-            hipLaunchKernelGGL(lig::k_explain_keep, dim3(diag_grid(WP)), dim3(lig::LIN_WG), 0, s, d_recv, W, (uint32_t)x.P, j, d_m, d_off, d_heads + j * WP, d_vals_in);
-            HIP_TRY(c, hipGetLastError());
-            TRY(mark(APH_MERGE));
+            if (n < x.P) TRY(f.zero(d_send + n, x.P - n));
+            TRY(f.mark(APH_SELECT));
+            TRY(f.all_gather(d_send, d_recv, (size_t)x.P * sizeof(lig::ExplainRecord), "all_gather(the asked terms of every rank)"));
+            TRY(f.mark(APH_EXCHANGE));
+            TRY(f.launch(lig::k_explain_keep, WP, d_recv, W, (uint32_t)x.P, j, d_m, d_off, d_heads + j * WP, d_vals_in));
+            TRY(f.mark(APH_MERGE));
         }
         // 4. merge and order on the host, permute the values, the records
         heads.resize((size_t)x.pieces * WP * 4);
-        if (!heads.empty()) HIP_TRY(c, hipMemcpyAsync(heads.data(), d_heads, heads.size() * 4, hipMemcpyDeviceToHost, s));
-        TRY(wait());
+        TRY(f.fetch(heads.data(), d_heads, (size_t)x.pieces * WP));
         if (!lig::explain_records_walk(heads.data(), W, x, m_of, NA, items)) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: a rank's record block is malformed");
         if (!lig::explain_merge(items, NA, first, perm)) FAIL(c, LIG_E_STATE, "lig_shard_rows_explain_attached: a term names no asked constraint");
-        ordered.resize(total);
-        ask.resize(rep);
-        first32.assign(first.begin(), first.end());
-        for (uint32_t i = 0; i < total; i++) { ordered[i].slot = items[i].slot; ordered[i].coef = items[i].coef; }
-        for (uint32_t i = 0; i < rep; i++) ask[i] = items[i].ask;
-        lig_lin_term* d_ordered = nullptr; uint32_t *d_perm = nullptr, *d_ask = nullptr, *d_first = nullptr, *d_rhs_index = nullptr, *d_rhs_coef = nullptr;
-        lig_explain_constraint* d_con = nullptr; lig_explain_term* d_out = nullptr;
-        TRY(sc.alloc((void**)&d_ordered, (size_t)total * sizeof(lig_lin_term)));
-        TRY(sc.alloc((void**)&d_perm, (size_t)total * 4));
-        TRY(sc.alloc((void**)&d_ask, (size_t)rep * 4));
-        TRY(sc.alloc((void**)&d_first, ((size_t)NA + 1) * 4));
-        TRY(sc.alloc((void**)&d_rhs_index, (size_t)NA * 4));
-        TRY(sc.alloc((void**)&d_rhs_coef, (size_t)NA * 4));
-        TRY(sc.alloc((void**)&d_con, (size_t)NA * sizeof(lig_explain_constraint)));
-        TRY(sc.alloc((void**)&d_out, (size_t)rep * sizeof(lig_explain_term)));
-        if (total) {
-            HIP_TRY(c, hipMemcpyAsync(d_ordered, ordered.data(), (size_t)total * sizeof(lig_lin_term), hipMemcpyHostToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(d_perm, perm.data(), (size_t)total * 4, hipMemcpyHostToDevice, s));
-        }
-        if (rep) HIP_TRY(c, hipMemcpyAsync(d_ask, ask.data(), (size_t)rep * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_first, first32.data(), ((size_t)NA + 1) * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_rhs_index, rhs_index.data(), (size_t)NA * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_rhs_coef, rhs_coef.data(), (size_t)NA * 4, hipMemcpyHostToDevice, s));
-        if (total) hipLaunchKernelGGL(lig::k_explain_permute, dim3(diag_grid(total)), dim3(lig::LIN_WG), 0, s, d_vals_in, d_perm, total, d_vals);
-        HIP_TRY(c, hipGetLastError());
-        TRY(mark(APH_MERGE));
+        uint32_t *d_perm = nullptr, *d_rhs_index = nullptr, *d_rhs_coef = nullptr;
+        TRY(explain_upload(f, items, first, NA, rep, o));
+        TRY(f.upload(d_perm, perm.data(), total));
+        TRY(f.upload(d_rhs_index, rhs_index.data(), NA));
+        TRY(f.upload(d_rhs_coef, rhs_coef.data(), NA));
+        if (total) TRY(f.launch(lig::k_explain_permute, total, d_vals_in, d_perm, total, d_vals));
+        TRY(f.mark(APH_MERGE));
         // values set on the side stream (lig_shard_rows_set_linear_values): the table is read in place once its conversion has finished
         if (a.coef_ready) HIP_TRY(c, hipStreamWaitEvent(s, a.coef_ready, 0));
-        const lig::ExplainFromValues wit{d_vals};
-        if (rep) hipLaunchKernelGGL(lig::k_explain_fill<lig::ExplainFromValues>, dim3(diag_grid(rep)), dim3(lig::LIN_WG), 0, s, d_ordered, d_ask, rep, d_asked, wit, a.coef, d_out);
-        hipLaunchKernelGGL(lig::k_explain_finish<lig::ExplainFromValues>, dim3(std::min<uint32_t>(NA, lig::DIAG_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, s, d_first, d_ordered, d_asked, NA,
-                           wit, a.coef, d_rhs_index, d_rhs_coef, d_con);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(con_out, d_con, (size_t)NA * sizeof(lig_explain_constraint), hipMemcpyDeviceToHost, s));
-        if (rep) HIP_TRY(c, hipMemcpyAsync(terms_out, d_out, (size_t)rep * sizeof(lig_explain_term), hipMemcpyDeviceToHost, s));
-        TRY(wait());
-        TRY(mark(APH_RECORDS));
-        return LIG_OK;
-    };
-    const int rc = body();
-    if (rc != LIG_OK && v.settle_failed()) { sc.abandon(); return rc; }      // poisoned: the scratch outlives the call
-    if (rc == LIG_OK) (void)wait();
-    if (used_comm) v.forget();                                                // before any send buffer is freed (lig_comm.forget)
-    if (rc != LIG_OK) return rc;
+        TRY(explain_records(f, o, d_asked, lig::ExplainFromValues{d_vals}, a.coef, d_rhs_index, d_rhs_coef, con_out, terms_out));
+        return f.mark(APH_RECORDS);
+    }));
     info->n_terms_total = total;
     info->n_terms_reported = rep;
-    if (trace_on)
-        std::fprintf(stderr, "[lig_trace] shard_explain_attached rank %u: select %.3f exchange %.3f merge %.3f records %.3f ms\n", v.rank, ph[APH_SELECT], ph[APH_EXCHANGE],
-                     ph[APH_MERGE], ph[APH_RECORDS]);
     return LIG_OK;
 }
 
@@ -1700,45 +1577,22 @@ int lig_internal_shard_explain_attached(lig_ctx* c, const lig_diag_shard& v, con
 // trace, n_slots > 0) in pieces of P = min(n_slots, LIG_DIAG_SLICE); the summed piece is copied to `values`.  ceil(n_slots / P) all-gathers.
 // Scratch: 4 P (slots) + 32 P (send) + 32 W P (receive) + 32 P (sums) + 4 rows_global.
 int lig_internal_shard_read_slots(lig_ctx* c, const lig_diag_shard& v, const uint32_t* slots, uint64_t n_slots, uint8_t* values) {
-    hipStream_t s = c->stream;
-    std::vector<uint32_t> local_of;
-    DiagScratch sc(c);
-    bool used_comm = false;
-    const DiagWait wait = [&v]() -> int { return v.drain("lig_shard_rows_read_slots"); };
-    const bool trace_on = lig::knobs().trace;
-    double ph[XPH_N] = {0, 0, 0, 0};
-    auto t_mark = clk::now();
-    const std::function<int(int)> mark = [&](int p) -> int {
-        if (!trace_on) return LIG_OK;
-        TRY(wait());
-        ph[p] += ms_since(t_mark);
-        t_mark = clk::now();
-        return LIG_OK;
-    };
-    auto body = [&]() -> int {
+    std::vector<uint32_t> local_of;      // (source of a queued upload: declared before the frame)
+    DiagShardFrame f(c, v, "lig_shard_rows_read_slots", "shard_read_slots", XPH_NAMES);
+    return f.run([&]() -> int {
         ExplainExchange x;
         uint32_t* d_slots = nullptr; fr* d_val = nullptr;
-        TRY(explain_exchange_alloc(c, sc, v, local_of, n_slots, x));
-        TRY(sc.alloc((void**)&d_slots, (size_t)x.P * 4));
-        TRY(sc.alloc((void**)&d_val, (size_t)x.P * 32));
+        TRY(explain_exchange_alloc(f, local_of, n_slots, x));
+        TRY(f.alloc(d_slots, x.P));
+        TRY(f.alloc(d_val, x.P));
         const uint64_t n_pieces = lig::explain_piece_count(n_slots, x.P);
         for (uint64_t j = 0; j < n_pieces; j++) {
             const uint32_t n = (uint32_t)lig::explain_piece_len(n_slots, x.P, j);
-            HIP_TRY(c, hipMemcpyAsync(d_slots, slots + j * x.P, (size_t)n * 4, hipMemcpyHostToDevice, s));
-            used_comm = true;
-            TRY(explain_exchange_piece(c, v, x, d_slots, 1, n, d_val, mark, "all_gather(witness values of the slots)"));
-            HIP_TRY(c, hipMemcpyAsync(values + j * x.P * 32, d_val, (size_t)n * 32, hipMemcpyDeviceToHost, s));
-            TRY(wait());
-            TRY(mark(XPH_RECORDS));
+            HIP_TRY(c, hipMemcpyAsync(d_slots, slots + j * x.P, (size_t)n * 4, hipMemcpyHostToDevice, f.s));
+            TRY(explain_exchange_piece(f, x, d_slots, 1, n, d_val, "all_gather(witness values of the slots)"));
+            TRY(f.fetch(values + j * x.P * 32, d_val, n));
+            TRY(f.mark(XPH_RECORDS));
         }
         return LIG_OK;
-    };
-    const int rc = body();
-    if (rc != LIG_OK && v.settle_failed()) { sc.abandon(); return rc; }      // poisoned: the scratch outlives the call
-    if (rc == LIG_OK) (void)wait();
-    if (used_comm) v.forget();                                                // before any send buffer is freed (lig_comm.forget)
-    if (trace_on && rc == LIG_OK)
-        std::fprintf(stderr, "[lig_trace] shard_read_slots rank %u: part %.3f exchange %.3f sum %.3f records %.3f ms\n", v.rank, ph[XPH_PART], ph[XPH_EXCHANGE], ph[XPH_SUM],
-                     ph[XPH_RECORDS]);
-    return rc;
+    });
 }
