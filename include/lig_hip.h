@@ -639,8 +639,8 @@ int lig_rows_read_slots(lig_trace *trace, const uint32_t *slots, uint64_t n_slot
  * with n_asked > 0, terms_out == NULL with term_cap > 0, out == NULL with cap > 0, and the range and order errors above -- all decided
  * on the host before anything is launched: an index out of range never reaches a kernel.  n_asked = 0 is LIG_OK and launches nothing.
  * The new structs version themselves with struct_bytes; they are not part of lig_abi_sizes (LIG_ABI_STRUCTS stays 6).
- * Not covered here: the sharded entry (a rank's share numbers its slots locally and holds only the terms of its rows) -- the next
- * change, as after every one-GPU step of this line; a share of a sharded trace attached here is LIG_E_STATE. */
+ * The sharded entry (a rank's share numbers its slots locally and holds only the terms of its rows) has its own calls,
+ * lig_shard_rows_explain_slots* / lig_shard_rows_untouched_slots* below; a share of a sharded trace attached here is LIG_E_STATE. */
 typedef struct { uint32_t slot, row_kind; uint64_t n_terms, first_term; uint8_t value[32]; } lig_slot_record;                /* 56 bytes */
 typedef struct { uint32_t slot, constraint, coef_index, constraint_terms; uint8_t coef[32]; uint8_t residual[32]; } lig_slot_term; /* 80 bytes */
 typedef struct {
@@ -939,6 +939,68 @@ int lig_shard_rows_read_slots(lig_shard *shard, const uint32_t *slots, uint64_t 
  * positions and values, 4 bytes per local row, 8 W + 16 n_asked, and the records, 88 n_asked + 84 min(S, term_cap). */
 int lig_shard_rows_explain_attached(lig_shard *shard, const uint32_t *constraints, uint64_t n_asked,
                                     lig_explain_constraint *con_out, lig_explain_term *terms_out, uint64_t term_cap, lig_explain_info *info);
+/* lig_rows_explain_slots* / lig_rows_untouched_slots* on a rows shard: from a suspect SLOT to the other constraints through it, and the
+ * witness slots no term touches.  No host can answer either: the terms of a slot lie in the share of the one rank that was dealt its row,
+ * numbered compactly through that rank's need list, and the residuals of those constraints span ranks.
+ * SLOTS ARE GLOBAL: row * l + column over the committed rows of the WHOLE trace; the asked list is strictly ascending.
+ * COLLECTIVE: every rank passes the same arguments.  EVERY RANK RECEIVES THE SAME BYTES, and they are what
+ * lig_rows_explain_slots_attached / lig_rows_untouched_slots_attached return on a one-GPU trace of the same rows under the same system
+ * and the table in force: order and first_term, n_terms, constraint_terms, constraint numbers of the whole trace, coefficient values,
+ * residuals, value and row_kind, every count in *info.  info->ms_total is the rank's own.
+ * The _attached forms use the share lig_shard_rows_set_linear attached, with the values of lig_shard_rows_set_linear_values in force (a
+ * conversion still running on the side stream is waited for with its event).  The forms with `sys` (the term list of the WHOLE trace, the
+ * same on every rank) run lig_linear_check, make a temporary share of it on every rank (what lig_shard_rows_set_linear makes: 8 bytes per
+ * kept term + 4 per local slot and needed constraint, and as much again in scratch), run the attached path on it -- one code path -- and
+ * destroy it before they return; what is attached to the shard is then neither read nor modified.  For the same statement both forms
+ * return the same bytes.
+ * WINDOW, FAILURE, POISONING exactly as lig_shard_rows_explain_attached: from the return of lig_shard_rows_commit until the next
+ * lig_shard_rows_restart, before or after the proof; the envelope of a shard that was asked is byte-identical to that of one that was not;
+ * nothing the attachment owns is written.
+ * REFUSALS are decided on the host, identically on every rank, before any launch and any collective.  LIG_E_ARG: a NULL shard; a NULL or
+ * short *info; slots or slot_out NULL with n_asked > 0, terms_out NULL with term_cap > 0, out NULL with cap > 0; slots not strictly
+ * ascending; a slot >= rows * l of the whole trace; on the forms with `sys`, a NULL sys or one lig_linear_check rejects.  LIG_E_STATE: no
+ * system set (the _attached forms), before the commit or after the restart, a shard not made by lig_shard_rows_begin, a poisoned shard.
+ * n_asked == 0: LIG_OK, no launch, no collective.
+ * HOW, lig_shard_rows_explain_slots*:
+ *   1. host: every asked slot's row goes through the rank's global -> local row table; the rank keeps the asked indices whose row it was
+ *      dealt, with their LOCAL slot numbers (ascending: local rows are in commit order).
+ *   2. device, over that sub-list: the segment lengths of the rank's own slot-major index, an exclusive scan, and a collect into 16-byte
+ *      items {index in the asked list, constraint OF THE WHOLE TRACE (through the need list), coef_index, valid = 1}, one 16-byte store
+ *      each -- one lane per item, a whole workgroup for a slot with more than 2048 terms (every term through a slot lies on its owner);
+ *      the values with the gather of lig_rows_read_slots on the local matrix.  No atomic.
+ *   3. ONE header all-gather whose size n_asked alone fixes (16 + 48 n_asked bytes per rank): m_r, and per asked slot {held, n_terms,
+ *      value}.  A slot has exactly one holder; presence is a field of its own, never inferred from a zero value.
+ *   4. with M = max m_r and P = min(M, LIG_DIAG_SLICE): ceil(M / P) all-gathers of 16 P bytes per rank; a rank's block beyond its own m_r
+ *      is zeroed (valid = 0).  As in lig_shard_rows_explain_attached the NUMBER of collectives depends on what the ranks hold only through
+ *      the m_r every rank has received.
+ *   5. the host of every rank walks the items (a valid item past m_r, an index >= n_asked, an item for a slot another rank holds, a slot
+ *      with two holders or none, counts that do not add up: LIG_E_STATE, never an index), puts them into the output order and takes the
+ *      distinct constraints in ascending order.
+ *   6. their sizes and residuals come from lig_shard_rows_explain_attached ITSELF, asked for the constraint records alone (term_cap = 0)
+ *      after every collective of steps 3 and 4 is complete: one evaluator, as on one GPU.  The list is the same on every rank, so its
+ *      collective schedule is too; with no term on any asked slot there is no such call on any rank.
+ *   7. the fill kernel of lig_rows_explain_slots writes the records with the table in force, read in place behind its event.
+ * HOW, lig_shard_rows_untouched_slots*: every rank runs the flag / scan / compact passes of the one-GPU call over its LOCAL LINEAR .. QZ
+ * rows against its local index in slices of 2^22 slots, writes the slot numbers of the WHOLE trace and keeps its first
+ * min(cap, selected) records on the device.  ONE header all-gather of 32 bytes {n_untouched, n_untouched_nonzero, kept, 0}, then, with
+ * M = max kept and P = min(M, LIG_DIAG_SLICE), ceil(M / P) all-gathers of 40 P bytes per rank.  The host merges the W ascending lists by
+ * slot and cuts at cap: the first cap of all are among each rank's first cap, so the cut is exact.  The counts are sums over ranks and
+ * complete whatever cap is.
+ * world == 1 without LIG_SHARD_FORCE_EXCHANGE: the same passes with a device copy in place of every all-gather, no collective (the
+ * one-GPU call cannot serve: the share is compactly numbered); with the knob set the exchange path runs with one rank.
+ * SCRATCH lives for the call only, on the context's main stream (every send buffer is an allocation of its own, lig_comm.forget runs
+ * before any of them is freed, and the scratch is abandoned when the shard is poisoned).  Explain, with H = the asked slots the rank
+ * holds, S = sum m_r, J = ceil(M / P), D = the distinct constraints: 56 H + 4 n_asked, (W + 1) (16 + 48 n_asked) for the headers, 16 m_r
+ * collected items, 16 P (send) + 16 W P (receive) + 16 J W P for the host's walk, 88 D + 96 min(S, term_cap) for the records, and -- while
+ * it runs -- the scratch of lig_shard_rows_explain_attached for D asked constraints.  Untouched: 16 bytes per local LINEAR .. QZ row, 16
+ * per slot of a slice, 40 kept, 32 (W + 1), 40 P (send) + 40 W P (receive) + 40 J W P. */
+int lig_shard_rows_explain_slots_attached(lig_shard *shard, const uint32_t *slots, uint64_t n_asked,
+                                          lig_slot_record *slot_out, lig_slot_term *terms_out, uint64_t term_cap, lig_slot_info *info);
+int lig_shard_rows_explain_slots(lig_shard *shard, const lig_linear_system *sys, const uint32_t *slots, uint64_t n_asked,
+                                 lig_slot_record *slot_out, lig_slot_term *terms_out, uint64_t term_cap, lig_slot_info *info);
+int lig_shard_rows_untouched_slots_attached(lig_shard *shard, int nonzero_only, lig_slot_value *out, uint64_t cap, lig_untouched_info *info);
+int lig_shard_rows_untouched_slots(lig_shard *shard, const lig_linear_system *sys, int nonzero_only, lig_slot_value *out, uint64_t cap,
+                                   lig_untouched_info *info);
 
 /* sizeof of the public structs as this build of the library sees them, in the order {lig_batch_op, lig_synth_job, lig_proof_info,
  * lig_verify_info, lig_rows_job, lig_comm}: a binding in another language (ctypes, cgo, JNI) checks its own layouts against these at

@@ -413,7 +413,7 @@ public:
     // explain() does; a batcher with a prepared program or without a system has no term list: std::logic_error (the _attached forms).
     // explain_slots_attached() / untouched_slots_attached(): the statement attached to the trace, as explain_attached().
     // All after commit(), before or after prove(), until the next commit(); the same bytes for the same statement.  std::logic_error
-    // before commit(), and on a batcher with shard_over(): a rank's share holds only the terms of its rows.
+    // before commit(), and on a batcher with shard_over(): a rank's share holds only the terms of its rows (the shard_ forms below).
     void explain_slots(const uint32_t* slots, uint64_t n_asked, lig_slot_record* slot_out, lig_slot_term* terms_out, uint64_t term_cap, lig_slot_info* info) {
         slots_ready("explain_slots", false);
         if (!info) throw std::invalid_argument("hip_row_batcher::explain_slots: null info");
@@ -442,6 +442,41 @@ public:
         if (!info) throw std::invalid_argument("hip_row_batcher::untouched_slots_attached: null info");
         info->struct_bytes = sizeof(lig_untouched_info);
         check(lig_rows_untouched_slots_attached(trace_, nonzero_only ? 1 : 0, out, cap, info), "lig_rows_untouched_slots_attached");
+    }
+    // The four calls above for a batcher with shard_over(): lig_shard_rows_explain_slots* / lig_shard_rows_untouched_slots* (lig_hip.h),
+    // COLLECTIVE calls over every rank's share -- the slots are those of the WHOLE trace, every rank passes the same arguments and gets the
+    // bytes the unsharded batcher returns.  shard_explain_slots() / shard_untouched_slots(): the system given to set_linear_system with the
+    // table of set_linear_values if one was set (a temporary share is made of it on every rank and released); the _attached forms: the
+    // share attached to the shard, no term list.  Window as explain_slots(); std::logic_error before commit(), on an unsharded batcher
+    // and without a linear system.
+    void shard_explain_slots(const uint32_t* slots, uint64_t n_asked, lig_slot_record* slot_out, lig_slot_term* terms_out, uint64_t term_cap, lig_slot_info* info) {
+        shard_slots_ready("shard_explain_slots", false);
+        if (!info) throw std::invalid_argument("hip_row_batcher::shard_explain_slots: null info");
+        lig_linear_system sys = *linear_.get();
+        if (values_set_) { sys.coefs = values_.data(); sys.n_coefs = values_.size() / 32; }
+        info->struct_bytes = sizeof(lig_slot_info);
+        check(lig_shard_rows_explain_slots(shard_, &sys, slots, n_asked, slot_out, terms_out, term_cap, info), "lig_shard_rows_explain_slots");
+    }
+    void shard_explain_slots_attached(const uint32_t* slots, uint64_t n_asked, lig_slot_record* slot_out, lig_slot_term* terms_out, uint64_t term_cap,
+                                      lig_slot_info* info) {
+        shard_slots_ready("shard_explain_slots_attached", true);
+        if (!info) throw std::invalid_argument("hip_row_batcher::shard_explain_slots_attached: null info");
+        info->struct_bytes = sizeof(lig_slot_info);
+        check(lig_shard_rows_explain_slots_attached(shard_, slots, n_asked, slot_out, terms_out, term_cap, info), "lig_shard_rows_explain_slots_attached");
+    }
+    void shard_untouched_slots(bool nonzero_only, lig_slot_value* out, uint64_t cap, lig_untouched_info* info) {
+        shard_slots_ready("shard_untouched_slots", false);
+        if (!info) throw std::invalid_argument("hip_row_batcher::shard_untouched_slots: null info");
+        lig_linear_system sys = *linear_.get();
+        if (values_set_) { sys.coefs = values_.data(); sys.n_coefs = values_.size() / 32; }
+        info->struct_bytes = sizeof(lig_untouched_info);
+        check(lig_shard_rows_untouched_slots(shard_, &sys, nonzero_only ? 1 : 0, out, cap, info), "lig_shard_rows_untouched_slots");
+    }
+    void shard_untouched_slots_attached(bool nonzero_only, lig_slot_value* out, uint64_t cap, lig_untouched_info* info) {
+        shard_slots_ready("shard_untouched_slots_attached", true);
+        if (!info) throw std::invalid_argument("hip_row_batcher::shard_untouched_slots_attached: null info");
+        info->struct_bytes = sizeof(lig_untouched_info);
+        check(lig_shard_rows_untouched_slots_attached(shard_, nonzero_only ? 1 : 0, out, cap, info), "lig_shard_rows_untouched_slots_attached");
     }
     // the next proof with this batcher: staging and (for the same row kinds) every device buffer of the trace are kept
     void reset(const hip_proof_meta* meta = nullptr) {
@@ -483,6 +518,14 @@ private:
         if (pass_ == 1 || !trace_) throw std::logic_error(w + " before commit");
         if (attached && (!has_linear() || !linear_on_trace_)) throw std::logic_error(w + " without a linear system or program");
         if (!attached && !linear_.is_set()) throw std::logic_error(w + " without a linear system (the _attached form)");
+    }
+    // shard_explain_slots* / shard_untouched_slots*: sharded, after commit(), with the statement the entry reads
+    void shard_slots_ready(const char* what, bool attached) const {
+        const std::string w = std::string("hip_row_batcher::") + what;
+        if (!sharded_) throw std::logic_error(w + ": not a sharded batcher (the call without shard_)");
+        if (pass_ == 1 || !shard_) throw std::logic_error(w + " before commit");
+        if (attached && (!has_linear() || !linear_on_trace_)) throw std::logic_error(w + " without a linear system");
+        if (!attached && !linear_.is_set()) throw std::logic_error(w + " without a linear system");
     }
     void apply_linear() {
         if (!has_linear() || !(sharded_ ? (bool)shard_ : (bool)trace_)) return;

@@ -47,6 +47,7 @@ EXPORTS = [
     "lig_rows_explain_slots", "lig_rows_explain_slots_attached", "lig_rows_untouched_slots", "lig_rows_untouched_slots_attached",
     "lig_shard_rows_explain", "lig_shard_rows_read_slots", "lig_shard_rows_explain_attached",
     "lig_shard_rows_set_linear_values", "lig_shard_rows_diagnose_attached",
+    "lig_shard_rows_explain_slots", "lig_shard_rows_explain_slots_attached", "lig_shard_rows_untouched_slots", "lig_shard_rows_untouched_slots_attached",
 ]
 
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
@@ -416,6 +417,10 @@ def load_library():
     L.lig_shard_rows_explain.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
     L.lig_shard_rows_read_slots.argtypes = [vp, vp, u64, vp]
     L.lig_shard_rows_explain_attached.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(ExplainInfo)]
+    L.lig_shard_rows_explain_slots.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, u64, C.POINTER(SlotInfo)]
+    L.lig_shard_rows_explain_slots_attached.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(SlotInfo)]
+    L.lig_shard_rows_untouched_slots.argtypes = [vp, C.POINTER(LinearSystem), C.c_int, vp, u64, C.POINTER(UntouchedInfo)]
+    L.lig_shard_rows_untouched_slots_attached.argtypes = [vp, C.c_int, vp, u64, C.POINTER(UntouchedInfo)]
     return L
 
 
@@ -1259,6 +1264,28 @@ class Context:
         values of shard_rows_set_linear_values in force): no term list is passed.  Collective: every rank passes the same constraints and
         the same term_cap and gets the same triple as shard_rows_explain"""
         return self._rows_explain(self.L.lig_shard_rows_explain_attached, (shard,), constraints, term_cap)
+
+    def shard_rows_explain_slots(self, shard, system, slots, term_cap=4096):
+        """lig_shard_rows_explain_slots: rows_explain_slots on a rows shard.  Collective: every rank passes the same `system` (of the WHOLE
+        trace), the same GLOBAL slots (row * l + column over the rows of the whole trace, strictly ascending) and the same term_cap, and
+        every rank gets the triple rows_explain_slots gives for the whole trace on one GPU"""
+        return self._rows_explain_slots(self.L.lig_shard_rows_explain_slots, (shard, C.byref(system) if system is not None else None), slots, term_cap)
+
+    def shard_rows_explain_slots_attached(self, shard, slots, term_cap=4096):
+        """lig_shard_rows_explain_slots_attached: shard_rows_explain_slots against the system attached to the shard (shard_rows_set_linear,
+        with the values of shard_rows_set_linear_values in force): no term list is passed.  Collective -> the same triple on every rank"""
+        return self._rows_explain_slots(self.L.lig_shard_rows_explain_slots_attached, (shard,), slots, term_cap)
+
+    def shard_rows_untouched_slots(self, shard, system, nonzero_only=False, cap=1024):
+        """lig_shard_rows_untouched_slots: rows_untouched_slots on a rows shard.  Collective: every rank passes the same `system` (of the
+        WHOLE trace), nonzero_only and cap, and every rank gets the pair rows_untouched_slots gives for the whole trace on one GPU (global
+        slots; the counts cover all ranks)"""
+        return self._rows_untouched_slots(self.L.lig_shard_rows_untouched_slots, (shard, C.byref(system) if system is not None else None), nonzero_only, cap)
+
+    def shard_rows_untouched_slots_attached(self, shard, nonzero_only=False, cap=1024):
+        """lig_shard_rows_untouched_slots_attached: shard_rows_untouched_slots against the system attached to the shard.  Collective -> the
+        same pair on every rank"""
+        return self._rows_untouched_slots(self.L.lig_shard_rows_untouched_slots_attached, (shard,), nonzero_only, cap)
 
     def shard_rows_read_slots(self, shard, slots):
         """lig_shard_rows_read_slots: rows_read_slots on a rows shard.  Collective: every rank passes the same global slots (row * l + column

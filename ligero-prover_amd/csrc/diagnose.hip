@@ -15,7 +15,8 @@
 // ATTACHED to the shard instead (k_diag_att_bounds, k_diag_att_part*: their header below) and lets the one holder of a right-hand side
 // subtract it there; the owner then only adds (k_diag_reduce<false>).
 // lig_rows_explain* / lig_rows_read_slots and their sharded counterparts (k_explain_*, k_read_slots) have a header of their own below, and so
-// have lig_rows_explain_slots* / lig_rows_untouched_slots* (k_slot_*, k_untouched_*), which read the slot-major program as it stands.
+// have lig_rows_explain_slots* / lig_rows_untouched_slots* (k_slot_*, k_untouched_*), which read the slot-major program as it stands, and
+// their sharded counterparts (k_slot_header, k_slot_collect_shard*: the owner of a slot's row collects, every rank receives).
 // Where the constraint-major list comes from is the only difference between the two one-GPU entries:
 //   lig_rows_diagnose            the caller's lig_linear_system, uploaded, with a scratch copy of its table in Montgomery form
 //   lig_rows_diagnose_attached   the statement ATTACHED to the trace.  Its program keeps the terms slot-major (linear.hip: begin[], ent[] =
@@ -49,6 +50,7 @@
 namespace lig {
 static constexpr uint32_t DIAG_MAX_BLOCKS = COEFS_MAX_BLOCKS;      // grid-stride passes: at most this many workgroups of LIN_WG lanes
 static constexpr uint64_t DIAG_QUAD_ITEMS = 1ull << 20;            // scratch budget of the quadratic pass: (term, column) items per slice (40 bytes each)
+static constexpr uint64_t DIAG_UNTOUCHED_ITEMS = 1ull << 22;       // scratch budget of the untouched pass: slots per slice (16 bytes each)
 
 // n / d for n < 2^32 and the launch-uniform d >= 1: m = floor(2^64 / d) + 1 (host: diag_reciprocal), exact because n * (m d - 2^64) < 2^64
 static __device__ __forceinline__ uint32_t diag_div(uint32_t n, uint64_t m) { return (uint32_t)__umul64hi((uint64_t)n, m); }
@@ -581,13 +583,57 @@ __global__ void __launch_bounds__(LIN_WG) k_slot_fill(const ExplainItem* __restr
         o[4] = make_uint4(r2.x, r2.y, r3.x, r3.y);
     }
 }
+// ---- lig_shard_rows_explain_slots*: one rank of a sharded rows job.  Every term through a slot lies in the share of the rank that was dealt
+// its row, so that rank runs k_slot_len / the scan / k_read_slots over the asked slots it holds, in its LOCAL numbering (lslots, ascending;
+// mine[i] = the index of lslots[i] in the asked list of the whole call), and
+//   k_slot_header               one lane per held slot: {held = 1, n_terms, 0, 0, value} into the rank's header block (slot_header_at,
+//                               explain_plan.hpp; 48 bytes at a 16-byte boundary: three 16-byte stores).  The block was zeroed first.
+//   k_slot_collect_shard        k_slot_collect into 16-byte SlotItems {index in the asked list, constraint OF THE WHOLE TRACE = need[ent.x],
+//                               coefficient index, valid = 1}, one 16-byte store each
+//   k_slot_collect_shard_heavy  k_slot_collect_heavy likewise: a hot slot's terms all lie on its owner
+// No atomic.  Every lslots[i] < n_slots = rows_local * l, every mine[i] < n_asked (slot_asked_here made both on the host), ent[].x < n_need
+// (the prepare), m <= n_terms checked before the collect is launched.
+__global__ void __launch_bounds__(LIN_WG) k_slot_header(const uint32_t* __restrict__ mine, const uint32_t* __restrict__ len, const fr* __restrict__ val, uint32_t n_here,
+                                                        uint32_t* __restrict__ hdr) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n_here; i += (uint64_t)gridDim.x * LIN_WG) {
+        uint4* o = reinterpret_cast<uint4*>(hdr + slot_header_at(mine[i]));
+        o[0] = make_uint4(1u, len[i], 0u, 0u);
+        fr_store(reinterpret_cast<fr*>(o + 1), fr_load(val + i));
+    }
+}
+static __device__ __forceinline__ void slot_item_store(SlotItem* __restrict__ at, uint32_t ask, const uint2 en, const uint32_t* __restrict__ need) {
+    *reinterpret_cast<uint4*>(at) = make_uint4(ask, need[en.x], en.y, 1u);
+}
+__global__ void __launch_bounds__(LIN_WG) k_slot_collect_shard(const uint32_t* __restrict__ lslots, const uint32_t* __restrict__ mine, uint32_t n_here,
+                                                               const uint32_t* __restrict__ pre, uint32_t m, const uint32_t* __restrict__ begin,
+                                                               const uint2* __restrict__ ent, const uint32_t* __restrict__ need, SlotItem* __restrict__ items) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < m; i += (uint64_t)gridDim.x * LIN_WG) {
+        const uint32_t a = diag_slot_of(pre, n_here, (uint32_t)i), b = pre[a];
+        if (pre[a + 1] - b > HEAVY_MIN) continue;                             // k_slot_collect_shard_heavy
+        slot_item_store(items + i, mine[a], ent[begin[lslots[a]] + ((uint32_t)i - b)], need);
+    }
+}
+// workgroup -> heavy held slot heavy[blockIdx.x + i * gridDim.x] (indices into lslots, ascending)
+__global__ void __launch_bounds__(LIN_WG) k_slot_collect_shard_heavy(const uint32_t* __restrict__ heavy, uint32_t n_heavy, const uint32_t* __restrict__ lslots,
+                                                                     const uint32_t* __restrict__ mine, const uint32_t* __restrict__ pre,
+                                                                     const uint32_t* __restrict__ begin, const uint2* __restrict__ ent,
+                                                                     const uint32_t* __restrict__ need, SlotItem* __restrict__ items) {
+    for (uint32_t h = blockIdx.x; h < n_heavy; h += gridDim.x) {
+        const uint32_t a = heavy[h], b = pre[a], n = pre[a + 1] - b, src = begin[lslots[a]], ask = mine[a];
+        for (uint32_t j = threadIdx.x; j < n; j += LIN_WG) slot_item_store(items + b + j, ask, ent[src + j], need);
+    }
+}
 // ---- lig_rows_untouched_slots*: the slots of the LINEAR / QX / QY / QZ rows with an empty segment.  lrows = those rows ascending, {row, kind};
-// item i of a slice = column i % l of row lrows[first + i / l].
+// item i of a slice = column i % l of row lrows[first + i / l].  On a rank of a sharded rows job (lig_shard_rows_untouched_slots*) lrows is
+// {LOCAL row, kind, row of the WHOLE trace, 0}: the local row addresses begin[] and the matrix, the global one makes the record's slot.
 //   k_untouched_flag     flag[i] = 1 when the segment of the slot is empty, + 2^32 when its committed element is not zero besides (fr_load:
 //                        two 16-byte loads) -- one 64-bit exclusive scan (rocPRIM) carries both counts, no atomic
 //   k_untouched_compact  the selected slots with a position below `cap` -> {slot, kind, value} in ascending order; a record has 40 bytes:
 //                        8-byte stores
-__global__ void __launch_bounds__(LIN_WG) k_untouched_flag(const uint2* __restrict__ lrows, uint32_t first, uint32_t n_items, const uint32_t* __restrict__ begin,
+static __device__ __forceinline__ uint32_t untouched_trace_row(const uint2 lr) { return lr.x; }
+static __device__ __forceinline__ uint32_t untouched_trace_row(const uint4 lr) { return lr.z; }
+template <class LR>
+__global__ void __launch_bounds__(LIN_WG) k_untouched_flag(const LR* __restrict__ lrows, uint32_t first, uint32_t n_items, const uint32_t* __restrict__ begin,
                                                            const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip, uint64_t* __restrict__ flag) {
     for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n_items; i += (uint64_t)gridDim.x * LIN_WG) {
         const uint32_t t = diag_div((uint32_t)i, l_recip), col = (uint32_t)i - t * l, row = lrows[first + t].x, s = row * l + col;
@@ -596,7 +642,8 @@ __global__ void __launch_bounds__(LIN_WG) k_untouched_flag(const uint2* __restri
         flag[i] = f;
     }
 }
-__global__ void __launch_bounds__(LIN_WG) k_untouched_compact(const uint64_t* __restrict__ flag, const uint64_t* __restrict__ pos, const uint2* __restrict__ lrows,
+template <class LR>
+__global__ void __launch_bounds__(LIN_WG) k_untouched_compact(const uint64_t* __restrict__ flag, const uint64_t* __restrict__ pos, const LR* __restrict__ lrows,
                                                               uint32_t first, uint32_t n_items, const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip,
                                                               uint32_t nonzero_only, uint32_t cap, lig_slot_value* __restrict__ out) {
     const uint32_t shift = nonzero_only ? 32u : 0u;
@@ -604,10 +651,10 @@ __global__ void __launch_bounds__(LIN_WG) k_untouched_compact(const uint64_t* __
         const uint32_t at = (uint32_t)(pos[i] >> shift);
         if (!(uint32_t)(flag[i] >> shift) || at >= cap) continue;
         const uint32_t t = diag_div((uint32_t)i, l_recip), col = (uint32_t)i - t * l;
-        const uint2 lr = lrows[first + t];
+        const LR lr = lrows[first + t];
         const fr w = fr_load(msgs + (size_t)lr.x * k + col);
         uint2* o = reinterpret_cast<uint2*>(out + at);
-        o[0] = make_uint2(lr.x * l + col, lr.y);
+        o[0] = make_uint2(untouched_trace_row(lr) * l + col, lr.y);
         for (int j = 0; j < 4; j++) o[1 + j] = make_uint2(w.v[2 * j], w.v[2 * j + 1]);
     }
 }
@@ -1097,7 +1144,7 @@ int lig_internal_rows_explain_slots(lig_ctx* c, const fr* msgs, const uint8_t* k
 // counts, and once more for the records of a slice that reports some.
 int lig_internal_rows_untouched_slots(lig_ctx* c, const fr* msgs, const uint8_t* kinds, uint64_t rows, const lig_linear_view& v, int nonzero_only, lig_slot_value* out,
                                       uint64_t cap, lig_untouched_info* info) {
-    static constexpr uint64_t UNTOUCHED_ITEMS = 1ull << 22;      // scratch budget: slots per slice (16 bytes each)
+    static constexpr uint64_t UNTOUCHED_ITEMS = lig::DIAG_UNTOUCHED_ITEMS;
     if (v.sharded) FAIL(c, LIG_E_STATE, "lig_rows_untouched_slots: the attached structure is one rank's share of a sharded trace");
     if ((uint64_t)v.n_slots != rows * (uint64_t)c->l) FAIL(c, LIG_E_STATE, "lig_rows_untouched_slots: the program does not cover the slots of this trace");
     const uint32_t l = c->l;
@@ -1117,7 +1164,7 @@ int lig_internal_rows_untouched_slots(lig_ctx* c, const fr* msgs, const uint8_t*
     for (uint64_t r0 = 0; r0 < NL; r0 += per) {      // (the first slice is the largest: its scan sizes the temp for all of them)
         const uint32_t items = (uint32_t)(std::min(per, NL - r0) * l);
         TRY(f.zero(d_flag + items, 1));
-        TRY(f.launch(lig::k_untouched_flag, items, d_lrows, (uint32_t)r0, items, v.begin, msgs, l, f.k, f.l_recip, d_flag));
+        TRY(f.launch(lig::k_untouched_flag<uint2>, items, d_lrows, (uint32_t)r0, items, v.begin, msgs, l, f.k, f.l_recip, d_flag));
         uint64_t both = 0;      // the two counts of the slice, packed
         TRY(f.scan(d_flag, d_pos, items, &both));
         const uint32_t un = (uint32_t)both, nz = (uint32_t)(both >> 32);
@@ -1125,7 +1172,7 @@ int lig_internal_rows_untouched_slots(lig_ctx* c, const fr* msgs, const uint8_t*
         n_untouched += un; n_nonzero += nz;
         const uint32_t rep = (uint32_t)std::min<uint64_t>(nonzero_only ? nz : un, cap - reported);
         if (rep) {
-            TRY(f.launch(lig::k_untouched_compact, items, d_flag, d_pos, d_lrows, (uint32_t)r0, items, msgs, l, f.k, f.l_recip, nonzero_only ? 1u : 0u, rep, d_out));
+            TRY(f.launch(lig::k_untouched_compact<uint2>, items, d_flag, d_pos, d_lrows, (uint32_t)r0, items, msgs, l, f.k, f.l_recip, nonzero_only ? 1u : 0u, rep, d_out));
             TRY(f.fetch(out + reported, d_out, rep));
             reported += rep;
         }
@@ -1595,4 +1642,251 @@ int lig_internal_shard_read_slots(lig_ctx* c, const lig_diag_shard& v, const uin
         }
         return LIG_OK;
     });
+}
+
+// One rank of a sharded rows job (lig_shard_rows_explain_slots*, lig_hip.h).  att = the rank's share attached to the shard, or the temporary
+// share the entry made from the caller's term list (sharded either way); kinds: one per committed row of the WHOLE trace; slots has passed
+// explain_slots_ok against the rows of the whole trace and is strictly ascending, n_asked > 0.  alone: as lig_internal_shard_explain_attached.
+// Collective: ONE header all-gather of 4 slot_header_words(n_asked) bytes per rank (m_r, and per asked slot {held, n_terms, value}), then --
+// with M = max m_r, known on every rank from the headers -- explain_piece_count(M, P) all-gathers of 16 P bytes per rank,
+// P = explain_piece_size(M, LIG_DIAG_SLICE); then, when any slot has a term, lig_internal_shard_explain_attached itself over the distinct
+// constraints with term_cap = 0 (one evaluator; the list is the same on every rank, hence its schedule).  The fetch of the last piece has
+// drained the stream before that call: no collective of this frame is in flight while the inner frame issues its own, and the inner frame's
+// v.forget runs while this frame's send buffers are still allocated -- this frame's own runs again before they are freed.
+// Scratch on top of the inner call: 12 n_here + 32 n_here + 8 (n_here + 1) for the held slots (local numbers, indices, values, lengths and
+// prefix sums), 4 n_asked, (W + 1) header blocks, 16 m_r collected items, 16 P (send) + 16 W P (receive) + 16 J W P for the host's walk
+// (J = ceil(M / P)), and the records: 88 distinct + 96 min(sum m_r, term_cap).
+int lig_internal_shard_explain_slots(lig_ctx* c, const lig_diag_shard& v, const lig_linear* att, bool alone, const uint8_t* kinds, const uint32_t* slots, uint64_t n_asked,
+                                     lig_slot_record* slot_out, lig_slot_term* terms_out, uint64_t term_cap, lig_slot_info* info) {
+    static const char* const who = "lig_shard_rows_explain_slots";
+    const lig_linear_view a = lig_internal_linear_view(att);
+    const uint32_t NA = (uint32_t)n_asked, W = v.world, l = c->l, k = c->k, NT = (uint32_t)a.n_terms;
+    const uint64_t rows_local = v.grow->size();
+    // what the kernels index with: the local slots tile the rank's rows, a slot of the whole trace fits 32 bits
+    if (!a.sharded || a.rows_local != rows_local || (uint64_t)a.n_slots != rows_local * l || v.rows_global * (uint64_t)l > (1ull << 32) || a.n_terms >= (1ull << 32) ||
+        (NT && !rows_local) || v.rank >= W || (alone && W != 1))
+        FAIL(c, LIG_E_STATE, std::string(who) + ": the linear structure is not this rank's share of the sharded trace");
+    // (sources and targets of queued copies: declared before the frame, whose scratch drains the stream when it goes)
+    std::vector<uint32_t> local_of(v.rows_global, lig::LIN_NOT_LOCAL), mine, lslots, pre, heavy, hdr_all, holder, n_terms, values, distinct, cidx;
+    for (size_t lr = 0; lr < rows_local; lr++) {
+        if ((*v.grow)[lr] >= v.rows_global) FAIL(c, LIG_E_STATE, std::string(who) + ": a local row lies outside the trace");
+        local_of[(*v.grow)[lr]] = (uint32_t)lr;
+    }
+    lig::slot_asked_here(slots, n_asked, l, local_of, lig::LIN_NOT_LOCAL, mine, lslots);
+    const uint32_t NM = (uint32_t)mine.size();
+    std::vector<uint64_t> m_of, first;
+    std::vector<lig::SlotItem> recv_all;
+    std::vector<lig::ExplainItem> items;
+    std::vector<lig_explain_constraint> con;
+    enum { SPH_SELECT, SPH_EXCHANGE, SPH_MERGE, SPH_RESIDUALS, SPH_RECORDS };
+    DiagShardFrame f(c, v, who, "shard_explain_slots", {"select", "exchange", "merge", "residuals", "records"}, alone);
+    hipStream_t s = f.s;
+    uint32_t total = 0, rep = 0, ND = 0;
+
+    TRY(f.run([&]() -> int {
+        // 1. the asked slots this rank holds: segment lengths, prefix sums, values, the header block, the items
+        const size_t hw = (size_t)lig::slot_header_words(NA);
+        uint32_t *d_slots = nullptr, *d_lslots = nullptr, *d_mine = nullptr, *d_len = nullptr, *d_pre = nullptr, *d_hdr = nullptr, *d_hdr_all = nullptr; fr* d_val = nullptr;
+        TRY(f.upload(d_slots, slots, NA));
+        TRY(f.upload(d_lslots, lslots.data(), NM));
+        TRY(f.upload(d_mine, mine.data(), NM));
+        TRY(f.alloc(d_len, (size_t)NM + 1));
+        TRY(f.alloc(d_pre, (size_t)NM + 1));
+        TRY(f.alloc(d_val, NM));
+        TRY(f.alloc(d_hdr, hw));
+        TRY(f.alloc(d_hdr_all, (size_t)W * hw));
+        TRY(f.zero(d_hdr, hw));
+        TRY(f.zero(d_len + NM, 1));
+        if (NM) {
+            TRY(f.launch(lig::k_slot_len, NM, d_lslots, NM, a.begin, d_len));
+            TRY(f.launch(lig::k_read_slots, NM, d_lslots, NM, v.msgs, l, k, f.l_recip, d_val));
+        }
+        TRY(f.scan_enqueue(d_len, d_pre, NM));
+        HIP_TRY(c, hipMemcpyAsync(d_hdr, d_pre + NM, 4, hipMemcpyDeviceToDevice, s));
+        if (NM) TRY(f.launch(lig::k_slot_header, NM, d_mine, d_len, d_val, NM, d_hdr));
+        pre.resize((size_t)NM + 1);
+        TRY(f.fetch(pre.data(), d_pre, (size_t)NM + 1));
+        const uint32_t m_own = pre[NM];
+        // distinct slots own disjoint segments: the lengths add up to at most the terms kept, every prefix sum is exact in 32 bits
+        if (m_own > NT || !std::is_sorted(pre.begin(), pre.end())) FAIL(c, LIG_E_STATE, std::string(who) + ": the share's index does not add up to its term count");
+        for (uint32_t i = 0; i < NM; i++) if (pre[i + 1] - pre[i] > lig::HEAVY_MIN) heavy.push_back(i);
+        lig::SlotItem* d_items = nullptr;
+        TRY(f.alloc(d_items, m_own));
+        if (m_own) TRY(f.launch(lig::k_slot_collect_shard, m_own, d_lslots, d_mine, NM, d_pre, m_own, a.begin, a.ent, a.need, d_items));
+        if (!heavy.empty()) {
+            uint32_t* d_heavy = nullptr;
+            TRY(f.upload(d_heavy, heavy.data(), heavy.size()));
+            TRY(f.launch_blocks(lig::k_slot_collect_shard_heavy, (uint32_t)heavy.size(), d_heavy, (uint32_t)heavy.size(), d_lslots, d_mine, d_pre, a.begin, a.ent, a.need, d_items));
+        }
+        TRY(f.mark(SPH_SELECT));
+        // 2. the headers: every m_r, the holder of every slot with its count and value
+        TRY(f.all_gather(d_hdr, d_hdr_all, hw * 4, "all_gather(counts and values of the asked slots)"));
+        hdr_all.resize((size_t)W * hw);
+        TRY(f.fetch(hdr_all.data(), d_hdr_all, (size_t)W * hw));
+        if (!lig::slot_header_merge(hdr_all.data(), W, NA, m_of, holder, n_terms, values) || m_of[v.rank] != m_own)
+            FAIL(c, LIG_E_STATE, std::string(who) + ": a rank's header block is malformed");
+        const lig::ExplainRecordSchedule x = lig::explain_record_schedule(m_of, v.slice);
+        if ((uint64_t)W * x.P >= (1ull << 32)) FAIL(c, LIG_E_STATE, std::string(who) + ": a piece of the item exchange exceeds 2^32 items");
+        total = (uint32_t)x.off[W];
+        rep = (uint32_t)std::min<uint64_t>(total, term_cap);
+        TRY(f.mark(SPH_EXCHANGE));
+        // 3. the items, in pieces of P per rank
+        const size_t WP = (size_t)W * x.P;
+        lig::SlotItem *d_send = nullptr, *d_recv = nullptr, *d_all = nullptr;
+        TRY(f.alloc(d_send, x.P));
+        TRY(f.alloc(d_recv, WP));
+        TRY(f.alloc(d_all, (size_t)x.pieces * WP));
+        for (uint64_t j = 0; j < x.pieces; j++) {
+            const uint64_t lo = std::min<uint64_t>(j * x.P, m_own), n = std::min<uint64_t>(x.P, m_own - lo);      // this rank's items of the piece
+            if (n) HIP_TRY(c, hipMemcpyAsync(d_send, d_items + lo, (size_t)n * sizeof(lig::SlotItem), hipMemcpyDeviceToDevice, s));
+            if (n < x.P) TRY(f.zero(d_send + n, x.P - n));
+            TRY(f.mark(SPH_SELECT));
+            TRY(f.all_gather(d_send, d_recv, (size_t)x.P * sizeof(lig::SlotItem), "all_gather(the terms through the asked slots of every rank)"));
+            HIP_TRY(c, hipMemcpyAsync(d_all + j * WP, d_recv, WP * sizeof(lig::SlotItem), hipMemcpyDeviceToDevice, s));
+            TRY(f.mark(SPH_EXCHANGE));
+        }
+        // 4. walk, order, the distinct constraints -- on the host of every rank.  The fetch drains the stream: every collective above is complete.
+        recv_all.resize((size_t)x.pieces * WP);
+        TRY(f.fetch(recv_all.data(), d_all, recv_all.size()));
+        if (!lig::slot_items_walk(recv_all.data(), W, x, m_of, NA, holder, n_terms, items)) FAIL(c, LIG_E_STATE, std::string(who) + ": a rank's item block is malformed");
+        if (!lig::explain_order(items, NA, first)) FAIL(c, LIG_E_STATE, std::string(who) + ": a collected term names no asked slot");
+        distinct.resize(total);
+        for (uint32_t i = 0; i < total; i++) {
+            if (items[i].slot >= a.n_constraints) FAIL(c, LIG_E_STATE, std::string(who) + ": an item names no constraint of the system");
+            distinct[i] = items[i].slot;
+        }
+        std::sort(distinct.begin(), distinct.end());
+        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+        ND = (uint32_t)distinct.size();
+        con.resize(ND);
+        TRY(f.mark(SPH_MERGE));
+        // 5. their sizes and residuals: the attached selection pass of the shard itself, asked for the constraint records alone
+        if (ND) {
+            lig_explain_info einfo;
+            std::memset(&einfo, 0, sizeof einfo);
+            einfo.struct_bytes = sizeof einfo;
+            TRY(lig_internal_shard_explain_attached(c, v, att, alone, distinct.data(), ND, con.data(), nullptr, 0, &einfo));
+        }
+        TRY(f.mark(SPH_RESIDUALS));
+        // 6. the records, with the table in force
+        if (rep) {
+            cidx.resize(rep);
+            for (uint32_t i = 0; i < rep; i++) cidx[i] = (uint32_t)(std::lower_bound(distinct.begin(), distinct.end(), items[i].slot) - distinct.begin());
+            lig::ExplainItem* d_ordered = nullptr; uint32_t* d_cidx = nullptr; lig_explain_constraint* d_con = nullptr; lig_slot_term* d_out = nullptr;
+            TRY(f.upload(d_ordered, items.data(), rep));
+            TRY(f.upload(d_cidx, cidx.data(), rep));
+            TRY(f.upload(d_con, con.data(), ND));
+            TRY(f.alloc(d_out, rep));
+            // values set on the side stream (lig_shard_rows_set_linear_values): the table is read in place once its conversion has finished
+            if (a.coef_ready) HIP_TRY(c, hipStreamWaitEvent(s, a.coef_ready, 0));
+            TRY(f.launch(lig::k_slot_fill, rep, d_ordered, d_cidx, rep, d_slots, d_con, a.coef, d_out));
+            TRY(f.fetch(terms_out, d_out, rep));
+        }
+        return f.mark(SPH_RECORDS);
+    }));
+    for (uint32_t i = 0; i < NA; i++) {
+        lig_slot_record& r = slot_out[i];
+        std::memset(&r, 0, sizeof r);
+        r.slot = slots[i]; r.row_kind = kinds[slots[i] / l] & 0x7fu;
+        r.n_terms = n_terms[i]; r.first_term = first[i];
+        std::memcpy(r.value, values.data() + 8 * (size_t)i, 32);
+    }
+    info->n_terms_total = total;
+    info->n_terms_reported = rep;
+    info->n_constraints_distinct = ND;
+    return LIG_OK;
+}
+
+// One rank of a sharded rows job (lig_shard_rows_untouched_slots*, lig_hip.h); att, kinds and alone as above.  The rank runs the one-GPU pass
+// over its LOCAL LINEAR .. QZ rows against its local begin[] in slices of DIAG_UNTOUCHED_ITEMS, writes the slots of the WHOLE trace and keeps
+// its first min(cap, selected) records on the device.  Collective: ONE all-gather of the 32-byte header {n_untouched, n_untouched_nonzero,
+// kept, 0}, then -- with M = max kept -- explain_piece_count(M, P) all-gathers of 40 P bytes per rank.  The host merges the W ascending
+// lists and cuts at cap (untouched_merge): the first cap of all are among each rank's first cap.
+// Scratch: 16 bytes per local LINEAR .. QZ row, 16 per slot of a slice, 40 kept, 32 (W + 1), 40 P (send) + 40 W P (receive) + 40 J W P.
+int lig_internal_shard_untouched_slots(lig_ctx* c, const lig_diag_shard& v, const lig_linear* att, bool alone, const uint8_t* kinds, int nonzero_only, lig_slot_value* out,
+                                       uint64_t cap, lig_untouched_info* info) {
+    static const char* const who = "lig_shard_rows_untouched_slots";
+    const lig_linear_view a = lig_internal_linear_view(att);
+    const uint32_t W = v.world, l = c->l, k = c->k;
+    const uint64_t rows_local = v.grow->size();
+    if (!a.sharded || a.rows_local != rows_local || (uint64_t)a.n_slots != rows_local * l || v.rows_global * (uint64_t)l > (1ull << 32) || v.rank >= W || (alone && W != 1))
+        FAIL(c, LIG_E_STATE, std::string(who) + ": the linear structure is not this rank's share of the sharded trace");
+    // (sources and targets of queued copies: declared before the frame, whose scratch drains the stream when it goes)
+    std::vector<uint4> lrows;
+    for (size_t lr = 0; lr < rows_local; lr++) {
+        const size_t g = (*v.grow)[lr];
+        if (g >= v.rows_global) FAIL(c, LIG_E_STATE, std::string(who) + ": a local row lies outside the trace");
+        if ((kinds[g] & 0x7fu) <= LIG_ROW_QZ) lrows.push_back(make_uint4((uint32_t)lr, kinds[g] & 0x7fu, (uint32_t)g, 0u));
+    }
+    const uint64_t NL = lrows.size();
+    uint64_t header[lig::UNTOUCHED_HEADER_WORDS] = {0, 0, 0, 0}, n_untouched = 0, n_nonzero = 0;
+    std::vector<uint64_t> hdr_all, kept;
+    std::vector<lig_slot_value> recv_all, merged;
+    enum { UPH_LOCAL, UPH_EXCHANGE, UPH_MERGE };
+    DiagShardFrame f(c, v, who, "shard_untouched_slots", {"local", "exchange", "merge"}, alone);
+    hipStream_t s = f.s;
+
+    TRY(f.run([&]() -> int {
+        // 1. the rank's own rows
+        const uint64_t per = std::max<uint64_t>(lig::DIAG_UNTOUCHED_ITEMS / l, 1);      // rows per slice: per * l < 2^32 (rows_global * l <= 2^32)
+        const uint64_t slice_items = std::min(per, NL) * l, keep_cap = std::min<uint64_t>(cap, NL * l);
+        uint4* d_lrows = nullptr; uint64_t *d_flag = nullptr, *d_pos = nullptr, *d_hdr = nullptr, *d_hdr_all = nullptr; lig_slot_value* d_keep = nullptr;
+        TRY(f.upload(d_lrows, lrows.data(), NL));
+        TRY(f.alloc(d_flag, (size_t)slice_items + 1));
+        TRY(f.alloc(d_pos, (size_t)slice_items + 1));
+        TRY(f.alloc(d_keep, keep_cap));
+        TRY(f.alloc(d_hdr_all, (size_t)W * lig::UNTOUCHED_HEADER_WORDS));
+        uint64_t un_mine = 0, nz_mine = 0, kept_mine = 0;
+        for (uint64_t r0 = 0; r0 < NL; r0 += per) {      // (the first slice is the largest: its scan sizes the temp for all of them)
+            const uint32_t items = (uint32_t)(std::min(per, NL - r0) * l);
+            TRY(f.zero(d_flag + items, 1));
+            TRY(f.launch(lig::k_untouched_flag<uint4>, items, d_lrows, (uint32_t)r0, items, a.begin, v.msgs, l, k, f.l_recip, d_flag));
+            uint64_t both = 0;      // the two counts of the slice, packed
+            TRY(f.scan(d_flag, d_pos, items, &both));
+            const uint32_t un = (uint32_t)both, nz = (uint32_t)(both >> 32);
+            if (un > items || nz > un) FAIL(c, LIG_E_STATE, std::string(who) + ": counted more slots than the slice holds");
+            un_mine += un; nz_mine += nz;
+            const uint32_t rep = (uint32_t)std::min<uint64_t>(nonzero_only ? nz : un, keep_cap - kept_mine);
+            if (rep) {
+                TRY(f.launch(lig::k_untouched_compact<uint4>, items, d_flag, d_pos, d_lrows, (uint32_t)r0, items, v.msgs, l, k, f.l_recip, nonzero_only ? 1u : 0u, rep,
+                             d_keep + kept_mine));
+                kept_mine += rep;
+            }
+        }
+        header[0] = un_mine; header[1] = nz_mine; header[2] = kept_mine;
+        TRY(f.upload(d_hdr, header, lig::UNTOUCHED_HEADER_WORDS));
+        TRY(f.mark(UPH_LOCAL));
+        // 2. the counts of every rank
+        TRY(f.all_gather(d_hdr, d_hdr_all, sizeof header, "all_gather(counts of the untouched slots)"));
+        hdr_all.resize((size_t)W * lig::UNTOUCHED_HEADER_WORDS);
+        TRY(f.fetch(hdr_all.data(), d_hdr_all, hdr_all.size()));
+        if (!lig::untouched_header_merge(hdr_all.data(), W, nonzero_only != 0, cap, n_untouched, n_nonzero, kept) || kept[v.rank] != kept_mine)
+            FAIL(c, LIG_E_STATE, std::string(who) + ": a rank's header block is malformed");
+        // 3. the kept records, in pieces of P per rank
+        const lig::ExplainRecordSchedule x = lig::explain_record_schedule(kept, v.slice);
+        if ((uint64_t)W * x.P >= (1ull << 32)) FAIL(c, LIG_E_STATE, std::string(who) + ": a piece of the record exchange exceeds 2^32 records");
+        const size_t WP = (size_t)W * x.P;
+        lig_slot_value *d_send = nullptr, *d_recv = nullptr, *d_all = nullptr;
+        TRY(f.alloc(d_send, x.P));
+        TRY(f.alloc(d_recv, WP));
+        TRY(f.alloc(d_all, (size_t)x.pieces * WP));
+        for (uint64_t j = 0; j < x.pieces; j++) {
+            const uint64_t lo = std::min<uint64_t>(j * x.P, kept_mine), n = std::min<uint64_t>(x.P, kept_mine - lo);
+            if (n) HIP_TRY(c, hipMemcpyAsync(d_send, d_keep + lo, (size_t)n * sizeof(lig_slot_value), hipMemcpyDeviceToDevice, s));
+            if (n < x.P) TRY(f.zero(d_send + n, x.P - n));
+            TRY(f.all_gather(d_send, d_recv, (size_t)x.P * sizeof(lig_slot_value), "all_gather(the untouched slots of every rank)"));
+            HIP_TRY(c, hipMemcpyAsync(d_all + j * WP, d_recv, WP * sizeof(lig_slot_value), hipMemcpyDeviceToDevice, s));
+        }
+        recv_all.resize((size_t)x.pieces * WP);
+        TRY(f.fetch(recv_all.data(), d_all, recv_all.size()));
+        TRY(f.mark(UPH_EXCHANGE));
+        // 4. W ascending lists -> the first cap of all
+        if (!lig::untouched_merge(recv_all.data(), W, x, kept, cap, merged)) FAIL(c, LIG_E_STATE, std::string(who) + ": a rank's record block is malformed");
+        return f.mark(UPH_MERGE);
+    }));
+    if (!merged.empty()) std::memcpy(out, merged.data(), merged.size() * sizeof(lig_slot_value));
+    info->n_untouched = n_untouched;
+    info->n_untouched_nonzero = n_nonzero;
+    info->n_reported = merged.size();
+    return LIG_OK;
 }

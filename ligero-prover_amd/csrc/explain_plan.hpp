@@ -2,9 +2,11 @@
 // the order of the term records, and where every asked constraint's records begin in that order; and of lig_shard_rows_explain /
 // lig_shard_rows_read_slots: the items and right-hand sides of the asked constraints from the caller's term list, the piece schedule of
 // the value exchange; and of lig_shard_rows_explain_attached: the header block of a rank, the schedule of the record all-gathers, the
-// walk over the received records and their merge into the output order.
+// walk over the received records and their merge into the output order; and of lig_shard_rows_explain_slots* /
+// lig_shard_rows_untouched_slots*: which asked slots a rank holds, its header block, the walk over the received items, the merge of the
+// ranks' untouched lists.
 // Host only: nothing but lig_hip.h and the standard library, so that a plain host compiler builds it (tests/cpp/explain_plan_prog.cpp,
-// tests/cpp/shard_explain_plan_prog.cpp, tests/cpp/shard_explain_attached_plan_prog.cpp).
+// tests/cpp/shard_explain_plan_prog.cpp, tests/cpp/shard_explain_attached_plan_prog.cpp, tests/cpp/shard_slots_plan_prog.cpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -170,6 +172,132 @@ inline bool explain_merge(std::vector<ExplainItem>& items, uint64_t n_asked, std
         if (explain_item_less(src[b], src[a])) return false;
         return a < b;
     });
+    return true;
+}
+
+// ---- lig_shard_rows_explain_slots*: the terms through a slot lie in the share of the ONE rank that was dealt its row; that rank collects
+// them from its own slot-major index and every rank receives all of them.
+// The asked slots (of the WHOLE trace, strictly ascending, every one < rows_global * l: the entry has checked them) a rank holds:
+// mine[i] = the index in the asked list, local[i] = the slot in the rank's own rows x l numbering, through local_of (global row -> local
+// row, not_local for a row of another rank).  Local rows are in commit order, so local[] is strictly ascending as well.
+inline void slot_asked_here(const uint32_t* slots, uint64_t n_asked, uint32_t l, const std::vector<uint32_t>& local_of, uint32_t not_local,
+                            std::vector<uint32_t>& mine, std::vector<uint32_t>& local) {
+    mine.clear();
+    local.clear();
+    for (uint64_t a = 0; a < n_asked; a++) {
+        const uint32_t row = slots[a] / l, lr = row < local_of.size() ? local_of[row] : not_local;
+        if (lr == not_local) continue;
+        mine.push_back((uint32_t)a);
+        local.push_back(lr * l + (slots[a] - row * l));
+    }
+}
+// One collected term, as it crosses the ranks: ask = the index of its slot in the asked list, the constraint OF THE WHOLE TRACE, the
+// coefficient index, valid = 1 (a zeroed item, valid = 0, pads a rank's block).
+struct SlotItem { uint32_t ask, constraint, coef, valid; };
+static_assert(sizeof(SlotItem) == 16, "k_slot_collect_shard writes these 16 bytes with one store");
+// The header block of one rank, in 32-bit words: word 0 = m_r, the items the rank collected; words 1 .. 3 zero; then 12 words per asked
+// slot a: {held, n_terms, 0, 0, value[8]} -- held = 1 when the rank was dealt the row of the slot, n_terms = the length of its segment
+// and value = the canonical committed w then, all zero otherwise.  Presence is a field of its own: a committed zero is a value.
+// (constexpr: k_slot_header of diagnose.hip addresses its block with slot_header_at)
+constexpr uint64_t slot_header_words(uint64_t n_asked) { return 4 + 12 * n_asked; }
+constexpr uint64_t slot_header_at(uint64_t a) { return 4 + 12 * a; }
+// The W gathered header blocks (block g from rank g) -> m[g]; holder[a] = the one rank that holds asked slot a, n_terms[a] and
+// value[8 a .. 8 a + 8) as that rank reported them.  false, a malformed block: a non-zero reserved word, held not 0 / 1, a count or a
+// value without held, a slot with two holders or with none, an m_r that is not the sum of the n_terms the rank reported, sum m_r >= 2^32.
+inline bool slot_header_merge(const uint32_t* blocks, uint32_t W, uint64_t n_asked, std::vector<uint64_t>& m, std::vector<uint32_t>& holder,
+                              std::vector<uint32_t>& n_terms, std::vector<uint32_t>& value) {
+    const uint64_t words = slot_header_words(n_asked);
+    m.assign(W, 0);
+    holder.assign(n_asked, W);
+    n_terms.assign(n_asked, 0);
+    value.assign(8 * n_asked, 0);
+    uint64_t total = 0;
+    for (uint32_t g = 0; g < W; g++) {
+        const uint32_t* b = blocks + (size_t)g * words;
+        if (b[1] | b[2] | b[3]) return false;
+        m[g] = b[0];
+        total += b[0];
+        uint64_t sum = 0;
+        for (uint64_t a = 0; a < n_asked; a++) {
+            const uint32_t* h = b + slot_header_at(a);
+            if (h[0] > 1 || h[2] || h[3]) return false;
+            if (!h[0]) {
+                for (int w = 1; w < 12; w++) if (h[w]) return false;
+                continue;
+            }
+            if (holder[a] != W) return false;
+            holder[a] = g; n_terms[a] = h[1];
+            for (int w = 0; w < 8; w++) value[8 * a + w] = h[4 + w];
+            sum += h[1];
+        }
+        if (sum != b[0]) return false;
+    }
+    for (uint64_t a = 0; a < n_asked; a++) if (holder[a] == W) return false;
+    return total < (1ull << 32);
+}
+// The walk over the received items: pieces x W x P of them (the schedule of explain_record_schedule over the m_r: piece major, then rank,
+// then entry).  -> items[off[g] + i] = item i of rank g as an ExplainItem whose `slot` field carries the constraint (explain_order then
+// gives the output order: asked slot, constraint, coefficient index); the invalid tails are dropped.  false, a malformed block: an item
+// before m_r that is not valid, a valid item past m_r, ask >= n_asked, an item for a slot another rank holds, a slot whose items do not
+// add up to the n_terms its holder reported.
+inline bool slot_items_walk(const SlotItem* recv, uint32_t W, const ExplainRecordSchedule& x, const std::vector<uint64_t>& m, uint64_t n_asked,
+                            const std::vector<uint32_t>& holder, const std::vector<uint32_t>& n_terms, std::vector<ExplainItem>& items) {
+    items.assign((size_t)x.off[W], ExplainItem{0, 0, 0});
+    std::vector<uint64_t> seen(n_asked, 0);
+    for (uint64_t j = 0; j < x.pieces; j++)
+        for (uint32_t g = 0; g < W; g++)
+            for (uint64_t r = 0; r < x.P; r++) {
+                const SlotItem& h = recv[(j * W + g) * x.P + r];
+                const uint64_t i = j * x.P + r;
+                if (i >= m[g]) { if (h.valid) return false; continue; }
+                if (h.valid != 1 || h.ask >= n_asked || holder[h.ask] != g) return false;
+                seen[h.ask]++;
+                items[(size_t)(x.off[g] + i)] = ExplainItem{h.ask, h.constraint, h.coef};
+            }
+    for (uint64_t a = 0; a < n_asked; a++) if (seen[a] != n_terms[a]) return false;
+    return true;
+}
+
+// ---- lig_shard_rows_untouched_slots*: every rank lists the untouched slots of its own rows (slots of the WHOLE trace, ascending) and keeps
+// its first min(cap, selected) records; the global first `cap` are among them, so merging the W lists and cutting at `cap` is exact.
+// The header block of one rank: {n_untouched, n_untouched_nonzero, kept, 0} as 64-bit words.
+static constexpr uint64_t UNTOUCHED_HEADER_WORDS = 4;
+// The W gathered header blocks -> the two sums and kept[g].  false, a malformed block: a non-zero reserved word, more non-zero than
+// untouched slots, kept != min(cap, the selected count of the rank).
+inline bool untouched_header_merge(const uint64_t* blocks, uint32_t W, bool nonzero_only, uint64_t cap, uint64_t& n_untouched, uint64_t& n_nonzero,
+                                   std::vector<uint64_t>& kept) {
+    kept.assign(W, 0);
+    n_untouched = n_nonzero = 0;
+    for (uint32_t g = 0; g < W; g++) {
+        const uint64_t* b = blocks + (size_t)g * UNTOUCHED_HEADER_WORDS;
+        if (b[3] || b[1] > b[0] || b[0] >= (1ull << 32)) return false;
+        if (b[2] != std::min<uint64_t>(cap, nonzero_only ? b[1] : b[0])) return false;
+        n_untouched += b[0]; n_nonzero += b[1];
+        kept[g] = b[2];
+    }
+    return true;
+}
+// The received records: pieces x W x P of them (explain_record_schedule over kept[]), record i of rank g in piece i / P, entry i % P of
+// its block.  -> the first `cap` of all of them in ascending slot order.  false: a rank's list is not strictly ascending, or two ranks
+// list one slot (a row has one owner).
+inline bool untouched_merge(const lig_slot_value* recv, uint32_t W, const ExplainRecordSchedule& x, const std::vector<uint64_t>& kept, uint64_t cap,
+                            std::vector<lig_slot_value>& out) {
+    out.clear();
+    const auto at = [&](uint32_t g, uint64_t i) -> const lig_slot_value& { return recv[((i / x.P) * W + g) * x.P + i % x.P]; };
+    for (uint32_t g = 0; g < W; g++)
+        for (uint64_t i = 1; i < kept[g]; i++) if (at(g, i).slot <= at(g, i - 1).slot) return false;
+    std::vector<uint64_t> next(W, 0);
+    uint64_t last = ~0ull;
+    while (out.size() < cap) {
+        uint32_t best = W;
+        for (uint32_t g = 0; g < W; g++)
+            if (next[g] < kept[g] && (best == W || at(g, next[g]).slot < at(best, next[best]).slot)) best = g;
+        if (best == W) break;
+        const lig_slot_value& r = at(best, next[best]++);
+        if (last != ~0ull && r.slot <= last) return false;
+        last = r.slot;
+        out.push_back(r);
+    }
     return true;
 }
 }  // namespace lig

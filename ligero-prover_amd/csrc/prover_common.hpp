@@ -532,6 +532,13 @@ int lig_internal_shard_read_slots(lig_ctx* c, const lig_diag_shard& v, const uin
 // without the forced exchange -- the same passes without a collective.
 int lig_internal_shard_explain_attached(lig_ctx* c, const lig_diag_shard& v, const lig_linear* att, bool alone, const uint32_t* asked, uint64_t n_asked,
                                         lig_explain_constraint* con_out, lig_explain_term* terms_out, uint64_t term_cap, lig_explain_info* info);
+// lig_shard_rows_explain_slots* / lig_shard_rows_untouched_slots*: the constraints through the asked slots (of the WHOLE trace, checked and
+// strictly ascending, n_asked > 0) and the untouched LINEAR .. QZ slots from the rank's share `att` (sharded: the one attached to the shard,
+// or a temporary one made from the caller's term list); kinds: one per committed row of the whole trace; alone as above.
+int lig_internal_shard_explain_slots(lig_ctx* c, const lig_diag_shard& v, const lig_linear* att, bool alone, const uint8_t* kinds, const uint32_t* slots, uint64_t n_asked,
+                                     lig_slot_record* slot_out, lig_slot_term* terms_out, uint64_t term_cap, lig_slot_info* info);
+int lig_internal_shard_untouched_slots(lig_ctx* c, const lig_diag_shard& v, const lig_linear* att, bool alone, const uint8_t* kinds, int nonzero_only, lig_slot_value* out,
+                                       uint64_t cap, lig_untouched_info* info);
 
 // the batch program of a job on the device: committed rows are written to rows_out in program order (prover.hip)
 int lig_run_batch_program(lig_ctx* c, const lig_synth_job& job, fr* rows_out);

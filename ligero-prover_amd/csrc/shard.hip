@@ -1074,6 +1074,92 @@ int lig_shard_rows_read_slots(lig_shard* S, const uint32_t* slots, uint64_t n_sl
     return lig_internal_shard_read_slots(c, v, slots, n_slots, values);
 }
 
+// lig_rows_explain_slots* / lig_rows_untouched_slots* on a rows shard (diagnose.hip): collective, every rank obtains the bytes of the one-GPU
+// call on the whole trace.  Both read the slot-major index of the rank's share: the one attached to the shard (att), or a temporary one made
+// from sys with lig_internal_linear_create_shard and destroyed before the call returns -- one code path; what is attached is then neither
+// read nor modified.  Window, state checks and refusals as lig_shard_rows_explain_attached: decided here, on the host, identically on every
+// rank, before anything is launched and before any collective (args_ok: the entry's own check of its lists against the rows of the whole
+// trace).  One rank alone runs the same passes over its compactly numbered share without a collective.
+using ShardSlotsRun = std::function<int(lig_ctx*, const lig_diag_shard&, const lig_linear*, bool, const uint8_t*)>;
+static int shard_slots_call(const char* which, const char* debug_name, bool att, lig_shard* S, const lig_linear_system* sys,
+                            const std::function<bool(uint64_t, uint32_t)>& args_ok, bool nothing_to_do, const ShardSlotsRun& run) {
+    SHARD_COMMON;
+    (void)n;
+    CHECK_CTX(c);
+    const std::string w(which);
+    if (S->poisoned) FAIL(c, LIG_E_STATE, w + ": the shard is poisoned (work queued behind a failed collective never drained): destroy it");
+    if (!S->from_rows) FAIL(c, LIG_E_STATE, w + ": not a rows shard (lig_shard_rows_begin)");
+    if (!S->diag_ok) FAIL(c, LIG_E_STATE, w + ": no committed matrix (between lig_shard_rows_commit and the next lig_shard_rows_restart)");
+    if (att && !S->linear) FAIL(c, LIG_E_STATE, w + ": no linear system is set (lig_shard_rows_set_linear)");
+    if (!att && !sys) FAIL(c, LIG_E_ARG, w + ": null linear system");
+    const std::vector<uint8_t> kinds = kinds_of(S->rows);
+    if (!att && lig_linear_check(sys, kinds.data(), R, l) != LIG_OK) FAIL(c, LIG_E_ARG, w + ": linear system rejected by lig_linear_check");
+    if (!args_ok(R, l)) FAIL(c, LIG_E_ARG, w + ": the asked slots must be strictly ascending and below rows * l of the whole trace");
+    if (nothing_to_do) return LIG_OK;
+    ShardDebugScope dbg(S, debug_name, nullptr);
+    SHARD_DIAG_VIEW(v);
+    const bool alone = W == 1 && !S->exchange_even_alone;
+    if (att) return run(c, v, S->linear, alone, kinds.data());
+    lig_linear* tmp = nullptr;
+    TRY(lig_internal_linear_create_shard(c, sys, kinds.data(), S->R, S->grow, S->rank, S->world, &tmp));
+    const int rc = run(c, v, tmp, alone, kinds.data());
+    if (rc != LIG_OK && S->poisoned) return rc;      // kernels that never drained may still read the temporary share: it outlives the call
+    const std::string why = c->err;
+    lig_internal_linear_destroy(tmp);
+    c->err = why;
+    return rc;
+}
+static int shard_explain_slots(const char* which, bool att, lig_shard* S, const lig_linear_system* sys, const uint32_t* slots, uint64_t n_asked, lig_slot_record* slot_out,
+                               lig_slot_term* terms_out, uint64_t term_cap, lig_slot_info* info) {
+    if (!S || !info || info->struct_bytes < sizeof(lig_slot_info)) return LIG_E_ARG;
+    if ((n_asked && (!slot_out || !slots)) || (term_cap && !terms_out)) return LIG_E_ARG;
+    const auto t_begin = clk::now();
+    const uint32_t struct_bytes = info->struct_bytes;
+    const auto args_ok = [&](uint64_t rows, uint32_t l) -> bool {
+        if (!lig::explain_slots_ok(slots, n_asked, rows, l)) return false;
+        for (uint64_t i = 1; i < n_asked; i++) if (slots[i] <= slots[i - 1]) return false;
+        return true;
+    };
+    TRY(shard_slots_call(which, att ? "explain_slots_attached" : "explain_slots", att, S, sys, args_ok, !n_asked,
+                         [&](lig_ctx* c, const lig_diag_shard& v, const lig_linear* L, bool alone, const uint8_t* kinds) -> int {
+        std::memset(info, 0, sizeof *info);
+        info->struct_bytes = struct_bytes;
+        return lig_internal_shard_explain_slots(c, v, L, alone, kinds, slots, n_asked, slot_out, terms_out, term_cap, info);
+    }));
+    if (!n_asked) { std::memset(info, 0, sizeof *info); info->struct_bytes = struct_bytes; }
+    info->ms_total = ms_since(t_begin);
+    return LIG_OK;
+}
+static int shard_untouched_slots(const char* which, bool att, lig_shard* S, const lig_linear_system* sys, int nonzero_only, lig_slot_value* out, uint64_t cap,
+                                 lig_untouched_info* info) {
+    if (!S || !info || info->struct_bytes < sizeof(lig_untouched_info)) return LIG_E_ARG;
+    if (cap && !out) return LIG_E_ARG;
+    const auto t_begin = clk::now();
+    const uint32_t struct_bytes = info->struct_bytes;
+    TRY(shard_slots_call(which, att ? "untouched_slots_attached" : "untouched_slots", att, S, sys, [](uint64_t, uint32_t) -> bool { return true; }, false,
+                         [&](lig_ctx* c, const lig_diag_shard& v, const lig_linear* L, bool alone, const uint8_t* kinds) -> int {
+        std::memset(info, 0, sizeof *info);
+        info->struct_bytes = struct_bytes;
+        return lig_internal_shard_untouched_slots(c, v, L, alone, kinds, nonzero_only, out, cap, info);
+    }));
+    info->ms_total = ms_since(t_begin);
+    return LIG_OK;
+}
+int lig_shard_rows_explain_slots_attached(lig_shard* S, const uint32_t* slots, uint64_t n_asked, lig_slot_record* slot_out, lig_slot_term* terms_out, uint64_t term_cap,
+                                          lig_slot_info* info) {
+    return shard_explain_slots("lig_shard_rows_explain_slots_attached", true, S, nullptr, slots, n_asked, slot_out, terms_out, term_cap, info);
+}
+int lig_shard_rows_explain_slots(lig_shard* S, const lig_linear_system* sys, const uint32_t* slots, uint64_t n_asked, lig_slot_record* slot_out, lig_slot_term* terms_out,
+                                 uint64_t term_cap, lig_slot_info* info) {
+    return shard_explain_slots("lig_shard_rows_explain_slots", false, S, sys, slots, n_asked, slot_out, terms_out, term_cap, info);
+}
+int lig_shard_rows_untouched_slots_attached(lig_shard* S, int nonzero_only, lig_slot_value* out, uint64_t cap, lig_untouched_info* info) {
+    return shard_untouched_slots("lig_shard_rows_untouched_slots_attached", true, S, nullptr, nonzero_only, out, cap, info);
+}
+int lig_shard_rows_untouched_slots(lig_shard* S, const lig_linear_system* sys, int nonzero_only, lig_slot_value* out, uint64_t cap, lig_untouched_info* info) {
+    return shard_untouched_slots("lig_shard_rows_untouched_slots", false, S, sys, nonzero_only, out, cap, info);
+}
+
 // The sparse linear system of the WHOLE trace on a rows shard: every rank passes the same system (a collective contract, like the kinds) and
 // keeps its share -- the terms of the rows it was dealt, the constraints those need, its slice of the right-hand sides (linear.hip).
 int lig_shard_rows_set_linear(lig_shard* S, const lig_linear_system* sys) {
