@@ -662,6 +662,56 @@ int lig_rows_untouched_slots_attached(lig_trace *trace, int nonzero_only, lig_sl
 int lig_rows_untouched_slots(lig_trace *trace, const lig_linear_system *sys, int nonzero_only, lig_slot_value *out, uint64_t cap,
                              lig_untouched_info *info);
 
+/* ---- derived slots: the outputs of linear constraints formed on the device  (csrc/derive.hip, csrc/derive_plan.hpp)
+ * Upstream every backend.eval(expr) (include/zkp/backend/core.hpp:311) creates a NEW witness whose value is a linear expression of older
+ * witnesses, tied to them by one linear constraint in which it has coefficient -1.  A caller that recorded its term list holds that
+ * constraint already; with the entries below it no longer evaluates the expression per proof, and the slot needs no bytes on the link (a
+ * bit row whose only wide slots are eval outputs stays a pure LIG_ELEM_BIT row, without records).  The linear counterpart of
+ * LIG_ELEM_PRODUCT.
+ *   A derived slot t with DEFINING constraint c of `sys`, sum_j a_j * w[s_j] = b_c: t occurs exactly once among the terms of c, with
+ *   coefficient index LIG_COEF_ONE or LIG_COEF_NEG_ONE, and its committed value is
+ *       w[t] = b_c - sum_{j != t} a_j * w[s_j]   (coefficient +1)        w[t] = sum_{j != t} a_j * w[s_j] - b_c   (coefficient -1)
+ *   canonical, mod p.  Whatever the caller's row carries at t is IGNORED (the caller writes 0 there, as for the column of a mixed-row
+ *   record).  The other terms may lie on any LINEAR / QX / QY / QZ row of the trace: rows behind t's row, LIG_ELEM_PRODUCT rows, other
+ *   derived slots.  A slot derived from derived slots belongs to a later WAVE: wave = 1 + the largest wave among its derived terms (0 for
+ *   a slot that is not derived), computed on the host; at most LIG_DERIVE_MAX_WAVES.
+ * lig_derived_check: host only, no context.  lig_linear_check(sys, kinds, rows, l) first; then LIG_E_ARG for: a slot listed twice; a
+ * constraint >= n_constraints; a target absent from its constraint or present twice; a target whose coefficient is a table index (even
+ * one whose value is 1); a cycle; more than LIG_DERIVE_MAX_WAVES waves; a target on a LIG_ELEM_PRODUCT row; a target that is an operand
+ * slot of a LIG_ELEM_PRODUCT row -- column i of the QX or QY row directly in front of one: the product is formed from the PACKED operand
+ * rows and would not see the derived value.  elem_bytes: as in lig_rows_job (one per row), NULL: no row is derived.  d may be in any
+ * order; n == 0 is accepted (no wave).  wave_out (n entries, or NULL) <- the wave of d[i]; *info (or NULL; struct_bytes set by the
+ * caller) <- n_slots = n, n_terms = the OTHER terms of all defining constraints, n_waves.
+ * lig_rows_set_derived: runs that check against the trace's kinds and widths (LIG_E_ARG, nothing launched, the previous list stays in
+ * force and the trace usable), then COPIES what it needs before it returns: the terms of the n defining constraints, their right-hand-side
+ * table entries, and the table values of sys->coefs AS PASSED (converted to Montgomery form on the device once per call); the rest of sys
+ * is not kept.  Any time after lig_rows_begin; the list applies from the next lig_rows_commit on and survives lig_rows_restart; a second
+ * call replaces it; d == NULL or n == 0 removes it.  LIG_E_STATE for a lig_synth_prepare trace.  It is independent of what is attached for
+ * proving: it works with lig_rows_set_linear, with lig_rows_attach_linear and with caller-supplied randomness rows.
+ * lig_rows_set_linear_values does NOT reach it: for other right-hand sides call lig_rows_set_derived again with the new table.
+ *   WHERE  in lig_rows_commit, on the encode stream, after every row of the trace has been expanded (derived product rows and the records
+ *          of mixed rows included) and before the first encode: one launch per wave, written into the matrix THIS commit encodes (after a
+ *          lig_rows_restart issued between commit and prove that is the second matrix); the pads are not touched (derived slots are data
+ *          slots < l).  The second attempt of a commit whose upload timed out runs the pass again.  HOST rows that arrive chunk by chunk:
+ *          with a list set, the arrival wait, expansion and pads of ALL chunks are queued first, then the waves, then the encodes -- the
+ *          upload / encode overlap is given up for such a trace, and only for such a trace (LIG_SHA_GATE=2 is ignored while a list is
+ *          set).  Without a list stage 1 queues exactly what it queued before.
+ *   READERS of the committed matrix see the derived values: lig_rows_diagnose*, lig_rows_explain*, lig_rows_read_slots,
+ *          lig_rows_explain_slots*.  The verifier side ignores the list, as it ignores msgs.
+ *   The prover's valid_linear CANNOT fail on a defining constraint (as valid_quad is vacuous for a LIG_ELEM_PRODUCT triple): a caller whose
+ *   own evaluation would have been wrong now proves a different w, and the OTHER constraints on that slot fail instead.
+ *   Deterministic: one lane (a workgroup with a fixed summation tree for a constraint with more than 64 other terms) per target, no
+ *   atomic on a field element: the same bytes on every run.
+ * Not done: the sharded entry (no lig_shard_* call takes a list).  Not done: per-chunk reach, so that a chunk waits only for the rows its
+ * derived slots read; derived operands of LIG_ELEM_PRODUCT rows.
+ * The new structs version themselves with struct_bytes; they are not part of lig_abi_sizes (LIG_ABI_STRUCTS stays 6). */
+enum { LIG_DERIVE_MAX_WAVES = 16 };
+typedef struct { uint32_t slot, constraint; } lig_derived_slot;                                                     /* 8 bytes */
+typedef struct { uint32_t struct_bytes, reserved; uint64_t n_slots, n_terms; uint32_t n_waves, reserved2; } lig_derived_info;   /* 32 bytes */
+int lig_derived_check(const lig_linear_system *sys, const uint8_t *kinds, uint64_t rows, uint32_t l, const uint8_t *elem_bytes /* NULL ok */,
+                      const lig_derived_slot *d, uint64_t n, uint32_t *wave_out /* n entries or NULL */, lig_derived_info *info /* NULL ok */);
+int lig_rows_set_derived(lig_trace *trace, const lig_linear_system *sys, const lig_derived_slot *d, uint64_t n, lig_derived_info *info /* NULL ok */);
+
 /* ==== proof file framing (src/webgpu_prover.cpp:437-457 writes gzip(level 6) of the serialized envelope with
  * Boost.iostreams; src/webgpu_verifier.cpp:249-253 reads it back).  Host-only helpers on zlib: the output is a standard
  * gzip member that any gzip reader (the reference's gzip_decompressor included) accepts; compressed BYTES depend on the
@@ -1014,7 +1064,8 @@ void lig_abi_sizes(uint32_t out[LIG_ABI_STRUCTS]);
 int lig_profile_enable(lig_ctx *ctx, int on);
 int lig_profile_read(lig_ctx *ctx, uint64_t *launches, uint64_t *rows, double *total_ms);
 /* the same restricted to the bracketed launches of exactly rows_in_launch rows (512 = the full chunks: what a rocprofv3 kernel table
- * lists per launch size) */
+ * lists per launch size).  rows_in_launch = 0: the derive waves of lig_rows_commit on a trace with a list of derived slots
+ * (lig_rows_set_derived), one bracket per commit around all its waves -- with such a list set, lig_profile_read's sum includes them. */
 int lig_profile_read_launches(lig_ctx *ctx, uint32_t rows_in_launch, uint64_t *launches, double *total_ms);
 
 #ifdef __cplusplus

@@ -143,6 +143,7 @@ public:
     void shard_over(uint32_t rank, uint32_t world, const lig_comm* comm) {
         if (pass_ != 1 || !comm || !world || rank >= world) throw std::invalid_argument("hip_row_batcher::shard_over");
         if (program_) throw std::logic_error("hip_row_batcher::shard_over: a prepared linear program is not for a sharded batcher (set_linear_system)");
+        if (!derived_.empty()) throw std::logic_error("hip_row_batcher::shard_over: derived slots are not for a sharded batcher (set_derived_slots)");
         if (shard_) { lig_shard_destroy(shard_); shard_ = nullptr; linear_on_trace_ = false; }      // another deal: nothing of the old shard is reused
         sharded_ = true; rank_ = rank; world_ = world; comm_ = *comm;
     }
@@ -190,6 +191,21 @@ public:
         values_.assign(coefs, coefs + (coefs ? n_coefs * 32 : 0));
         values_on_trace_ = false;
         if (pass_ == 2 && linear_on_trace_) apply_values();      // (pass 1: with the attach / after the restart of the next commit())
+    }
+
+    // Derived slots (lig_rows_set_derived): the outputs of the guest's eval() calls.  d[i] = (slot, its
+    // DEFINING constraint in `sys`): the library forms w[slot] from the other terms of that constraint in commit(), whatever the row
+    // carries there (the driver writes 0, so a bit row stays a bit row).  In pass 1, before commit(); sys and d are copied (sys need
+    // not be the system of set_linear_system); kept across reset() for the next proof of the same shape, where the list stays
+    // resident on the trace -- for other right-hand sides call it again; n == 0 removes the list.  Not with shard_over(): the sharded
+    // entry takes no list.
+    void set_derived_slots(const lig_linear_system& sys, const lig_derived_slot* d, uint64_t n) {
+        if (pass_ != 1) throw std::logic_error("hip_row_batcher::set_derived_slots after commit (reset() first)");
+        if (sharded_) throw std::logic_error("hip_row_batcher::set_derived_slots: not on a sharded batcher");
+        if (n && !d) throw std::invalid_argument("hip_row_batcher::set_derived_slots: null list");
+        if (n) derived_sys_.assign(sys); else derived_sys_.clear();
+        derived_.assign(d, d + n);
+        derived_on_trace_ = false;
     }
 
     // ---- the callbacks of nonbatch_context_base (nonbatch_context.hpp:78-86).  `rand` rows are null in pass 1.
@@ -279,11 +295,15 @@ public:
         }
         if (trace_) {                                      // the next proof of the same program: every device buffer is reused
             if (same_shape(job)) check(lig_rows_restart(trace_, job.msgs, 0), "lig_rows_restart");
-            else { lig_trace_destroy(trace_); trace_ = nullptr; linear_on_trace_ = values_on_trace_ = false; }
+            else { lig_trace_destroy(trace_); trace_ = nullptr; linear_on_trace_ = values_on_trace_ = false; derived_on_trace_ = derived_.empty(); }
         }
         if (!trace_) check(lig_rows_begin(ctx_, &job, &trace_), "lig_rows_begin");
         shape_kinds_ = kinds_; shape_widths_ = widths; shape_wide_ = wide; shape_meta_ = meta_;
         apply_linear();                                   // (a trace that was restarted keeps the structure it has)
+        if (!derived_on_trace_) {                         // (... and the list of derived slots)
+            check(lig_rows_set_derived(trace_, derived_.empty() ? nullptr : derived_sys_.get(), derived_.empty() ? nullptr : derived_.data(), derived_.size(), nullptr), "lig_rows_set_derived");
+            derived_on_trace_ = true;
+        }
         check(lig_rows_commit(trace_, root, stage1_seed), "lig_rows_commit");
         for (auto& kd : kinds_) kd &= 0x7f;               // (pass 2 compares plain kinds)
         begin_pass2(kinds_.size());
@@ -745,6 +765,9 @@ private:
     hip_linear_system_copy linear_;
     const lig_linear_program* program_ = nullptr;         // set_linear_program: the caller's object (linear_ is then unset)
     std::vector<uint8_t> values_;                         // set_linear_values
+    hip_linear_system_copy derived_sys_;                  // set_derived_slots: the system the defining constraints are in
+    std::vector<lig_derived_slot> derived_;
+    bool derived_on_trace_ = true;                        // the trace holds the list above (no trace, no list: nothing to do)
     bool values_set_ = false;
     bool linear_on_trace_ = false;                        // trace_ holds linear_ / program_ (it stays resident across lig_rows_restart)
     bool values_on_trace_ = false;                        // ... and the values of values_ (or, !values_set_, its own table)

@@ -48,6 +48,7 @@ EXPORTS = [
     "lig_shard_rows_explain", "lig_shard_rows_read_slots", "lig_shard_rows_explain_attached",
     "lig_shard_rows_set_linear_values", "lig_shard_rows_diagnose_attached",
     "lig_shard_rows_explain_slots", "lig_shard_rows_explain_slots_attached", "lig_shard_rows_untouched_slots", "lig_shard_rows_untouched_slots_attached",
+    "lig_derived_check", "lig_rows_set_derived",
 ]
 
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
@@ -58,6 +59,7 @@ ROWS_JOB_WIDE = 1          # lig_rows_job.reserved: the struct has wide_per_row 
 WIDE_RECORD_BYTES = 36     # lig_rows_job.wide_per_row: a record of a mixed row, uint32 column + 8 uint32 limbs (LIG_WIDE_RECORD_BYTES)
 ARG_I64, ARG_STR, ARG_HEX = 0, 1, 2
 COEF_ONE, COEF_NEG_ONE = 0xFFFFFFFF, 0xFFFFFFFE      # lig_lin_term.coef values that need no table entry (LIG_COEF_ONE / LIG_COEF_NEG_ONE)
+DERIVE_MAX_WAVES = 16      # lig_rows_set_derived: a derived slot may read derived slots of at most this many earlier waves (LIG_DERIVE_MAX_WAVES)
 
 
 class VerifyInfo(C.Structure):
@@ -150,6 +152,35 @@ def linear_check(system, kinds, l):
     """lig_linear_check (host only) -> the return code: 0, or LIG_E_ARG (-1) for a system that breaks a rule of the format"""
     kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
     return load_library().lig_linear_check(C.byref(system), kinds.ctypes.data if len(kinds) else None, len(kinds), l)
+
+
+class DerivedInfo(C.Structure):
+    """lig_derived_info: n_slots = the listed slots, n_terms = the other terms of all defining constraints, n_waves"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("reserved", C.c_uint32), ("n_slots", C.c_uint64), ("n_terms", C.c_uint64),
+                ("n_waves", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
+def _derived_pairs(pairs):
+    """(slot, defining constraint) pairs -> the (n, 2) uint32 array of lig_derived_slot"""
+    d = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    return d
+
+
+def derived_check(system, kinds, l, pairs, elem_bytes=None):
+    """lig_derived_check (host only): pairs = (slot, defining constraint) of every derived slot, any order; elem_bytes: the widths of the
+    rows job or None -> the wave of every pair (uint32 array, 1 = reads no derived slot); LigError(-1) for a list the rules refuse"""
+    kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+    d = _derived_pairs(pairs)
+    eb = np.ascontiguousarray(elem_bytes, dtype=np.uint8) if elem_bytes is not None else None
+    if eb is not None and len(eb) != len(kinds):
+        raise ValueError("derived_check: %d widths for %d rows" % (len(eb), len(kinds)))
+    waves = np.zeros(len(d), dtype=np.uint32)
+    rc = load_library().lig_derived_check(C.byref(system), kinds.ctypes.data if len(kinds) else None, len(kinds), l,
+                                          eb.ctypes.data if eb is not None and len(eb) else None, d.ctypes.data if len(d) else None, len(d),
+                                          waves.ctypes.data if len(d) else None, None)
+    if rc != 0:
+        raise LigError("lig_derived_check failed (%d)" % rc)
+    return waves
 
 
 def linear_shard_count(system, kinds, l, rank, world):
@@ -388,6 +419,8 @@ def load_library():
     L.lig_profile_read_launches.argtypes = [vp, u32, C.POINTER(u64), C.POINTER(C.c_double)]
     L.lig_linear_check.argtypes = [C.POINTER(LinearSystem), vp, u64, u32]
     L.lig_linear_form.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, vp, vp, vp]
+    L.lig_derived_check.argtypes = [C.POINTER(LinearSystem), vp, u64, u32, vp, vp, u64, vp, C.POINTER(DerivedInfo)]
+    L.lig_rows_set_derived.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, C.POINTER(DerivedInfo)]
     L.lig_rows_set_linear.argtypes = [vp, C.POINTER(LinearSystem)]
     L.lig_rows_verify_set_linear.argtypes = [vp, C.POINTER(LinearSystem)]
     L.lig_shard_rows_set_linear.argtypes = [vp, C.POINTER(LinearSystem)]
@@ -1089,6 +1122,16 @@ class Context:
     def rows_set_linear(self, trace, system):
         """lig_rows_set_linear: rows_prove(trace, None, None) then forms randomness matrix and constant itself; None removes it"""
         self.check(self.L.lig_rows_set_linear(trace, C.byref(system) if system is not None else None))
+
+    def rows_set_derived(self, trace, system, pairs):
+        """lig_rows_set_derived: pairs = (slot, defining constraint of `system`) of the slots the library forms itself from the next
+        rows_commit on (whatever the rows carry there is ignored); None or an empty list removes the list -> DerivedInfo"""
+        info = DerivedInfo()
+        info.struct_bytes = C.sizeof(DerivedInfo)
+        d = _derived_pairs(pairs) if pairs is not None else np.zeros((0, 2), dtype=np.uint32)
+        self.check(self.L.lig_rows_set_derived(trace, C.byref(system) if system is not None else None, d.ctypes.data if len(d) else None, len(d),
+                                               C.byref(info)))
+        return info
 
     def rows_verify_set_linear(self, vtrace, system):
         self.check(self.L.lig_rows_verify_set_linear(vtrace, C.byref(system) if system is not None else None))

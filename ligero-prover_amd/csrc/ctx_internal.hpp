@@ -101,6 +101,8 @@ int lig_internal_encode_2k_rows(lig_ctx* c, void* buf, size_t rows, hipStream_t 
 int lig_internal_encode_generic(lig_ctx* c, void* buf, hipStream_t on = nullptr);
 // dst (device) <- src (host, any memory), `bytes` a multiple of 4, enqueued on `st`; src may be reused as soon as this returns
 int lig_internal_upload_small(lig_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st);
+// lig_profile_*: the next pair of timing events, booked as a launch of `rows` rows (0: the derive waves of stage 1); both NULL while profiling is off
+int lig_internal_profile_bracket(lig_ctx* c, uint32_t rows, hipEvent_t* e0, hipEvent_t* e1);
 // host_pinned (hipHostMalloc'ed, 16-byte aligned) <- src (device), enqueued on `st` as a copy kernel (no DMA engine); the data is
 // visible to the host once work queued behind it on `st` has been waited for (event / stream synchronize)
 int lig_internal_download(lig_ctx* c, void* host_pinned, const void* src, size_t bytes, hipStream_t st);

@@ -1,0 +1,131 @@
+// derive.hip -- derived slots: the outputs of linear constraints formed on the device (lig_derived_check, lig_rows_set_derived; lig_hip.h).
+//
+// Upstream every backend.eval(expr) creates a new witness w[t] that one linear constraint ties to older witnesses, with coefficient -1
+// (include/zkp/backend/core.hpp:311).  A caller that has recorded its term list marks that constraint as the DEFINING constraint of t; the
+// library then forms w[t] from the other terms of the constraint instead of reading it from the caller's row.  The linear counterpart of
+// k_expand_product (expand.hip).
+//
+//   host    derive_plan.hpp checks the list and orders it in waves (a slot derived from derived slots belongs to a later wave); the program
+//           -- targets, their other terms, the coefficient table -- is copied to the device once per lig_rows_set_derived, the table
+//           converted to Montgomery form there (k_lin_coefs_mont, linear.hip)
+//   device  k_derive_wave, one launch per wave on the encode stream of stage 1 (prover.hip), after every row of the trace is expanded and
+//           before the first encode:
+//             light targets (at most DERIVE_LANE_MAX = 64 other terms): one lane each walks its terms over the expanded message matrix --
+//               the walk of k_diag_lin (lin_eval.hpp, shared, not copied); the specials +1 / -1 take no multiplication
+//             heavy targets (more terms): one workgroup each strides the terms and adds the lanes' sums with the fixed LDS tree of
+//               k_diag_lin_heavy
+//           then b - sum or sum - b, canonical, two 16-byte stores into the matrix.  A target reads only slots that are not derived or
+//           belong to an earlier wave (launch order on one stream), never a slot written by its own launch.  No atomic on a field
+//           element: the same bytes on every run.  Every index the kernel uses was checked on the host (lig_linear_check, plan_derived).
+#include "derive_plan.hpp"
+#include "lin_eval.hpp"
+#include "prover_common.hpp"
+
+namespace lig {
+static constexpr uint32_t DERIVE_MAX_BLOCKS = COEFS_MAX_BLOCKS;      // block cap of each of the two parts of a wave's grid
+
+static __device__ __forceinline__ void derive_store(const DeriveTarget tg, fr sum, fr* msgs, uint32_t l, uint32_t k, uint64_t l_recip,
+                                                    const fr* __restrict__ coef_mont) {
+    const fr b = tg.rhs == DERIVE_RHS_ZERO ? fr_zero() : diag_coef_value(tg.rhs, coef_mont);
+    const uint32_t row = diag_div(tg.slot, l_recip), col = tg.slot - row * l;
+    fr_store(msgs + (size_t)row * k + col, tg.negate ? fr_sub(sum, b) : fr_sub(b, sum));
+}
+// workgroups [0, light_blocks): lane -> light target (grid-stride); the others: workgroup -> heavy target n_light + h (block-stride)
+__global__ void __launch_bounds__(LIN_WG) k_derive_wave(const DeriveTarget* __restrict__ targets, uint32_t n_light, uint32_t n_heavy, uint32_t light_blocks,
+                                                        const lig_lin_term* __restrict__ terms, fr* msgs, uint32_t l, uint32_t k, uint64_t l_recip,
+                                                        const fr* __restrict__ coef_mont) {
+    __shared__ fr sh[LIN_WG];
+    if (blockIdx.x < light_blocks) {
+        for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n_light; i += (uint64_t)light_blocks * LIN_WG) {
+            const DeriveTarget tg = targets[i];
+            derive_store(tg, diag_sum_lane(tg.begin, tg.end, terms, msgs, l, k, l_recip, coef_mont, DiagAllRows{}), msgs, l, k, l_recip, coef_mont);
+        }
+        return;
+    }
+    const uint32_t heavy_blocks = gridDim.x - light_blocks;
+    for (uint32_t h = blockIdx.x - light_blocks; h < n_heavy; h += heavy_blocks) {      // (uniform over the workgroup: the barriers of lin_block_sum are reached by all lanes)
+        const DeriveTarget tg = targets[n_light + h];
+        const fr sum = diag_sum_block(tg.begin, tg.end, terms, msgs, l, k, l_recip, coef_mont, DiagAllRows{}, sh);
+        if (threadIdx.x == 0) derive_store(tg, sum, msgs, l, k, l_recip, coef_mont);
+        __syncthreads();                                                  // sh is reused by the next target
+    }
+}
+}  // namespace lig
+
+// the program of one lig_rows_set_derived on the device; nothing writes it after the call has returned
+struct lig_derive {
+    int device = 0;
+    std::vector<uint32_t> wave_begin, wave_light;
+    lig::DeriveTarget* targets = nullptr;
+    lig_lin_term* terms = nullptr;
+    fr* coef_mont = nullptr;
+};
+
+static void derived_info_fill(lig_derived_info* info, const lig::DerivePlan& p, uint64_t n) {
+    if (!info) return;
+    const uint32_t struct_bytes = info->struct_bytes;
+    std::memset(info, 0, sizeof *info);
+    info->struct_bytes = struct_bytes;
+    info->n_slots = n;
+    info->n_terms = p.terms.size();
+    info->n_waves = p.n_waves;
+}
+
+extern "C" int lig_derived_check(const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, uint32_t l, const uint8_t* elem_bytes,
+                                 const lig_derived_slot* d, uint64_t n, uint32_t* wave_out, lig_derived_info* info) {
+    if (info && info->struct_bytes < sizeof(lig_derived_info)) return LIG_E_ARG;
+    if (lig_linear_check(sys, kinds, rows, l) != LIG_OK) return LIG_E_ARG;
+    lig::DerivePlan p;
+    if (lig::plan_derived(*sys, kinds, rows, l, elem_bytes, d, n, p)) return LIG_E_ARG;
+    if (wave_out) for (uint64_t i = 0; i < n; i++) wave_out[i] = p.wave_of[i];
+    derived_info_fill(info, p, n);
+    return LIG_OK;
+}
+
+void lig_internal_derive_destroy(lig_derive* D) {
+    if (!D) return;
+    (void)hipSetDevice(D->device);
+    (void)hipFree(D->targets); (void)hipFree(D->terms); (void)hipFree(D->coef_mont);
+    delete D;
+}
+
+int lig_internal_derive_create(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, const uint8_t* elem_bytes, const lig_derived_slot* d,
+                               uint64_t n, lig_derive** out, lig_derived_info* info) {
+    *out = nullptr;
+    if (info && info->struct_bytes < sizeof(lig_derived_info)) FAIL(c, LIG_E_ARG, "lig_rows_set_derived: lig_derived_info.struct_bytes too small");
+    if (lig_linear_check(sys, kinds, rows, c->l) != LIG_OK) FAIL(c, LIG_E_ARG, "lig_rows_set_derived: linear system rejected by lig_linear_check");
+    lig::DerivePlan p;
+    if (const char* why = lig::plan_derived(*sys, kinds, rows, c->l, elem_bytes, d, n, p)) FAIL(c, LIG_E_ARG, std::string("lig_rows_set_derived: ") + why);
+    std::unique_ptr<lig_derive, void (*)(lig_derive*)> D(new lig_derive(), lig_internal_derive_destroy);
+    D->device = c->device;
+    D->wave_begin = p.wave_begin; D->wave_light = p.wave_light;
+    auto put = [&](void** dev, const void* host, size_t bytes) -> int {      // (blocking copies from pageable memory: the plan goes when this call returns)
+        const hipError_t e = hipMalloc(dev, bytes ? bytes : 16);
+        if (e != hipSuccess) { (void)hipGetLastError(); FAIL(c, LIG_E_NOMEM, std::string("lig_rows_set_derived: ") + hipGetErrorString(e)); }
+        if (bytes) HIP_TRY(c, hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
+        return LIG_OK;
+    };
+    TRY(put((void**)&D->targets, p.targets.data(), p.targets.size() * sizeof(lig::DeriveTarget)));
+    TRY(put((void**)&D->terms, p.terms.data(), p.terms.size() * sizeof(lig_lin_term)));
+    TRY(put((void**)&D->coef_mont, p.coefs.data(), p.coefs.size()));
+    lig::launch_lin_coefs_mont(c->stream, D->coef_mont, p.coefs.size() / 32);      // once per call; the waves run on the same stream
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    derived_info_fill(info, p, n);
+    *out = D.release();
+    return LIG_OK;
+}
+
+// the waves, in order, on `st`: msgs = the expanded rows x k matrix of the commit in progress
+int lig_internal_derive_run(lig_ctx* c, const lig_derive* D, fr* msgs, hipStream_t st) {
+    const uint64_t l_recip = lig::lin_reciprocal(c->l);
+    for (size_t w = 0; w + 1 < D->wave_begin.size(); w++) {
+        const uint32_t first = D->wave_begin[w], n_all = D->wave_begin[w + 1] - first, n_light = D->wave_light[w], n_heavy = n_all - n_light;
+        const uint32_t light_blocks = std::min((n_light + lig::LIN_WG - 1) / lig::LIN_WG, lig::DERIVE_MAX_BLOCKS), heavy_blocks = std::min(n_heavy, lig::DERIVE_MAX_BLOCKS);
+        if (!(light_blocks + heavy_blocks)) continue;
+        hipLaunchKernelGGL(lig::k_derive_wave, dim3(light_blocks + heavy_blocks), dim3(lig::LIN_WG), 0, st, D->targets + first, n_light, n_heavy, light_blocks,
+                           D->terms, msgs, c->l, c->k, l_recip, D->coef_mont);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return LIG_OK;
+}

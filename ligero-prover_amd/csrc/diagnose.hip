@@ -45,6 +45,7 @@
 
 #include "explain_plan.hpp"
 #include "lin_common.hpp"
+#include "lin_eval.hpp"
 #include "prover_common.hpp"
 
 namespace lig {
@@ -52,54 +53,8 @@ static constexpr uint32_t DIAG_MAX_BLOCKS = COEFS_MAX_BLOCKS;      // grid-strid
 static constexpr uint64_t DIAG_QUAD_ITEMS = 1ull << 20;            // scratch budget of the quadratic pass: (term, column) items per slice (40 bytes each)
 static constexpr uint64_t DIAG_UNTOUCHED_ITEMS = 1ull << 22;       // scratch budget of the untouched pass: slots per slice (16 bytes each)
 
-// n / d for n < 2^32 and the launch-uniform d >= 1: m = floor(2^64 / d) + 1 (host: diag_reciprocal), exact because n * (m d - 2^64) < 2^64
-static __device__ __forceinline__ uint32_t diag_div(uint32_t n, uint64_t m) { return (uint32_t)__umul64hi((uint64_t)n, m); }
-
-static __device__ __forceinline__ fr diag_one() {
-    fr o = fr_zero();
-    o.v[0] = 1;
-    return o;
-}
-// where the row a term names lies in `msgs`: the whole matrix (one GPU), or a rank's share through its global -> local row table
-// (LIN_NOT_LOCAL: another rank holds that row)
-struct DiagAllRows { __device__ __forceinline__ uint32_t operator()(uint32_t row) const { return row; } };
-struct DiagLocalRows { const uint32_t* __restrict__ local_of; __device__ __forceinline__ uint32_t operator()(uint32_t row) const { return local_of[row]; } };
-// acc (canonical) += a * w for the coefficient index `coef` and the canonical witness value w
-static __device__ __forceinline__ fr diag_apply(const fr& acc, uint32_t coef, const fr& w, const fr* __restrict__ coef_mont) {
-    if (coef == LIG_COEF_ONE) return fr_add(acc, w);
-    if (coef == LIG_COEF_NEG_ONE) return fr_sub(acc, w);
-    return fr_add(acc, fr_montmul(w, fr_load(coef_mont + coef)));         // w * (a R) / R = a * w, canonical
-}
-// acc (canonical) += coef * w[slot] for one term (unchanged for a term whose row is not in `msgs`)
-template <class Rows>
-static __device__ __forceinline__ fr diag_accumulate(const fr& acc, const lig_lin_term tm, const fr* __restrict__ msgs, uint32_t l, uint32_t k, uint64_t l_recip,
-                                                     const fr* __restrict__ coef_mont, const Rows rows) {
-    const uint32_t grow = diag_div(tm.slot, l_recip), col = tm.slot - grow * l, row = rows(grow);
-    if (row == LIN_NOT_LOCAL) return acc;
-    return diag_apply(acc, tm.coef, fr_load(msgs + (size_t)row * k + col), coef_mont);
-}
-// the canonical value a coefficient index stands for
-static __device__ __forceinline__ fr diag_coef_value(uint32_t coef, const fr* __restrict__ coef_mont) {
-    if (coef == LIG_COEF_ONE) return diag_one();
-    if (coef == LIG_COEF_NEG_ONE) return fr_neg(diag_one());
-    return fr_montmul(fr_load(coef_mont + coef), diag_one());             // (a R) * 1 / R = a
-}
-// the two walks over the terms [b, e) of one constraint: one lane; or the lanes of a workgroup striding the segment, then the fixed tree
-// (valid in thread 0; reached by all lanes of the workgroup)
-template <class Rows>
-static __device__ __forceinline__ fr diag_sum_lane(uint32_t b, uint32_t e, const lig_lin_term* __restrict__ terms, const fr* __restrict__ msgs, uint32_t l, uint32_t k,
-                                                   uint64_t l_recip, const fr* __restrict__ coef_mont, const Rows rows) {
-    fr acc = fr_zero();
-    for (uint32_t t = b; t < e; t++) acc = diag_accumulate(acc, terms[t], msgs, l, k, l_recip, coef_mont, rows);
-    return acc;
-}
-template <class Rows>
-static __device__ __forceinline__ fr diag_sum_block(uint32_t b, uint32_t e, const lig_lin_term* __restrict__ terms, const fr* __restrict__ msgs, uint32_t l, uint32_t k,
-                                                    uint64_t l_recip, const fr* __restrict__ coef_mont, const Rows rows, fr* sh) {
-    fr acc = fr_zero();
-    for (uint32_t t = b + threadIdx.x; t < e; t += LIN_WG) acc = diag_accumulate(acc, terms[t], msgs, l, k, l_recip, coef_mont, rows);
-    return lin_block_sum(acc, sh);
-}
+// (the walk over the terms of a constraint -- diag_div, diag_apply, diag_accumulate, diag_coef_value, diag_sum_lane, diag_sum_block -- is in
+// lin_eval.hpp: derive.hip evaluates the same sums)
 // acc - b_c -> residual and flag of constraint c, stored at index `at`; rhs_index[c] = 1 + the position of c in the right-hand-side list, 0: b_c = 0
 static __device__ __forceinline__ void diag_finish(uint32_t c, uint32_t at, fr acc, const uint32_t* __restrict__ rhs_index, const uint32_t* __restrict__ rhs_coef,
                                                    const fr* __restrict__ coef_mont, fr* __restrict__ res, uint32_t* __restrict__ flag) {
@@ -661,7 +616,7 @@ __global__ void __launch_bounds__(LIN_WG) k_untouched_compact(const uint64_t* __
 }  // namespace lig
 
 namespace {
-uint64_t diag_reciprocal(uint32_t d) { return d <= 1 ? ~0ull : ~0ull / d + 1; }       // floor(2^64 / d) + 1 (d = 1 is never used: l >= 2)
+uint64_t diag_reciprocal(uint32_t d) { return lig::lin_reciprocal(d); }
 uint32_t diag_grid(uint64_t items) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + lig::LIN_WG - 1) / lig::LIN_WG, 1), lig::DIAG_MAX_BLOCKS); }
 using DiagWait = std::function<int()>;      // "the main stream has drained": the way a proof waits (one GPU), or the bounded poll of a shard
 

@@ -39,6 +39,7 @@ struct lig_trace {
     bool up_by_thread = false;
     fr* rands_full = nullptr;           // lig_rows_push_rands / lig_rows_set_linear: R x k, device resident
     lig_linear* linear = nullptr;       // lig_rows_set_linear: the sparse linear system, regrouped by slot (linear.hip); survives lig_rows_restart
+    lig_derive* derive = nullptr;       // lig_rows_set_derived: the slots stage 1 forms from their defining constraints (derive.hip); survives lig_rows_restart
     uint64_t rands_pushed = 0;          // rows handed to the uploader so far (the page's push word counts the rows that have ARRIVED)
     bool push_sync = false;             // lig_rows_push_rands without an uploader thread: the pushed rows were copied synchronously
     std::vector<UploadJob> push_log;    // the pushes of the committed trace (their host rows stay valid until lig_rows_prove returns): what a retry copies again
@@ -49,6 +50,7 @@ struct lig_trace {
     // area the packed rows are uploaded to (expanded into `msgs` chunk by chunk in stage 1)
     bool narrow = false;
     std::vector<uint64_t> src_off;
+    std::vector<uint8_t> widths;        // elem_bytes of every row (32 for a full-width row): what lig_rows_set_derived checks its list against
     uint64_t* src_off_dev = nullptr; uint8_t* widths_dev = nullptr; uint8_t* packed_dev = nullptr;
     ProductRows prod;                   // derived rows (LIG_ELEM_PRODUCT): formed next to the expansion from the packed x and y rows
     WideRows wide;                      // mixed rows (lig_rows_job.wide_per_row): their records are written behind the expansion
@@ -280,6 +282,21 @@ static int trace_alloc(lig_ctx* c, lig_trace* T) {
     return LIG_OK;
 }
 
+// (the brackets of lig_profile_*, lig_capi.hip, for a launch this file makes)
+int lig_internal_profile_bracket(lig_ctx* c, uint32_t rows, hipEvent_t* e0, hipEvent_t* e1) {
+    *e0 = *e1 = nullptr;
+    if (!c->prof_on) return LIG_OK;
+    if (c->prof_used == c->prof_events.size()) {
+        hipEvent_t a, b;
+        HIP_TRY(c, hipEventCreate(&a)); HIP_TRY(c, hipEventCreate(&b));
+        c->prof_events.push_back({a, b});
+    }
+    *e0 = c->prof_events[c->prof_used].first; *e1 = c->prof_events[c->prof_used].second;
+    if (c->prof_launch_rows.size() < c->prof_used + 1) c->prof_launch_rows.resize(c->prof_used + 1);
+    c->prof_launch_rows[c->prof_used] = rows;
+    c->prof_used++; c->prof_rows += rows;
+    return LIG_OK;
+}
 // ================= stage 1: row forming (pads + masks from the encoding stream), encode, column hash, Merkle root
 static int prove_stage1(lig_trace* T, lig_proof_info* info, const std::function<void(const char*)>& mark) {
     lig_ctx* c = T->c;
@@ -330,17 +347,29 @@ static int prove_stage1(lig_trace* T, lig_proof_info* info, const std::function<
     };
     const int enc_mode = T->zres ? lig::ENC_ZRES : lig::ENC_PLANAR;
     const int gate = lig::knobs().sha_gate;
+    // Derived slots (lig_rows_set_derived): their waves read slots of ANY row, so every row of the trace has to be expanded first.  Rows that
+    // arrive chunk by chunk: the arrival wait, expansion and pads of all chunks, then the waves, then the encodes -- such a trace gives up the
+    // upload / encode overlap.  Device rows were expanded by rows_load on this stream.  Without a list nothing below differs.
+    const bool derive = T->derive != nullptr;
+    if (derive) {
+        if (streamed) for (size_t ci = 0; ci < T->sched1.size(); ci++) TRY(pre(ci, s_enc));
+        hipEvent_t e0 = nullptr, e1 = nullptr;                    // lig_profile_read_launches(rows_in_launch = 0): the waves of this commit
+        TRY(lig_internal_profile_bracket(c, 0, &e0, &e1));
+        if (e0) HIP_TRY(c, hipEventRecord(e0, s_enc));
+        TRY(lig_internal_derive_run(c, T->derive, T->msgs, s_enc));
+        if (e1) HIP_TRY(c, hipEventRecord(e1, s_enc));
+    }
     // LIG_SHA_GATE=2 (round 6): K1 of chunk ci+1 is queued BEHIND the last kernel of chunk ci and runs alone -- the hash of chunk ci
     // waits for it (K1 is latency-bound: next to the hash waves it takes 2.2x as long, on the critical path of a lone proof) --
     // then the hash is placed, then the tile kernel of chunk ci+1 goes on.  (One Y scratch: K1 of ci+1 starts after chunk ci is done with it.)
-    const bool k1_ahead = gate == 2 && c->fast && lig_tune::CHUNK <= lig::knobs().encode_chunk;
+    const bool k1_ahead = gate == 2 && c->fast && lig_tune::CHUNK <= lig::knobs().encode_chunk && !derive;
     if (k1_ahead && !T->sched1.empty()) {
         TRY(pre(0, s_enc));
         TRY(lig_internal_encode_rows(c, T->msgs, T->cw, T->sched1[0].second - T->sched1[0].first, enc_mode, s_enc, 1));
     }
     for (size_t ci = 0; ci < T->sched1.size(); ci++) {
         const size_t b = T->sched1[ci].first, nb = T->sched1[ci].second - b;
-        if (!k1_ahead) TRY(pre(ci, s_enc));
+        if (!k1_ahead && !derive) TRY(pre(ci, s_enc));
         TRY(lig_internal_encode_rows(c, T->msgs + b * k, T->cw + b * k3, nb, enc_mode, s_enc, k1_ahead ? 14 : 15));
         HIP_TRY(c, hipEventRecord(c->ev_fork, s_enc));
         HIP_TRY(c, hipStreamWaitEvent(s_sha, c->ev_fork, 0));
@@ -705,6 +734,7 @@ void lig_trace_destroy(lig_trace* T) {
     T->up.drain();                                        // an upload still in flight
     T->rand.drain();
     lig_internal_linear_destroy(T->linear);
+    lig_internal_derive_destroy(T->derive);
     T->c->sha.erase(T->sha_state);
     if (T->leak) {      // destinations of a transfer that was given up on and has never completed (upload_settled): they outlive the trace
         T->rands_full = nullptr; T->msgs_alt = nullptr; T->msgs = nullptr; T->randb = nullptr; T->packed_dev = nullptr;
@@ -850,6 +880,7 @@ static int rows_begin_impl(lig_ctx* c, const lig_rows_job* job, lig_trace* T) {
     if (T->narrow) {
         TRY(lig_internal_upload_narrow_plan(c, np, &T->src_off_dev, &T->widths_dev, &T->prod, &T->wide));
         T->src_off = std::move(np.src_off);
+        T->widths = np.widths;
         if (T->wide.any()) HIP_TRY(c, hipHostMalloc((void**)&T->h_wide_flag, sizeof(uint32_t)));
         if (!job->msgs_on_device) HIP_TRY(c, hipMalloc((void**)&T->packed_dev, T->src_off[R] ? T->src_off[R] : 16));
     }
@@ -1023,6 +1054,27 @@ int lig_rows_set_linear(lig_trace* T, const lig_linear_system* sys) {
     lig_linear* L = nullptr;
     TRY(lig_internal_linear_create(c, sys, kinds_of(T->rows).data(), T->R, &L));       // lig_linear_check first: nothing is launched for a system it rejects
     return trace_take_linear(T, L, "lig_rows_set_linear");
+}
+
+// derived slots (derive.hip): checked against the trace's kinds and widths, copied, in force from the next lig_rows_commit on.  A refused
+// list changes nothing.  (No derive kernel is in flight here: lig_rows_commit returns only after stage 1 has drained.)
+int lig_rows_set_derived(lig_trace* T, const lig_linear_system* sys, const lig_derived_slot* d, uint64_t n, lig_derived_info* info) {
+    if (!T) return LIG_E_ARG;
+    lig_ctx* c = T->c;
+    CHECK_CTX(c);
+    if (!T->from_rows) FAIL(c, LIG_E_STATE, "lig_rows_set_derived: not a rows trace");
+    if (!d || !n) {
+        if (info && info->struct_bytes < sizeof(lig_derived_info)) FAIL(c, LIG_E_ARG, "lig_rows_set_derived: lig_derived_info.struct_bytes too small");
+        lig_internal_derive_destroy(T->derive);
+        T->derive = nullptr;
+        if (info) { const uint32_t sb = info->struct_bytes; std::memset(info, 0, sizeof *info); info->struct_bytes = sb; }
+        return LIG_OK;
+    }
+    lig_derive* D = nullptr;
+    TRY(lig_internal_derive_create(c, sys, kinds_of(T->rows).data(), T->R, T->narrow ? T->widths.data() : nullptr, d, n, &D, info));
+    lig_internal_derive_destroy(T->derive);
+    T->derive = D;
+    return LIG_OK;
 }
 
 int lig_rows_attach_linear(lig_trace* T, const lig_linear_program* p) {

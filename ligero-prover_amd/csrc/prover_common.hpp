@@ -472,6 +472,14 @@ struct lig_linear_view {
 };
 lig_linear_view lig_internal_linear_view(const lig_linear* L);
 
+// derived slots (derive.hip; lig_hip.h: lig_rows_set_derived): create = lig_linear_check + plan_derived (derive_plan.hpp) against the kinds and
+// widths given (elem_bytes: one per row, or NULL) + the program copied to the device, its table converted on the context stream; synchronous.
+// run = one launch per wave on `st` over the expanded rows x k matrix `msgs` (stage 1, in front of the first encode).
+struct lig_derive;
+int lig_internal_derive_create(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, const uint8_t* elem_bytes, const lig_derived_slot* d,
+                               uint64_t n, lig_derive** out, lig_derived_info* info);
+void lig_internal_derive_destroy(lig_derive* D);
+int lig_internal_derive_run(lig_ctx* c, const lig_derive* D, fr* msgs, hipStream_t st);
 // lig_rows_diagnose (diagnose.hip): the residual of every linear constraint of `sys` (NULL: none; it has passed lig_linear_check) and of every
 // (quadratic term, column < l) over the committed rows x k matrix `msgs`; tri_dev = the trace's quadratic terms, 3 row indices each.
 // Blocking, on the context's main stream; waits the way a proof does (lig_internal_wait_stream, prover.hip).

@@ -16,7 +16,8 @@ KERNELS = ["k_encode_in<10>", "k_encode_tiles<10, true>", "k_encode_tiles<10, fa
            "k_diag_lin", "k_diag_lin_heavy", "k_diag_quad", "k_diag_lin_part", "k_diag_lin_part_heavy", "k_diag_reduce<true>", "k_diag_reduce<false>",
            "k_diag_att_bounds", "k_diag_att_part", "k_diag_att_part_heavy",
            "k_explain_mark", "k_explain_collect", "k_explain_gather", "k_explain_fill<ExplainFromMatrix>", "k_explain_finish<ExplainFromMatrix>", "k_read_slots",
-           "k_explain_part", "k_explain_sum", "k_explain_fill<ExplainFromValues>", "k_explain_finish<ExplainFromValues>"]
+           "k_explain_part", "k_explain_sum", "k_explain_fill<ExplainFromValues>", "k_explain_finish<ExplainFromValues>",
+           "k_derive_wave"]
 BEGIN, END = "<!-- isa-table:begin -->", "<!-- isa-table:end -->"
 
 
