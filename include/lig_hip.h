@@ -702,8 +702,8 @@ int lig_rows_untouched_slots(lig_trace *trace, const lig_linear_system *sys, int
  *   own evaluation would have been wrong now proves a different w, and the OTHER constraints on that slot fail instead.
  *   Deterministic: one lane (a workgroup with a fixed summation tree for a constraint with more than 64 other terms) per target, no
  *   atomic on a field element: the same bytes on every run.
- * Not done: the sharded entry (no lig_shard_* call takes a list).  Not done: per-chunk reach, so that a chunk waits only for the rows its
- * derived slots read; derived operands of LIG_ELEM_PRODUCT rows.
+ * The sharded entry: lig_shard_rows_set_derived, below lig_shard_rows_set_linear.  Not done: per-chunk reach, so that a chunk waits only
+ * for the rows its derived slots read; derived operands of LIG_ELEM_PRODUCT rows.
  * The new structs version themselves with struct_bytes; they are not part of lig_abi_sizes (LIG_ABI_STRUCTS stays 6). */
 enum { LIG_DERIVE_MAX_WAVES = 16 };
 typedef struct { uint32_t slot, constraint; } lig_derived_slot;                                                     /* 8 bytes */
@@ -845,6 +845,42 @@ int lig_shard_rows_linear_stats(const lig_shard *shard, uint64_t *local_terms, u
  * GPU is touched.  LIG_E_ARG: world == 0, rank >= world, a system lig_linear_check rejects. */
 int lig_linear_shard_count(const lig_linear_system *sys, const uint8_t *kinds, uint64_t rows, uint32_t l, uint32_t rank, uint32_t world,
                            uint64_t *local_terms, uint64_t *needed_constraints);
+/* Derived slots on a rows shard: what lig_rows_set_derived is on one GPU (csrc/derive.hip, csrc/derive_plan.hpp).  `sys` and `d` describe
+ * the WHOLE trace with global slots, exactly what lig_rows_set_derived takes.  COLLECTIVE CONTRACT as lig_shard_rows_set_linear: every
+ * rank passes the same system and the same list -- the exchange schedule is computed from them on every rank; ranks that differ are not
+ * detected (their all-gathers disagree in size, or they commit different rows).  The call itself issues NO collective and never waits
+ * for a peer.  Accepted and refused lists are those of lig_derived_check against the kinds and widths of all rows of the job (LIG_E_ARG:
+ * nothing launched, no collective, the previous list stays in force); LIG_E_STATE: a shard not made by lig_shard_rows_begin, a poisoned
+ * shard; LIG_E_ARG: info->struct_bytes too small.  Copies what it needs before it returns; survives lig_shard_rows_restart; a second call
+ * replaces the list; d == NULL or n == 0 removes it; lig_shard_rows_set_linear_values does not reach it; freed by lig_shard_destroy.
+ *   A target is formed by the rank that was dealt its row, wave by wave (the waves of lig_derived_check, numbered over the whole list).
+ *   Its other terms are LOCAL (on a row of the same rank) or IMPORTED (on a row of another rank, possibly derived there in an earlier
+ *   wave).  Per wave w every rank q sends E_q(w) = the distinct slots it holds that a wave-w target of ANOTHER rank reads and that no
+ *   earlier wave has sent, ascending: one all-gather of B(w) = max_q |E_q(w)| elements per rank, into an import buffer that is
+ *   addressed absolutely over the commit.  A wave with B(w) = 0 issues no collective, on every rank alike: a list whose constraints are
+ *   row-local (a machine word recomposed from bits of its own row) exchanges nothing.  Field addition is exact: the regrouped sum gives
+ *   the bytes of lig_rows_set_derived.
+ *   WHERE  in lig_shard_rows_commit, on the main stream, before the first round's encode: per wave the export kernel and the all-gather
+ *          (both only when B(w) > 0), then the wave kernel, which stores into the rank's local rows; the pads are not touched.  A failed
+ *          collective takes the path of every other collective of the commit (LIG_E_STATE, possibly a poisoned shard).  Host rows that
+ *          arrive round by round (LIG_SHARD_UPLOADER=1): every round's arrival is waited for first -- such a trace gives up the upload /
+ *          encode overlap.  Without a list the commit queues exactly what it queued before.
+ *   READERS see the derived values: lig_shard_rows_read_slots, lig_shard_rows_diagnose*, lig_shard_rows_explain*,
+ *          lig_shard_rows_explain_slots*, lig_shard_rows_untouched_slots*, stage 2.
+ * *info (or NULL; struct_bytes set by the caller): n_slots, n_terms, n_waves of the whole list; n_exchanges = waves with an all-gather;
+ * of THIS rank: local_targets, local_terms + imported_terms (the other terms of its targets), imports = distinct foreign slots its
+ * targets read, exports = slots it sends, exchange_bytes = 32 * world * sum_w B(w), the bytes it receives per commit.
+ * lig_derived_shard_count: host only, no context, no shard: the same numbers for `rank` of `world` from the deal of lig_shard_rows_plan
+ * (LIG_E_ARG also for world == 0, rank >= world, a NULL info).
+ * Not done: sharing one plan between the ranks of a process; detecting ranks that pass different lists. */
+typedef struct { uint32_t struct_bytes, reserved;
+                 uint64_t n_slots, n_terms; uint32_t n_waves, n_exchanges;   /* whole list; waves that need an all-gather */
+                 uint64_t local_targets, local_terms, imported_terms,        /* this rank */
+                          imports, exports, exchange_bytes;                  /* distinct foreign slots read / own slots sent; bytes this rank receives per commit */
+               } lig_derived_shard_info;                                                                            /* 80 bytes */
+int lig_derived_shard_count(const lig_linear_system *sys, const uint8_t *kinds, uint64_t rows, uint32_t l, const uint8_t *elem_bytes /* NULL ok */,
+                            const lig_derived_slot *d, uint64_t n, uint32_t rank, uint32_t world, lig_derived_shard_info *info);
+int lig_shard_rows_set_derived(lig_shard *shard, const lig_linear_system *sys, const lig_derived_slot *d, uint64_t n, lig_derived_shard_info *info /* NULL ok */);
 
 /* lig_rows_diagnose on a rows shard (csrc/diagnose.hip, csrc/shard.hip).  COLLECTIVE: every rank calls it with the same `sys` -- the system
  * of the WHOLE trace, global slots, as lig_shard_rows_set_linear takes it -- and the same caps.  EVERY RANK RETURNS THE SAME BYTES, and

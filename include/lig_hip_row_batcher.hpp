@@ -144,7 +144,7 @@ public:
         if (pass_ != 1 || !comm || !world || rank >= world) throw std::invalid_argument("hip_row_batcher::shard_over");
         if (program_) throw std::logic_error("hip_row_batcher::shard_over: a prepared linear program is not for a sharded batcher (set_linear_system)");
         if (!derived_.empty()) throw std::logic_error("hip_row_batcher::shard_over: derived slots are not for a sharded batcher (set_derived_slots)");
-        if (shard_) { lig_shard_destroy(shard_); shard_ = nullptr; linear_on_trace_ = false; }      // another deal: nothing of the old shard is reused
+        if (shard_) { lig_shard_destroy(shard_); shard_ = nullptr; linear_on_trace_ = false; shard_derived_on_shard_ = shard_derived_.empty(); }      // another deal: nothing of the old shard is reused
         sharded_ = true; rank_ = rank; world_ = world; comm_ = *comm;
     }
 
@@ -197,8 +197,8 @@ public:
     // DEFINING constraint in `sys`): the library forms w[slot] from the other terms of that constraint in commit(), whatever the row
     // carries there (the driver writes 0, so a bit row stays a bit row).  In pass 1, before commit(); sys and d are copied (sys need
     // not be the system of set_linear_system); kept across reset() for the next proof of the same shape, where the list stays
-    // resident on the trace -- for other right-hand sides call it again; n == 0 removes the list.  Not with shard_over(): the sharded
-    // entry takes no list.
+    // resident on the trace -- for other right-hand sides call it again; n == 0 removes the list.  Not with shard_over(): a sharded
+    // batcher takes its list through shard_set_derived_slots() below.
     void set_derived_slots(const lig_linear_system& sys, const lig_derived_slot* d, uint64_t n) {
         if (pass_ != 1) throw std::logic_error("hip_row_batcher::set_derived_slots after commit (reset() first)");
         if (sharded_) throw std::logic_error("hip_row_batcher::set_derived_slots: not on a sharded batcher");
@@ -206,6 +206,19 @@ public:
         if (n) derived_sys_.assign(sys); else derived_sys_.clear();
         derived_.assign(d, d + n);
         derived_on_trace_ = false;
+    }
+    // set_derived_slots() for a batcher with shard_over(): lig_shard_rows_set_derived (lig_hip.h).  sys and d describe the WHOLE trace with
+    // global slots and EVERY RANK PASSES THE SAME LIST (the ranks compute their exchange schedule from it; no collective is involved in the
+    // call).  Each rank forms the targets on its own rows in commit(), importing the operands other ranks hold; a list whose constraints
+    // are row-local exchanges nothing.  In pass 1, before commit(); copied; kept across reset() -- the list stays resident on the shard,
+    // applied before lig_shard_rows_commit; n == 0 removes it.  std::logic_error on an unsharded batcher and after commit().
+    void shard_set_derived_slots(const lig_linear_system& sys, const lig_derived_slot* d, uint64_t n) {
+        if (!sharded_) throw std::logic_error("hip_row_batcher::shard_set_derived_slots: not a sharded batcher (set_derived_slots)");
+        if (pass_ != 1) throw std::logic_error("hip_row_batcher::shard_set_derived_slots after commit (reset() first)");
+        if (n && !d) throw std::invalid_argument("hip_row_batcher::shard_set_derived_slots: null list");
+        if (n) shard_derived_sys_.assign(sys); else shard_derived_sys_.clear();
+        shard_derived_.assign(d, d + n);
+        shard_derived_on_shard_ = false;
     }
 
     // ---- the callbacks of nonbatch_context_base (nonbatch_context.hpp:78-86).  `rand` rows are null in pass 1.
@@ -600,11 +613,16 @@ private:
         shipped_ = job.elem_bytes ? (size_t)(out - reinterpret_cast<uint8_t*>(rows_.row(0))) : n_local_ * words * 8;
         if (shard_) {                                      // the next proof of the same program: the shard's buffers and its share of the system are reused
             if (same_shape(job)) check(lig_shard_rows_restart(shard_, job.msgs, 0), "lig_shard_rows_restart");
-            else { lig_shard_destroy(shard_); shard_ = nullptr; linear_on_trace_ = false; }
+            else { lig_shard_destroy(shard_); shard_ = nullptr; linear_on_trace_ = false; shard_derived_on_shard_ = shard_derived_.empty(); }
         }
         if (!shard_) check(lig_shard_rows_begin(ctx_, &job, rank_, world_, &comm_, &shard_), "lig_shard_rows_begin");
         shape_kinds_ = kinds_; shape_widths_ = job.elem_bytes ? widths : std::vector<uint8_t>(); shape_wide_ = wide; shape_meta_ = meta_;
         apply_linear();                                   // this rank's share of the system, under the commit
+        if (!shard_derived_on_shard_) {                   // (... and its program of the derived slots: the shard keeps it across its restart)
+            check(lig_shard_rows_set_derived(shard_, shard_derived_.empty() ? nullptr : shard_derived_sys_.get(), shard_derived_.empty() ? nullptr : shard_derived_.data(),
+                                             shard_derived_.size(), nullptr), "lig_shard_rows_set_derived");
+            shard_derived_on_shard_ = true;
+        }
         check(lig_shard_rows_commit(shard_, root, stage1_seed), "lig_shard_rows_commit");
         for (auto& kd : kinds_) kd &= 0x7f;               // (pass 2 compares plain kinds)
         const size_t rand_rows = has_linear() ? 0 : n_local_;      // with a system no randomness row is staged (one scratch row for next_slot)
@@ -768,6 +786,9 @@ private:
     hip_linear_system_copy derived_sys_;                  // set_derived_slots: the system the defining constraints are in
     std::vector<lig_derived_slot> derived_;
     bool derived_on_trace_ = true;                        // the trace holds the list above (no trace, no list: nothing to do)
+    hip_linear_system_copy shard_derived_sys_;            // shard_set_derived_slots: the same three for a batcher with shard_over()
+    std::vector<lig_derived_slot> shard_derived_;
+    bool shard_derived_on_shard_ = true;
     bool values_set_ = false;
     bool linear_on_trace_ = false;                        // trace_ holds linear_ / program_ (it stays resident across lig_rows_restart)
     bool values_on_trace_ = false;                        // ... and the values of values_ (or, !values_set_, its own table)

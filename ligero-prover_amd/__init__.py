@@ -49,6 +49,7 @@ EXPORTS = [
     "lig_shard_rows_set_linear_values", "lig_shard_rows_diagnose_attached",
     "lig_shard_rows_explain_slots", "lig_shard_rows_explain_slots_attached", "lig_shard_rows_untouched_slots", "lig_shard_rows_untouched_slots_attached",
     "lig_derived_check", "lig_rows_set_derived",
+    "lig_derived_shard_count", "lig_shard_rows_set_derived",
 ]
 
 ROW_KINDS = dict(LINEAR=0, QX=1, QY=2, QZ=3, INIT=4, BIT=5, EQX=6, EQY=7, BQX=8, BQY=9, BQZ=10)
@@ -181,6 +182,36 @@ def derived_check(system, kinds, l, pairs, elem_bytes=None):
     if rc != 0:
         raise LigError("lig_derived_check failed (%d)" % rc)
     return waves
+
+
+class DerivedShardInfo(C.Structure):
+    """lig_derived_shard_info: n_slots, n_terms, n_waves of the whole list, n_exchanges = its waves with an all-gather; of this rank:
+    local_targets, local_terms + imported_terms (the other terms of its targets), imports = distinct foreign slots read, exports = slots
+    sent, exchange_bytes = what it receives per commit"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("reserved", C.c_uint32), ("n_slots", C.c_uint64), ("n_terms", C.c_uint64),
+                ("n_waves", C.c_uint32), ("n_exchanges", C.c_uint32), ("local_targets", C.c_uint64), ("local_terms", C.c_uint64),
+                ("imported_terms", C.c_uint64), ("imports", C.c_uint64), ("exports", C.c_uint64), ("exchange_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if not name.startswith("reserved") and name != "struct_bytes"}
+
+
+def derived_shard_count(system, kinds, l, pairs, elem_bytes, rank, world):
+    """lig_derived_shard_count (host only): what lig_shard_rows_set_derived reports on `rank` of `world` for the list `pairs` under the deal
+    of shard_rows_plan -> DerivedShardInfo; LigError(-1) for rank >= world, world == 0 or a list lig_derived_check refuses"""
+    kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+    d = _derived_pairs(pairs)
+    eb = np.ascontiguousarray(elem_bytes, dtype=np.uint8) if elem_bytes is not None else None
+    if eb is not None and len(eb) != len(kinds):
+        raise ValueError("derived_shard_count: %d widths for %d rows" % (len(eb), len(kinds)))
+    info = DerivedShardInfo()
+    info.struct_bytes = C.sizeof(DerivedShardInfo)
+    rc = load_library().lig_derived_shard_count(C.byref(system), kinds.ctypes.data if len(kinds) else None, len(kinds), l,
+                                                eb.ctypes.data if eb is not None and len(eb) else None, d.ctypes.data if len(d) else None, len(d),
+                                                rank, world, C.byref(info))
+    if rc != 0:
+        raise LigError("lig_derived_shard_count failed (%d)" % rc)
+    return info
 
 
 def linear_shard_count(system, kinds, l, rank, world):
@@ -425,6 +456,8 @@ def load_library():
     L.lig_rows_verify_set_linear.argtypes = [vp, C.POINTER(LinearSystem)]
     L.lig_shard_rows_set_linear.argtypes = [vp, C.POINTER(LinearSystem)]
     L.lig_shard_rows_linear_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.lig_derived_shard_count.argtypes = [C.POINTER(LinearSystem), vp, u64, u32, vp, vp, u64, u32, u32, C.POINTER(DerivedShardInfo)]
+    L.lig_shard_rows_set_derived.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, C.POINTER(DerivedShardInfo)]
     L.lig_linear_shard_count.argtypes = [C.POINTER(LinearSystem), vp, u64, u32, u32, u32, C.POINTER(u64), C.POINTER(u64)]
     L.lig_linear_prepare.argtypes = [vp, C.POINTER(LinearSystem), vp, u64, C.POINTER(vp)]
     L.lig_linear_program_release.argtypes = [vp]
@@ -935,6 +968,16 @@ class Context:
         """lig_shard_rows_set_linear: `system` describes the WHOLE trace and is the same on every rank; shard_rows_prove(shard, None, None)
         then forms this rank's randomness rows and the constant itself; None removes it"""
         self.check(self.L.lig_shard_rows_set_linear(shard, C.byref(system) if system is not None else None))
+
+    def shard_rows_set_derived(self, shard, system, pairs):
+        """lig_shard_rows_set_derived: pairs = (global slot, defining constraint of `system`) of the slots of the WHOLE trace the ranks form
+        themselves from the next shard_rows_commit on; the same on every rank; None or an empty list removes the list -> DerivedShardInfo"""
+        info = DerivedShardInfo()
+        info.struct_bytes = C.sizeof(DerivedShardInfo)
+        d = _derived_pairs(pairs) if pairs is not None else np.zeros((0, 2), dtype=np.uint32)
+        self.check(self.L.lig_shard_rows_set_derived(shard, C.byref(system) if system is not None else None, d.ctypes.data if len(d) else None, len(d),
+                                                     C.byref(info)))
+        return info
 
     def shard_rows_linear_stats(self, shard):
         """-> (local_terms, sampled_constraints) of the system set last on this rank"""

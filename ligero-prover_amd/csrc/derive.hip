@@ -17,6 +17,13 @@
 //           then b - sum or sum - b, canonical, two 16-byte stores into the matrix.  A target reads only slots that are not derived or
 //           belong to an earlier wave (launch order on one stream), never a slot written by its own launch.  No atomic on a field
 //           element: the same bytes on every run.  Every index the kernel uses was checked on the host (lig_linear_check, plan_derived).
+//   shard   lig_shard_rows_set_derived: the same list on a trace dealt over the ranks of a node.  plan_derived_shard (derive_plan.hpp) gives
+//           a rank the targets on its rows, their terms split into LOCAL ones (slot = local row * l + col of the rank's matrix) and
+//           IMPORTED ones (slot = position in the rank's import buffer), and the exchange schedule every rank computes alike.  Per wave,
+//           on the main stream of stage 1 (shard.hip): k_derive_export copies the slots other ranks read from the matrix into a send
+//           block (zero tail), ONE all-gather appends the ranks' blocks to the import buffer -- both only for a wave in which something
+//           crosses ranks -- then k_derive_wave_shard: k_derive_wave with the two sources, the same walk, the same light / heavy split,
+//           tree and block cap, the store into the local row.  Exact field addition: the regrouped sum is the one-GPU sum, byte for byte.
 #include "derive_plan.hpp"
 #include "lin_eval.hpp"
 #include "prover_common.hpp"
@@ -47,6 +54,46 @@ __global__ void __launch_bounds__(LIN_WG) k_derive_wave(const DeriveTarget* __re
         const DeriveTarget tg = targets[n_light + h];
         const fr sum = diag_sum_block(tg.begin, tg.end, terms, msgs, l, k, l_recip, coef_mont, DiagAllRows{}, sh);
         if (threadIdx.x == 0) derive_store(tg, sum, msgs, l, k, l_recip, coef_mont);
+        __syncthreads();                                                  // sh is reused by the next target
+    }
+}
+
+// ---- a rows shard
+// lane i < block: send[i] = the value of the i-th slot of this rank's E(w) (local slot -> row, column of the rank's matrix), zero for i >= n
+__global__ void __launch_bounds__(LIN_WG) k_derive_export(const uint32_t* __restrict__ slots, uint32_t n, uint32_t block, const fr* __restrict__ msgs, uint32_t l, uint32_t k,
+                                                          uint64_t l_recip, fr* __restrict__ send) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < block; i += (uint64_t)gridDim.x * LIN_WG) {
+        fr v = fr_zero();
+        if (i < n) {
+            const uint32_t slot = slots[i], row = diag_div(slot, l_recip), col = slot - row * l;
+            v = fr_load(msgs + (size_t)row * k + col);
+        }
+        fr_store(send + i, v);
+    }
+}
+static __device__ __forceinline__ void derive_store_shard(const DeriveShardTarget tg, fr sum, fr* msgs, uint32_t k, const fr* __restrict__ coef_mont) {
+    const fr b = tg.rhs == DERIVE_RHS_ZERO ? fr_zero() : diag_coef_value(tg.rhs, coef_mont);
+    fr_store(msgs + (size_t)tg.row * k + tg.col, tg.negate ? fr_sub(sum, b) : fr_sub(b, sum));
+}
+// k_derive_wave over a rank's share: terms [begin, mid) from the rank's matrix, [mid, end) from its import buffer
+__global__ void __launch_bounds__(LIN_WG) k_derive_wave_shard(const DeriveShardTarget* __restrict__ targets, uint32_t n_light, uint32_t n_heavy, uint32_t light_blocks,
+                                                              const lig_lin_term* __restrict__ terms, fr* msgs, const fr* __restrict__ imported, uint32_t l, uint32_t k,
+                                                              uint64_t l_recip, const fr* __restrict__ coef_mont) {
+    __shared__ fr sh[LIN_WG];
+    if (blockIdx.x < light_blocks) {
+        for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n_light; i += (uint64_t)light_blocks * LIN_WG) {
+            const DeriveShardTarget tg = targets[i];
+            const fr own = diag_walk(fr_zero(), tg.begin, tg.mid, 1, terms, msgs, l, k, l_recip, coef_mont, DiagAllRows{});
+            derive_store_shard(tg, diag_walk(own, tg.mid, tg.end, 1, terms, imported, l, k, l_recip, coef_mont, DiagFlat{}), msgs, k, coef_mont);
+        }
+        return;
+    }
+    const uint32_t heavy_blocks = gridDim.x - light_blocks;
+    for (uint32_t h = blockIdx.x - light_blocks; h < n_heavy; h += heavy_blocks) {      // (uniform over the workgroup, as in k_derive_wave)
+        const DeriveShardTarget tg = targets[n_light + h];
+        const fr own = diag_walk(fr_zero(), tg.begin + threadIdx.x, tg.mid, LIN_WG, terms, msgs, l, k, l_recip, coef_mont, DiagAllRows{});
+        const fr sum = lin_block_sum(diag_walk(own, tg.mid + threadIdx.x, tg.end, LIN_WG, terms, imported, l, k, l_recip, coef_mont, DiagFlat{}), sh);
+        if (threadIdx.x == 0) derive_store_shard(tg, sum, msgs, k, coef_mont);
         __syncthreads();                                                  // sh is reused by the next target
     }
 }
@@ -125,6 +172,109 @@ int lig_internal_derive_run(lig_ctx* c, const lig_derive* D, fr* msgs, hipStream
         if (!(light_blocks + heavy_blocks)) continue;
         hipLaunchKernelGGL(lig::k_derive_wave, dim3(light_blocks + heavy_blocks), dim3(lig::LIN_WG), 0, st, D->targets + first, n_light, n_heavy, light_blocks,
                            D->terms, msgs, c->l, c->k, l_recip, D->coef_mont);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return LIG_OK;
+}
+
+// ---- a rows shard: one rank's program of lig_shard_rows_set_derived; nothing writes it after the call has returned
+struct lig_derive_shard {
+    int device = 0;
+    std::vector<uint32_t> wave_begin, wave_light, block, import_begin, export_begin;
+    lig::DeriveShardTarget* targets = nullptr;
+    lig_lin_term* terms = nullptr;
+    uint32_t* exports = nullptr;
+    fr* coef_mont = nullptr;
+};
+
+static void derived_shard_info_fill(lig_derived_shard_info* info, const lig::DerivePlan& p, const lig::DeriveShardPlan& sp, uint64_t n) {
+    if (!info) return;
+    const uint32_t struct_bytes = info->struct_bytes;
+    std::memset(info, 0, sizeof *info);
+    info->struct_bytes = struct_bytes;
+    info->n_slots = n;
+    info->n_terms = p.terms.size();
+    info->n_waves = p.n_waves;
+    info->n_exchanges = sp.n_exchanges;
+    info->local_targets = sp.targets.size();
+    info->local_terms = sp.local_terms;
+    info->imported_terms = sp.imported_terms;
+    info->imports = sp.n_imports;
+    info->exports = sp.n_exports;
+    info->exchange_bytes = 32 * sp.import_elems();      // world * sum_w B(w) elements
+}
+// why a list is refused on a shard (nullptr: accepted, p and sp are the plans); owner: the rank of every row of the whole trace
+static const char* derive_shard_plan(const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, uint32_t l, const uint8_t* elem_bytes, const lig_derived_slot* d,
+                                     uint64_t n, const std::vector<uint32_t>& owner, uint32_t rank, uint32_t world, lig::DerivePlan& p, lig::DeriveShardPlan& sp) {
+    if (lig_linear_check(sys, kinds, rows, l) != LIG_OK) return "linear system rejected by lig_linear_check";
+    if (const char* why = lig::plan_derived(*sys, kinds, rows, l, elem_bytes, d, n, p)) return why;
+    return lig::plan_derived_shard(p, lig::derive_deal_of(owner, world), l, rank, world, sp);
+}
+int lig_internal_derive_shard_count(const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, uint32_t l, const uint8_t* elem_bytes, const lig_derived_slot* d,
+                                    uint64_t n, const std::vector<uint32_t>& owner, uint32_t rank, uint32_t world, lig_derived_shard_info* info) {
+    lig::DerivePlan p;
+    lig::DeriveShardPlan sp;
+    if (derive_shard_plan(sys, kinds, rows, l, elem_bytes, d, n, owner, rank, world, p, sp)) return LIG_E_ARG;
+    derived_shard_info_fill(info, p, sp, n);
+    return LIG_OK;
+}
+
+void lig_internal_derive_shard_destroy(lig_derive_shard* D) {
+    if (!D) return;
+    (void)hipSetDevice(D->device);
+    (void)hipFree(D->targets); (void)hipFree(D->terms); (void)hipFree(D->exports); (void)hipFree(D->coef_mont);
+    delete D;
+}
+
+int lig_internal_derive_shard_create(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, const uint8_t* elem_bytes, const lig_derived_slot* d,
+                                     uint64_t n, const std::vector<uint32_t>& owner, uint32_t rank, uint32_t world, lig_derive_shard** out, uint64_t* send_elems,
+                                     uint64_t* import_elems, lig_derived_shard_info* info) {
+    *out = nullptr;
+    lig::DerivePlan p;
+    lig::DeriveShardPlan sp;
+    if (const char* why = derive_shard_plan(sys, kinds, rows, c->l, elem_bytes, d, n, owner, rank, world, p, sp)) FAIL(c, LIG_E_ARG, std::string("lig_shard_rows_set_derived: ") + why);
+    std::unique_ptr<lig_derive_shard, void (*)(lig_derive_shard*)> D(new lig_derive_shard(), lig_internal_derive_shard_destroy);
+    D->device = c->device;
+    D->wave_begin = sp.wave_begin; D->wave_light = sp.wave_light; D->block = sp.block; D->import_begin = sp.import_begin; D->export_begin = sp.export_begin;
+    auto put = [&](void** dev, const void* host, size_t bytes) -> int {      // (blocking copies from pageable memory: the plan goes when this call returns)
+        const hipError_t e = hipMalloc(dev, bytes ? bytes : 16);
+        if (e != hipSuccess) { (void)hipGetLastError(); FAIL(c, LIG_E_NOMEM, std::string("lig_shard_rows_set_derived: ") + hipGetErrorString(e)); }
+        if (bytes) HIP_TRY(c, hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
+        return LIG_OK;
+    };
+    TRY(put((void**)&D->targets, sp.targets.data(), sp.targets.size() * sizeof(lig::DeriveShardTarget)));
+    TRY(put((void**)&D->terms, sp.terms.data(), sp.terms.size() * sizeof(lig_lin_term)));
+    TRY(put((void**)&D->exports, sp.exports.data(), sp.exports.size() * sizeof(uint32_t)));
+    TRY(put((void**)&D->coef_mont, p.coefs.data(), p.coefs.size()));
+    lig::launch_lin_coefs_mont(c->stream, D->coef_mont, p.coefs.size() / 32);      // once per call; the waves run on the same stream
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *send_elems = 0;
+    for (const uint32_t b : sp.block) *send_elems = std::max<uint64_t>(*send_elems, b);
+    *import_elems = sp.import_elems();
+    derived_shard_info_fill(info, p, sp, n);
+    *out = D.release();
+    return LIG_OK;
+}
+
+// the waves of one commit, in order, on `st`: msgs = the rank's expanded local rows x k matrix; send (>= max B(w) elements) and imported
+// (>= world * sum B(w)) belong to the shard; all_gather(src, dst, bytes per rank) is the shard's (stream-ordered on st, or drained)
+int lig_internal_derive_shard_run(lig_ctx* c, const lig_derive_shard* D, fr* msgs, fr* send, fr* imported, hipStream_t st,
+                                  const std::function<int(const void*, void*, size_t, const char*)>& all_gather) {
+    const uint64_t l_recip = lig::lin_reciprocal(c->l);
+    for (size_t w = 0; w + 1 < D->wave_begin.size(); w++) {
+        if (const uint32_t B = D->block[w]) {
+            const uint32_t n_out = D->export_begin[w + 1] - D->export_begin[w];
+            hipLaunchKernelGGL(lig::k_derive_export, dim3(std::min((B + lig::LIN_WG - 1) / lig::LIN_WG, lig::DERIVE_MAX_BLOCKS)), dim3(lig::LIN_WG), 0, st,
+                               D->exports + D->export_begin[w], n_out, B, msgs, c->l, c->k, l_recip, send);
+            HIP_TRY(c, hipGetLastError());
+            TRY(all_gather(send, imported + D->import_begin[w], (size_t)B * 32, "all_gather(derived slots)"));
+        }
+        const uint32_t first = D->wave_begin[w], n_all = D->wave_begin[w + 1] - first, n_light = D->wave_light[w], n_heavy = n_all - n_light;
+        const uint32_t light_blocks = std::min((n_light + lig::LIN_WG - 1) / lig::LIN_WG, lig::DERIVE_MAX_BLOCKS), heavy_blocks = std::min(n_heavy, lig::DERIVE_MAX_BLOCKS);
+        if (!(light_blocks + heavy_blocks)) continue;
+        hipLaunchKernelGGL(lig::k_derive_wave_shard, dim3(light_blocks + heavy_blocks), dim3(lig::LIN_WG), 0, st, D->targets + first, n_light, n_heavy, light_blocks,
+                           D->terms, msgs, imported, c->l, c->k, l_recip, D->coef_mont);
     }
     HIP_TRY(c, hipGetLastError());
     return LIG_OK;

@@ -140,4 +140,133 @@ inline const char* plan_derived(const lig_linear_system& sys, const uint8_t* kin
     if (sys.n_coefs) out.coefs.assign(sys.coefs, sys.coefs + sys.n_coefs * 32);
     return nullptr;
 }
+
+// ---- the same list on a rows shard (lig_shard_rows_set_derived): one rank's program and the exchange schedule of all ranks
+//
+// The rows are dealt over `world` ranks; a target is formed by the rank that was dealt its row, from terms that lie on its own rows (LOCAL
+// terms) and on rows of other ranks (IMPORTED terms, some of them derived there in an earlier wave).  Every rank has the whole list and
+// the deal, so every rank computes the same schedule: E_q(w) = the distinct slots of rank q that a wave-w target of ANOTHER rank reads and
+// that no earlier wave has shipped, ascending.  The exchange of wave w is one all-gather of B(w) = max_q |E_q(w)| elements per rank; a wave
+// with B(w) = 0 has none, on every rank alike.  The import buffer is absolute over the commit: slot E_q(w)[i] lies at
+// import_begin[w] + q * B(w) + i.  A slot is shipped once, in the first wave that reads it across ranks; a derived slot of wave v is read
+// only by waves after v, so its value is final by then.
+
+// one derived slot a rank forms: local row and column of the target, then as DeriveTarget; terms [begin, mid) are local (slot = local row
+// * l + col in the rank's matrix), terms [mid, end) imported (slot = position in the import buffer)
+struct DeriveShardTarget { uint32_t row, col, negate, rhs, begin, mid, end; };
+static_assert(sizeof(DeriveShardTarget) == 28, "the kernel of derive.hip reads these 28 bytes");
+
+// the deal as the plan reads it: per global row the rank that was dealt it and its row index there.  Local rows are in commit order, so
+// the index is the number of earlier rows of the same rank.
+struct DeriveDeal { std::vector<uint32_t> owner, local_of; };
+inline DeriveDeal derive_deal_of(const std::vector<uint32_t>& owner, uint32_t world) {
+    DeriveDeal dl;
+    dl.owner = owner;
+    dl.local_of.resize(owner.size());
+    std::vector<uint32_t> held(world, 0);
+    for (size_t r = 0; r < owner.size(); r++) dl.local_of[r] = held[owner[r]]++;
+    return dl;
+}
+
+struct DeriveShardPlan {
+    uint32_t n_waves = 0, n_exchanges = 0;                 // waves of the whole list; those with B(w) > 0
+    std::vector<uint32_t> wave_begin, wave_light;          // THIS rank's targets per wave, light ones in front (as DerivePlan)
+    std::vector<DeriveShardTarget> targets;
+    std::vector<lig_lin_term> terms;
+    std::vector<uint32_t> block, import_begin;             // B(w); first element of wave w's blocks in the import buffer (+1 entry = its size)
+    // E_q(w) of every rank, global slots: sends[send_begin[q * n_waves + w] .. send_begin[q * n_waves + w + 1])
+    std::vector<uint32_t> send_begin, sends;
+    std::vector<uint32_t> export_begin, exports;           // E_rank(w) as local slots (n_waves + 1 offsets): what k_derive_export reads
+    uint64_t local_terms = 0, imported_terms = 0, n_imports = 0, n_exports = 0;      // n_imports: distinct foreign slots this rank reads
+    uint64_t import_elems() const { return import_begin.empty() ? 0 : import_begin.back(); }
+};
+
+// nullptr = planned, else why not.  P: the accepted program of plan_derived over the whole trace; deal: one entry per row of that trace,
+// every owner < world.
+inline const char* plan_derived_shard(const DerivePlan& P, const DeriveDeal& deal, uint32_t l, uint32_t rank, uint32_t world, DeriveShardPlan& out) {
+    out = DeriveShardPlan{};
+    const uint32_t NW = P.n_waves;
+    out.n_waves = NW;
+    out.wave_begin.assign((size_t)NW + 1, 0);
+    out.wave_light.assign(NW, 0);
+    out.block.assign(NW, 0);
+    out.import_begin.assign((size_t)NW + 1, 0);
+    out.send_begin.assign((size_t)world * NW + 1, 0);
+    out.export_begin.assign((size_t)NW + 1, 0);
+    if (!world || rank >= world) return "rank >= world";
+    const size_t rows = deal.owner.size();
+    auto row_of = [&](uint32_t slot) { return (size_t)(slot / l); };
+    std::unordered_map<uint32_t, uint32_t> position;       // shipped slot -> its place in the import buffer
+    std::vector<std::vector<uint32_t>> per_rank(world);    // the wave in hand: E_q(w)
+    std::vector<std::vector<uint32_t>> sends_of((size_t)world * NW);
+    std::unordered_map<uint32_t, uint8_t> read_here;       // distinct foreign slots of THIS rank's targets
+    for (uint32_t w = 0; w < NW; w++) {
+        for (auto& v : per_rank) v.clear();
+        for (uint32_t p = P.wave_begin[w]; p < P.wave_begin[w + 1]; p++) {
+            const DeriveTarget& tg = P.targets[p];
+            if (row_of(tg.slot) >= rows) return "a target beyond the deal";
+            const uint32_t holder = deal.owner[row_of(tg.slot)];
+            for (uint32_t t = tg.begin; t < tg.end; t++) {
+                const uint32_t s = P.terms[t].slot;
+                if (row_of(s) >= rows) return "a term beyond the deal";
+                const uint32_t q = deal.owner[row_of(s)];
+                if (q >= world) return "a row dealt to a rank >= world";
+                if (q != holder && !position.count(s)) per_rank[q].push_back(s);
+            }
+        }
+        uint64_t widest = 0;
+        for (uint32_t q = 0; q < world; q++) {
+            std::vector<uint32_t>& v = per_rank[q];
+            std::sort(v.begin(), v.end());
+            v.erase(std::unique(v.begin(), v.end()), v.end());
+            widest = std::max<uint64_t>(widest, v.size());
+        }
+        const uint64_t next = (uint64_t)out.import_begin[w] + widest * world;
+        if (next >= (1ull << 32)) return "the exchange needs 2^32 elements or more";
+        out.block[w] = (uint32_t)widest;
+        out.import_begin[w + 1] = (uint32_t)next;
+        if (widest) out.n_exchanges++;
+        for (uint32_t q = 0; q < world; q++) {
+            for (size_t i = 0; i < per_rank[q].size(); i++) position.emplace(per_rank[q][i], (uint32_t)(out.import_begin[w] + (uint64_t)q * widest + i));
+            sends_of[(size_t)q * NW + w] = per_rank[q];
+        }
+        // this rank's share of the wave: what it sends, then what it forms
+        for (const uint32_t s : per_rank[rank]) out.exports.push_back(deal.local_of[row_of(s)] * l + s % l);
+        out.export_begin[w + 1] = (uint32_t)out.exports.size();
+        for (uint32_t p = P.wave_begin[w]; p < P.wave_begin[w + 1]; p++) {
+            const DeriveTarget& tg = P.targets[p];
+            if (deal.owner[row_of(tg.slot)] != rank) continue;
+            DeriveShardTarget st;
+            st.row = deal.local_of[row_of(tg.slot)];
+            st.col = tg.slot % l;
+            st.negate = tg.negate;
+            st.rhs = tg.rhs;
+            st.begin = (uint32_t)out.terms.size();
+            for (uint32_t t = tg.begin; t < tg.end; t++) {
+                const lig_lin_term tm = P.terms[t];
+                if (deal.owner[row_of(tm.slot)] == rank) out.terms.push_back(lig_lin_term{deal.local_of[row_of(tm.slot)] * l + tm.slot % l, tm.coef});
+            }
+            st.mid = (uint32_t)out.terms.size();
+            for (uint32_t t = tg.begin; t < tg.end; t++) {
+                const lig_lin_term tm = P.terms[t];
+                if (deal.owner[row_of(tm.slot)] == rank) continue;
+                out.terms.push_back(lig_lin_term{position.at(tm.slot), tm.coef});      // (shipped in this wave at the latest)
+                read_here.emplace(tm.slot, 1);
+            }
+            st.end = (uint32_t)out.terms.size();
+            out.local_terms += st.mid - st.begin;
+            out.imported_terms += st.end - st.mid;
+            if (p - P.wave_begin[w] < P.wave_light[w]) out.wave_light[w]++;
+            out.targets.push_back(st);
+        }
+        out.wave_begin[w + 1] = (uint32_t)out.targets.size();
+    }
+    for (size_t i = 0; i < sends_of.size(); i++) {
+        out.sends.insert(out.sends.end(), sends_of[i].begin(), sends_of[i].end());
+        out.send_begin[i + 1] = (uint32_t)out.sends.size();
+    }
+    out.n_imports = read_here.size();
+    out.n_exports = out.exports.size();
+    return nullptr;
+}
 }  // namespace lig

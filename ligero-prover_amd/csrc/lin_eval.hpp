@@ -32,26 +32,36 @@ static __device__ __forceinline__ fr diag_accumulate(const fr& acc, const lig_li
     if (row == LIN_NOT_LOCAL) return acc;
     return diag_apply(acc, tm.coef, fr_load(msgs + (size_t)row * k + col), coef_mont);
 }
+// a term list whose `slot` is already an element of `msgs` -- a rank's import buffer on a rows shard (derive.hip): no row, no division
+struct DiagFlat {};
+static __device__ __forceinline__ fr diag_accumulate(const fr& acc, const lig_lin_term tm, const fr* __restrict__ msgs, uint32_t, uint32_t, uint64_t,
+                                                     const fr* __restrict__ coef_mont, const DiagFlat) {
+    return diag_apply(acc, tm.coef, fr_load(msgs + tm.slot), coef_mont);
+}
 // the canonical value a coefficient index stands for
 static __device__ __forceinline__ fr diag_coef_value(uint32_t coef, const fr* __restrict__ coef_mont) {
     if (coef == LIG_COEF_ONE) return diag_one();
     if (coef == LIG_COEF_NEG_ONE) return fr_neg(diag_one());
     return fr_montmul(fr_load(coef_mont + coef), diag_one());             // (a R) * 1 / R = a
 }
-// the two walks over the terms [b, e) of one constraint: one lane; or the lanes of a workgroup striding the segment, then the fixed tree
+// the one walk over terms of a constraint: acc += the terms b, b + step, ... below e, read through `rows` from `msgs`.  A sum over two
+// sources (a rank's matrix and its import buffer, derive.hip) is two calls, the second continuing the first's acc.
+template <class Rows>
+static __device__ __forceinline__ fr diag_walk(fr acc, uint32_t b, uint32_t e, uint32_t step, const lig_lin_term* __restrict__ terms, const fr* __restrict__ msgs,
+                                               uint32_t l, uint32_t k, uint64_t l_recip, const fr* __restrict__ coef_mont, const Rows rows) {
+    for (uint32_t t = b; t < e; t += step) acc = diag_accumulate(acc, terms[t], msgs, l, k, l_recip, coef_mont, rows);
+    return acc;
+}
+// its two uses over the terms [b, e) of one constraint: one lane; or the lanes of a workgroup striding the segment, then the fixed tree
 // (valid in thread 0; reached by all lanes of the workgroup)
 template <class Rows>
 static __device__ __forceinline__ fr diag_sum_lane(uint32_t b, uint32_t e, const lig_lin_term* __restrict__ terms, const fr* __restrict__ msgs, uint32_t l, uint32_t k,
                                                    uint64_t l_recip, const fr* __restrict__ coef_mont, const Rows rows) {
-    fr acc = fr_zero();
-    for (uint32_t t = b; t < e; t++) acc = diag_accumulate(acc, terms[t], msgs, l, k, l_recip, coef_mont, rows);
-    return acc;
+    return diag_walk(fr_zero(), b, e, 1, terms, msgs, l, k, l_recip, coef_mont, rows);
 }
 template <class Rows>
 static __device__ __forceinline__ fr diag_sum_block(uint32_t b, uint32_t e, const lig_lin_term* __restrict__ terms, const fr* __restrict__ msgs, uint32_t l, uint32_t k,
                                                     uint64_t l_recip, const fr* __restrict__ coef_mont, const Rows rows, fr* sh) {
-    fr acc = fr_zero();
-    for (uint32_t t = b + threadIdx.x; t < e; t += LIN_WG) acc = diag_accumulate(acc, terms[t], msgs, l, k, l_recip, coef_mont, rows);
-    return lin_block_sum(acc, sh);
+    return lin_block_sum(diag_walk(fr_zero(), b + threadIdx.x, e, LIN_WG, terms, msgs, l, k, l_recip, coef_mont, rows), sh);
 }
 }  // namespace lig

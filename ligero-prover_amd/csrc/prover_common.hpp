@@ -480,6 +480,19 @@ int lig_internal_derive_create(lig_ctx* c, const lig_linear_system* sys, const u
                                uint64_t n, lig_derive** out, lig_derived_info* info);
 void lig_internal_derive_destroy(lig_derive* D);
 int lig_internal_derive_run(lig_ctx* c, const lig_derive* D, fr* msgs, hipStream_t st);
+// the same on a rows shard (lig_shard_rows_set_derived): owner = the rank of every row of the whole trace (the deal); create = the check above +
+// plan_derived_shard for `rank`, the rank's program on the device, and what the shard has to provide: a send block of send_elems and an
+// import buffer of import_elems elements.  run = per wave export kernel + all_gather (only for a wave in which something crosses ranks) +
+// wave kernel on `st`.  count = the numbers alone, host only.
+struct lig_derive_shard;
+int lig_internal_derive_shard_count(const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, uint32_t l, const uint8_t* elem_bytes, const lig_derived_slot* d,
+                                    uint64_t n, const std::vector<uint32_t>& owner, uint32_t rank, uint32_t world, lig_derived_shard_info* info);
+int lig_internal_derive_shard_create(lig_ctx* c, const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, const uint8_t* elem_bytes, const lig_derived_slot* d,
+                                     uint64_t n, const std::vector<uint32_t>& owner, uint32_t rank, uint32_t world, lig_derive_shard** out, uint64_t* send_elems,
+                                     uint64_t* import_elems, lig_derived_shard_info* info);
+void lig_internal_derive_shard_destroy(lig_derive_shard* D);
+int lig_internal_derive_shard_run(lig_ctx* c, const lig_derive_shard* D, fr* msgs, fr* send, fr* imported, hipStream_t st,
+                                  const std::function<int(const void*, void*, size_t, const char*)>& all_gather);
 // lig_rows_diagnose (diagnose.hip): the residual of every linear constraint of `sys` (NULL: none; it has passed lig_linear_check) and of every
 // (quadratic term, column < l) over the committed rows x k matrix `msgs`; tri_dev = the trace's quadratic terms, 3 row indices each.
 // Blocking, on the context's main stream; waits the way a proof does (lig_internal_wait_stream, prover.hip).

@@ -73,6 +73,14 @@ struct lig_shard {
     // randomness matrix it is formed into per proof; both survive lig_shard_rows_restart
     lig_linear* linear = nullptr;
     fr* rands_lin = nullptr;
+    // derived slots (lig_shard_rows_set_derived): this rank's program (derive.hip), the send block of a wave's all-gather and the import
+    // buffer of a commit; survive lig_shard_rows_restart.  The buffers only grow: one a peer may still have mapped is never freed before
+    // lig_shard_destroy has told the communicator (derive_retired).
+    lig_derive_shard* derive = nullptr;
+    fr *derive_send = nullptr, *derive_import = nullptr;
+    uint64_t derive_send_cap = 0, derive_import_cap = 0;
+    std::vector<void*> derive_retired;
+    std::vector<uint8_t> elem_bytes_all;       // lig_rows_job.elem_bytes of ALL rows (empty: none given): what a list of derived slots is checked against
     bool used_comm = false;                    // a collective has been issued with buffers of this shard as send buffers
     bool exchange_even_alone = false;          // LIG_SHARD_FORCE_EXCHANGE: run pack + all-to-all with world == 1 too (tests)
     size_t chunk_rows(size_t g) const { return g < G ? gb[g + 1] - gb[g] : 0; }
@@ -311,6 +319,7 @@ void lig_shard_destroy(lig_shard* S) {
     }
     S->flags.release();
     lig_internal_linear_destroy(S->linear);
+    lig_internal_derive_shard_destroy(S->derive);
     (void)hipFree(S->rands_lin);
     // the send buffers below are about to be freed.  forget() may be a host collective (comm_ipc): a shard that fails before its
     // first collective (a local error in *_begin / *_prepare) has exported nothing and must not wait for peers that are not there
@@ -319,8 +328,9 @@ void lig_shard_destroy(lig_shard* S) {
     for (void* p : {(void*)S->msgs, (void*)S->cw, (void*)S->maskcw, (void*)S->send, (void*)S->recv, (void*)S->randb, (void*)S->rhalf, (void*)S->acc,
                     (void*)S->parts, (void*)S->accp, (void*)S->accg, (void*)S->dots, (void*)S->smp, (void*)S->smpg, (void*)S->sha_state,
                     (void*)S->leaves_slice, (void*)S->leaves, (void*)S->nodes, (void*)S->tri_dev, (void*)S->coef_dev, (void*)S->src_off_dev,
-                    (void*)S->widths_dev, (void*)S->packed_dev, (void*)S->prod.dev, (void*)S->wide.mixed.dev, (void*)S->wide.wide_dev, (void*)S->wide.flag_dev})
+                    (void*)S->widths_dev, (void*)S->packed_dev, (void*)S->prod.dev, (void*)S->wide.mixed.dev, (void*)S->wide.wide_dev, (void*)S->wide.flag_dev, (void*)S->derive_send, (void*)S->derive_import})
         (void)hipFree(p);
+    for (void* p : S->derive_retired) (void)hipFree(p);
     for (int i = 0; i < 2; i++)
         for (hipEvent_t e : {S->ev_enc[i], S->ev_comm[i], S->ev_hash[i]}) if (e) (void)hipEventDestroy(e);
     (void)hipHostFree(S->h_proof); (void)hipHostFree(S->h_enc); (void)hipHostFree(S->h_nodes); (void)hipHostFree(S->h_small);
@@ -453,13 +463,31 @@ static int shard_stage1(lig_shard* S, lig_proof_info* info) {
     TRY(lig_internal_encode_generic(c, mask, s_hash));
     TRY(lig_internal_encode_2k_rows(c, mlin, 2, s_hash));
     const bool exchange = W > 1 || S->exchange_even_alone;
+    // Derived slots (lig_shard_rows_set_derived): the waves read slots of any local row and, through the exchange, of other ranks' rows, so
+    // every local row has to be in place first.  Rows that arrive round by round: every round's arrival and pads first -- such a trace gives
+    // up the upload / encode overlap.  Per wave on the main stream: export kernel, all-gather (both only when something crosses ranks in
+    // that wave, on every rank alike), wave kernel.  Without a list nothing here is queued.
+    const bool derive = S->derive != nullptr;
+    if (derive) {
+        if (S->rows_by_thread)
+            for (size_t cidx = 0; cidx < S->rounds; cidx++) {
+                HIP_TRY(c, hipStreamWaitValue32(s, S->flags.dev + cidx, S->up.seq, hipStreamWaitValueGte, 0xffffffffu));
+                draw_pads(S->lrow0[cidx], S->lrow0[cidx + 1]);
+            }
+        hipEvent_t e0 = nullptr, e1 = nullptr;                    // lig_profile_read_launches(rows_in_launch = 0): the waves and exchanges of this commit
+        TRY(lig_internal_profile_bracket(c, 0, &e0, &e1));
+        if (e0) HIP_TRY(c, hipEventRecord(e0, s));
+        TRY(lig_internal_derive_shard_run(c, S->derive, S->msgs, S->derive_send, S->derive_import, s,
+                                          [&](const void* src, void* dst, size_t bytes, const char* what) -> int { return all_gather(src, dst, bytes, s, what); }));
+        if (e1) HIP_TRY(c, hipEventRecord(e1, s));
+    }
     const size_t blk_elems = CAP * ncol;                         // one block of the exchange buffers (per rank pair and round)
     uint64_t absorbed = 0;
     for (size_t cidx = 0; cidx < S->rounds; cidx++) {
         const int pb = (int)(cidx & 1);
         const size_t lb = S->lrow0[cidx], nb = S->lrow0[cidx + 1] - lb;
         fr* sendb = S->send + (size_t)pb * CAP * n; fr* recvb = S->recv + (size_t)pb * CAP * n;
-        if (S->rows_by_thread) {                              // my c-th chunk has arrived from the host
+        if (S->rows_by_thread && !derive) {                   // my c-th chunk has arrived from the host
             HIP_TRY(c, hipStreamWaitValue32(s, S->flags.dev + cidx, S->up.seq, hipStreamWaitValueGte, 0xffffffffu));
             draw_pads(lb, lb + nb);
         }
@@ -834,6 +862,7 @@ int lig_shard_rows_begin(lig_ctx* c, const lig_rows_job* job, uint32_t rank, uin
     const size_t R = S->R = S->rows.size();
     S->lin_pos.assign(R + 1, 0); S->wit_pos.assign(R + 1, 0);
     for (size_t r = 0; r < R; r++) S->lin_pos[r + 1] = S->lin_pos[r] + S->rows[r].data;
+    if (job->elem_bytes) S->elem_bytes_all.assign(job->elem_bytes, job->elem_bytes + R);
     int rc = shard_alloc(c, rank, world, S);
     if (rc == LIG_OK && (job->elem_bytes || lig::job_wide_per_row(*job))) {
         // the narrow row format: every row of the job is checked as lig_rows_begin does, the plan is of the local rows; the staging
@@ -1195,6 +1224,64 @@ int lig_shard_rows_set_linear_values(lig_shard* S, const uint8_t* coefs, uint64_
     if (!S->from_rows) FAIL(c, LIG_E_STATE, "lig_shard_rows_set_linear_values: not a rows shard (lig_shard_rows_begin)");
     if (!S->linear) FAIL(c, LIG_E_STATE, "lig_shard_rows_set_linear_values: no linear system is set (lig_shard_rows_set_linear)");
     return lig_internal_linear_set_values(c, S->linear, coefs, n_coefs, c->stream2);
+}
+// the rank that was dealt every row: chunk g of the deal belongs to rank g mod W
+static std::vector<uint32_t> shard_owner(const std::vector<size_t>& gb, uint32_t W, size_t R) {
+    std::vector<uint32_t> owner(R, 0);
+    for (size_t g = 0; g + 1 < gb.size(); g++)
+        for (size_t r = gb[g]; r < gb[g + 1]; r++) owner[r] = (uint32_t)(g % W);
+    return owner;
+}
+// Derived slots on a rows shard (derive.hip): the list of the WHOLE trace; every rank passes the same one (a contract, like the system of
+// lig_shard_rows_set_linear -- the exchange schedule is computed from it).  No collective here; a refused list changes nothing.  (No derive
+// kernel is in flight: lig_shard_rows_commit returns only after stage 1 has drained.)
+int lig_shard_rows_set_derived(lig_shard* S, const lig_linear_system* sys, const lig_derived_slot* d, uint64_t n, lig_derived_shard_info* info) {
+    if (!S) return LIG_E_ARG;
+    lig_ctx* c = S->c;
+    CHECK_CTX(c);
+    if (S->poisoned) FAIL(c, LIG_E_STATE, "lig_shard_rows_set_derived: the shard is poisoned (work queued behind a failed collective never drained): destroy it");
+    if (!S->from_rows) FAIL(c, LIG_E_STATE, "lig_shard_rows_set_derived: not a rows shard (lig_shard_rows_begin)");
+    if (info && info->struct_bytes < sizeof(lig_derived_shard_info)) FAIL(c, LIG_E_ARG, "lig_shard_rows_set_derived: lig_derived_shard_info.struct_bytes too small");
+    if (!d || !n) {
+        lig_internal_derive_shard_destroy(S->derive);
+        S->derive = nullptr;
+        if (info) { const uint32_t sb = info->struct_bytes; std::memset(info, 0, sizeof *info); info->struct_bytes = sb; }
+        return LIG_OK;
+    }
+    lig_derive_shard* D = nullptr;
+    uint64_t send_elems = 0, import_elems = 0;
+    lig_derived_shard_info mine;
+    mine.struct_bytes = sizeof mine;
+    TRY(lig_internal_derive_shard_create(c, sys, kinds_of(S->rows).data(), S->R, S->elem_bytes_all.empty() ? nullptr : S->elem_bytes_all.data(), d, n,
+                                         shard_owner(S->gb, S->world, S->R), S->rank, S->world, &D, &send_elems, &import_elems, &mine));
+    auto grow = [&](fr** buf, uint64_t* cap, uint64_t elems) -> int {
+        if (elems <= *cap) return LIG_OK;
+        fr* fresh = nullptr;
+        const hipError_t e = hipMalloc((void**)&fresh, elems * 32);
+        if (e != hipSuccess) { (void)hipGetLastError(); FAIL(c, LIG_E_NOMEM, std::string("lig_shard_rows_set_derived: exchange buffers: ") + hipGetErrorString(e)); }
+        if (*buf) S->derive_retired.push_back(*buf);
+        *buf = fresh; *cap = elems;
+        return LIG_OK;
+    };
+    int rc = grow(&S->derive_send, &S->derive_send_cap, send_elems);
+    if (rc == LIG_OK) rc = grow(&S->derive_import, &S->derive_import_cap, import_elems);
+    if (rc != LIG_OK) { const std::string why = c->err; lig_internal_derive_shard_destroy(D); c->err = why; return rc; }
+    lig_internal_derive_shard_destroy(S->derive);
+    S->derive = D;
+    if (info) { const uint32_t sb = info->struct_bytes; std::memset(info, 0, sizeof *info); std::memcpy(info, &mine, sizeof mine); info->struct_bytes = sb; }
+    return LIG_OK;
+}
+// host only: the numbers of lig_shard_rows_set_derived from the deal alone
+int lig_derived_shard_count(const lig_linear_system* sys, const uint8_t* kinds, uint64_t rows, uint32_t l, const uint8_t* elem_bytes, const lig_derived_slot* d,
+                            uint64_t n, uint32_t rank, uint32_t world, lig_derived_shard_info* info) {
+    if (!world || rank >= world || !info || info->struct_bytes < sizeof(lig_derived_shard_info)) return LIG_E_ARG;
+    if (lig_linear_check(sys, kinds, rows, l) != LIG_OK) return LIG_E_ARG;      // (kinds are read below only for a system it accepts)
+    std::vector<RowDesc> rd(rows);
+    for (uint64_t r = 0; r < rows; r++) rd[r] = RowDesc{(uint8_t)(kinds[r] & 0x7f), 0};
+    size_t rounds = 0;
+    std::vector<size_t> gb;
+    shard_chunks(rd, world, rounds, gb);
+    return lig_internal_derive_shard_count(sys, kinds, rows, l, elem_bytes, d, n, shard_owner(gb, world, rows), rank, world, info);
 }
 int lig_shard_rows_linear_stats(const lig_shard* S, uint64_t* local_terms, uint64_t* sampled_constraints) {
     if (!S || !local_terms || !sampled_constraints) return LIG_E_ARG;
