@@ -675,13 +675,25 @@ int lig_rows_untouched_slots(lig_trace *trace, const lig_linear_system *sys, int
  *   record).  The other terms may lie on any LINEAR / QX / QY / QZ row of the trace: rows behind t's row, LIG_ELEM_PRODUCT rows, other
  *   derived slots.  A slot derived from derived slots belongs to a later WAVE: wave = 1 + the largest wave among its derived terms (0 for
  *   a slot that is not derived), computed on the host; at most LIG_DERIVE_MAX_WAVES.
- * lig_derived_check: host only, no context.  lig_linear_check(sys, kinds, rows, l) first; then LIG_E_ARG for: a slot listed twice; a
- * constraint >= n_constraints; a target absent from its constraint or present twice; a target whose coefficient is a table index (even
- * one whose value is 1); a cycle; more than LIG_DERIVE_MAX_WAVES waves; a target on a LIG_ELEM_PRODUCT row; a target that is an operand
- * slot of a LIG_ELEM_PRODUCT row -- column i of the QX or QY row directly in front of one: the product is formed from the PACKED operand
- * rows and would not see the derived value.  elem_bytes: as in lig_rows_job (one per row), NULL: no row is derived.  d may be in any
- * order; n == 0 is accepted (no wave).  wave_out (n entries, or NULL) <- the wave of d[i]; *info (or NULL; struct_bytes set by the
- * caller) <- n_slots = n, n_terms = the OTHER terms of all defining constraints, n_waves.
+ *   A PRODUCT ENTRY {slot, LIG_DERIVED_PRODUCT} names column i < l of a LIG_ELEM_PRODUCT row r (slot = r * l + i).  Its committed value is
+ *       w[r * l + i] = w[(r - 2) * l + i] * w[(r - 1) * l + i] mod p, canonical,
+ *   read from the EXPANDED matrix in wave order -- so the records of mixed operand rows and operands derived in earlier waves are seen --
+ *   and it overwrites what the row's own pass wrote there from the packed sources.  With it the two mechanisms compose: column i of the
+ *   QX / QY row in front of a LIG_ELEM_PRODUCT row may be a derived slot IF the list also holds the product entry of column i of that
+ *   row.  t = eval(a + b); u = t * c; v = eval(u + d): list t with its constraint, u as a product entry, v with its constraint -- three
+ *   waves, and only a, b, c, d are shipped.  One wave numbering covers both kinds: a product entry is in wave 1 + max(wave(x_i),
+ *   wave(y_i)); one whose operands are both shipped is accepted in wave 1 and re-forms the same value; a target that reads a listed
+ *   product slot is in a later wave than it.
+ * lig_derived_check: host only, no context.  lig_linear_check(sys, kinds, rows, l) first; then LIG_E_ARG for: a slot listed twice (two
+ * entries of either kind); a constraint >= n_constraints; a target absent from its constraint or present twice; a target whose
+ * coefficient is a table index (even one whose value is 1); a cycle, also one through a product entry (x_i defined by a constraint that
+ * reads z_i); more than LIG_DERIVE_MAX_WAVES waves; a linear target on a LIG_ELEM_PRODUCT row; a target that is an operand slot of a
+ * LIG_ELEM_PRODUCT row -- column i of the QX or QY row directly in front of one -- WITHOUT the product entry of column i of that row: the
+ * row's own pass forms the product from the PACKED operand rows and would not see the derived value; a product entry on anything but a
+ * data slot of a row whose elem_bytes is LIG_ELEM_PRODUCT (elem_bytes == NULL, a LINEAR row, a shipped QZ row).  elem_bytes: as in
+ * lig_rows_job (one per row), NULL: no row is derived.  d may be in any order; n == 0 is accepted (no wave).  wave_out (n entries, or
+ * NULL) <- the wave of d[i], product entries included; *info (or NULL; struct_bytes set by the caller) <- n_slots = n, n_terms = the
+ * OTHER terms of all defining constraints + 2 per product entry, n_waves.
  * lig_rows_set_derived: runs that check against the trace's kinds and widths (LIG_E_ARG, nothing launched, the previous list stays in
  * force and the trace usable), then COPIES what it needs before it returns: the terms of the n defining constraints, their right-hand-side
  * table entries, and the table values of sys->coefs AS PASSED (converted to Montgomery form on the device once per call); the rest of sys
@@ -701,11 +713,12 @@ int lig_rows_untouched_slots(lig_trace *trace, const lig_linear_system *sys, int
  *   The prover's valid_linear CANNOT fail on a defining constraint (as valid_quad is vacuous for a LIG_ELEM_PRODUCT triple): a caller whose
  *   own evaluation would have been wrong now proves a different w, and the OTHER constraints on that slot fail instead.
  *   Deterministic: one lane (a workgroup with a fixed summation tree for a constraint with more than 64 other terms) per target, no
- *   atomic on a field element: the same bytes on every run.
+ *   atomic on a field element: the same bytes on every run.  The product entries of a wave are one more launch, one lane per entry.
  * The sharded entry: lig_shard_rows_set_derived, below lig_shard_rows_set_linear.  Not done: per-chunk reach, so that a chunk waits only
- * for the rows its derived slots read; derived operands of LIG_ELEM_PRODUCT rows.
+ * for the rows its derived slots read; product entries on shipped QZ rows.
  * The new structs version themselves with struct_bytes; they are not part of lig_abi_sizes (LIG_ABI_STRUCTS stays 6). */
 enum { LIG_DERIVE_MAX_WAVES = 16 };
+#define LIG_DERIVED_PRODUCT 0xFFFFFFFFu   /* lig_derived_slot.constraint: a product entry */
 typedef struct { uint32_t slot, constraint; } lig_derived_slot;                                                     /* 8 bytes */
 typedef struct { uint32_t struct_bytes, reserved; uint64_t n_slots, n_terms; uint32_t n_waves, reserved2; } lig_derived_info;   /* 32 bytes */
 int lig_derived_check(const lig_linear_system *sys, const uint8_t *kinds, uint64_t rows, uint32_t l, const uint8_t *elem_bytes /* NULL ok */,
@@ -860,6 +873,9 @@ int lig_linear_shard_count(const lig_linear_system *sys, const uint8_t *kinds, u
  *   addressed absolutely over the commit.  A wave with B(w) = 0 issues no collective, on every rank alike: a list whose constraints are
  *   row-local (a machine word recomposed from bits of its own row) exchanges nothing.  Field addition is exact: the regrouped sum gives
  *   the bytes of lig_rows_set_derived.
+ *   A product entry (LIG_DERIVED_PRODUCT) is formed by the rank that holds its row: the deal never splits a triple, so both operands are
+ *   local and it never imports.  A re-formed slot that a target of another rank reads is sent in the first wave that reads it across
+ *   ranks, a later wave than its own.  local_targets counts it, local_terms counts it as 2.
  *   WHERE  in lig_shard_rows_commit, on the main stream, before the first round's encode: per wave the export kernel and the all-gather
  *          (both only when B(w) > 0), then the wave kernel, which stores into the rank's local rows; the pads are not touched.  A failed
  *          collective takes the path of every other collective of the commit (LIG_E_STATE, possibly a poisoned shard).  Host rows that

@@ -198,7 +198,10 @@ public:
     // carries there (the driver writes 0, so a bit row stays a bit row).  In pass 1, before commit(); sys and d are copied (sys need
     // not be the system of set_linear_system); kept across reset() for the next proof of the same shape, where the list stays
     // resident on the trace -- for other right-hand sides call it again; n == 0 removes the list.  Not with shard_over(): a sharded
-    // batcher takes its list through shard_set_derived_slots() below.
+    // batcher takes its list through shard_set_derived_slots() below.  A product a * b of the guest whose operand is an eval() output
+    // (or whose product feeds one): list product_entry(slot of z) next to the operand's own entry -- column i of a derive_products z row
+    // is then re-formed from the committed operands in wave order (lig_hip.h: LIG_DERIVED_PRODUCT).
+    static lig_derived_slot product_entry(uint32_t slot) { return lig_derived_slot{slot, LIG_DERIVED_PRODUCT}; }
     void set_derived_slots(const lig_linear_system& sys, const lig_derived_slot* d, uint64_t n) {
         if (pass_ != 1) throw std::logic_error("hip_row_batcher::set_derived_slots after commit (reset() first)");
         if (sharded_) throw std::logic_error("hip_row_batcher::set_derived_slots: not on a sharded batcher");

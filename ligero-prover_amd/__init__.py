@@ -61,6 +61,7 @@ WIDE_RECORD_BYTES = 36     # lig_rows_job.wide_per_row: a record of a mixed row,
 ARG_I64, ARG_STR, ARG_HEX = 0, 1, 2
 COEF_ONE, COEF_NEG_ONE = 0xFFFFFFFF, 0xFFFFFFFE      # lig_lin_term.coef values that need no table entry (LIG_COEF_ONE / LIG_COEF_NEG_ONE)
 DERIVE_MAX_WAVES = 16      # lig_rows_set_derived: a derived slot may read derived slots of at most this many earlier waves (LIG_DERIVE_MAX_WAVES)
+DERIVED_PRODUCT = 0xFFFFFFFF      # the `constraint` of a product entry (slot, DERIVED_PRODUCT): slot = column i of an ELEM_PRODUCT row, re-formed as x_i * y_i from the matrix in wave order (LIG_DERIVED_PRODUCT)
 
 
 class VerifyInfo(C.Structure):
@@ -156,7 +157,7 @@ def linear_check(system, kinds, l):
 
 
 class DerivedInfo(C.Structure):
-    """lig_derived_info: n_slots = the listed slots, n_terms = the other terms of all defining constraints, n_waves"""
+    """lig_derived_info: n_slots = the listed slots, n_terms = the other terms of all defining constraints + 2 per product entry, n_waves"""
     _fields_ = [("struct_bytes", C.c_uint32), ("reserved", C.c_uint32), ("n_slots", C.c_uint64), ("n_terms", C.c_uint64),
                 ("n_waves", C.c_uint32), ("reserved2", C.c_uint32)]
 
@@ -168,7 +169,8 @@ def _derived_pairs(pairs):
 
 
 def derived_check(system, kinds, l, pairs, elem_bytes=None):
-    """lig_derived_check (host only): pairs = (slot, defining constraint) of every derived slot, any order; elem_bytes: the widths of the
+    """lig_derived_check (host only): pairs = (slot, defining constraint) of every derived slot and (slot, DERIVED_PRODUCT) of every product
+    entry, any order; elem_bytes: the widths of the
     rows job or None -> the wave of every pair (uint32 array, 1 = reads no derived slot); LigError(-1) for a list the rules refuse"""
     kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
     d = _derived_pairs(pairs)
@@ -971,7 +973,8 @@ class Context:
 
     def shard_rows_set_derived(self, shard, system, pairs):
         """lig_shard_rows_set_derived: pairs = (global slot, defining constraint of `system`) of the slots of the WHOLE trace the ranks form
-        themselves from the next shard_rows_commit on; the same on every rank; None or an empty list removes the list -> DerivedShardInfo"""
+        themselves from the next shard_rows_commit on, product entries (slot, DERIVED_PRODUCT) included; the same on every rank; None or an
+        empty list removes the list -> DerivedShardInfo"""
         info = DerivedShardInfo()
         info.struct_bytes = C.sizeof(DerivedShardInfo)
         d = _derived_pairs(pairs) if pairs is not None else np.zeros((0, 2), dtype=np.uint32)
@@ -1168,7 +1171,8 @@ class Context:
 
     def rows_set_derived(self, trace, system, pairs):
         """lig_rows_set_derived: pairs = (slot, defining constraint of `system`) of the slots the library forms itself from the next
-        rows_commit on (whatever the rows carry there is ignored); None or an empty list removes the list -> DerivedInfo"""
+        rows_commit on (whatever the rows carry there is ignored), and (slot, DERIVED_PRODUCT) of the columns of ELEM_PRODUCT rows to re-form
+        from the committed operands in wave order; None or an empty list removes the list -> DerivedInfo"""
         info = DerivedInfo()
         info.struct_bytes = C.sizeof(DerivedInfo)
         d = _derived_pairs(pairs) if pairs is not None else np.zeros((0, 2), dtype=np.uint32)

@@ -17,6 +17,10 @@
 //           then b - sum or sum - b, canonical, two 16-byte stores into the matrix.  A target reads only slots that are not derived or
 //           belong to an earlier wave (launch order on one stream), never a slot written by its own launch.  No atomic on a field
 //           element: the same bytes on every run.  Every index the kernel uses was checked on the host (lig_linear_check, plan_derived).
+//           PRODUCT entries ({slot, LIG_DERIVED_PRODUCT}: column i of a LIG_ELEM_PRODUCT row whose operand x_i or y_i is itself derived, or
+//           whose operand row carries records): k_derive_products, a second launch of the wave, one lane per entry -- two 32-byte loads
+//           from the matrix, fr_mul, one store over what k_expand_product wrote from the packed sources.  One wave numbering covers both
+//           kinds of entry, so t = eval(a + b); u = t * c; v = eval(u + d) is three waves.
 //   shard   lig_shard_rows_set_derived: the same list on a trace dealt over the ranks of a node.  plan_derived_shard (derive_plan.hpp) gives
 //           a rank the targets on its rows, their terms split into LOCAL ones (slot = local row * l + col of the rank's matrix) and
 //           IMPORTED ones (slot = position in the rank's import buffer), and the exchange schedule every rank computes alike.  Per wave,
@@ -24,6 +28,8 @@
 //           block (zero tail), ONE all-gather appends the ranks' blocks to the import buffer -- both only for a wave in which something
 //           crosses ranks -- then k_derive_wave_shard: k_derive_wave with the two sources, the same walk, the same light / heavy split,
 //           tree and block cap, the store into the local row.  Exact field addition: the regrouped sum is the one-GPU sum, byte for byte.
+//           A product entry is formed by the rank that holds its triple (the deal never splits one) with the same k_derive_products over
+//           local rows; it imports nothing, and a re-formed slot another rank reads is exported like any other slot.
 #include "derive_plan.hpp"
 #include "lin_eval.hpp"
 #include "prover_common.hpp"
@@ -56,6 +62,24 @@ __global__ void __launch_bounds__(LIN_WG) k_derive_wave(const DeriveTarget* __re
         if (threadIdx.x == 0) derive_store(tg, sum, msgs, l, k, l_recip, coef_mont);
         __syncthreads();                                                  // sh is reused by the next target
     }
+}
+
+// The product entries of a wave ({slot, LIG_DERIVED_PRODUCT}): lane -> entry (grid-stride), column `col` of the LIG_ELEM_PRODUCT row `row`
+// = w[row - 2][col] * w[row - 1][col], both read from the expanded matrix -- so the records of a mixed operand row and an operand derived
+// in an earlier wave are seen -- and multiplied as k_expand_product multiplies full-width operands (fr_mul: plain x plain -> plain,
+// canonical).  A launch of its own next to the wave's k_derive_wave: an operand is a slot of an earlier wave or not listed, and the slot
+// written is read by later waves only, so neither launch of a wave reads what the other writes.  One GPU and a rank of a shard alike (rows
+// of the matrix in hand: the deal never splits a triple).
+__global__ void __launch_bounds__(LIN_WG) k_derive_products(const DeriveProduct* __restrict__ products, uint32_t n, fr* msgs, uint32_t k) {
+    for (uint64_t i = (uint64_t)blockIdx.x * LIN_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LIN_WG) {
+        const DeriveProduct pr = products[i];
+        fr* const z = msgs + (size_t)pr.row * k + pr.col;
+        fr_store(z, fr_mul(fr_load(z - 2 * (size_t)k), fr_load(z - k)));
+    }
+}
+static void launch_derive_products(hipStream_t st, const DeriveProduct* products, uint32_t n, fr* msgs, uint32_t k) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_derive_products, dim3(std::min((n + LIN_WG - 1) / LIN_WG, DERIVE_MAX_BLOCKS)), dim3(LIN_WG), 0, st, products, n, msgs, k);
 }
 
 // ---- a rows shard
@@ -102,8 +126,9 @@ __global__ void __launch_bounds__(LIN_WG) k_derive_wave_shard(const DeriveShardT
 // the program of one lig_rows_set_derived on the device; nothing writes it after the call has returned
 struct lig_derive {
     int device = 0;
-    std::vector<uint32_t> wave_begin, wave_light;
+    std::vector<uint32_t> wave_begin, wave_light, prod_begin;
     lig::DeriveTarget* targets = nullptr;
+    lig::DeriveProduct* products = nullptr;
     lig_lin_term* terms = nullptr;
     fr* coef_mont = nullptr;
 };
@@ -114,7 +139,7 @@ static void derived_info_fill(lig_derived_info* info, const lig::DerivePlan& p, 
     std::memset(info, 0, sizeof *info);
     info->struct_bytes = struct_bytes;
     info->n_slots = n;
-    info->n_terms = p.terms.size();
+    info->n_terms = p.n_terms();
     info->n_waves = p.n_waves;
 }
 
@@ -132,7 +157,7 @@ extern "C" int lig_derived_check(const lig_linear_system* sys, const uint8_t* ki
 void lig_internal_derive_destroy(lig_derive* D) {
     if (!D) return;
     (void)hipSetDevice(D->device);
-    (void)hipFree(D->targets); (void)hipFree(D->terms); (void)hipFree(D->coef_mont);
+    (void)hipFree(D->targets); (void)hipFree(D->products); (void)hipFree(D->terms); (void)hipFree(D->coef_mont);
     delete D;
 }
 
@@ -145,7 +170,7 @@ int lig_internal_derive_create(lig_ctx* c, const lig_linear_system* sys, const u
     if (const char* why = lig::plan_derived(*sys, kinds, rows, c->l, elem_bytes, d, n, p)) FAIL(c, LIG_E_ARG, std::string("lig_rows_set_derived: ") + why);
     std::unique_ptr<lig_derive, void (*)(lig_derive*)> D(new lig_derive(), lig_internal_derive_destroy);
     D->device = c->device;
-    D->wave_begin = p.wave_begin; D->wave_light = p.wave_light;
+    D->wave_begin = p.wave_begin; D->wave_light = p.wave_light; D->prod_begin = p.prod_begin;
     auto put = [&](void** dev, const void* host, size_t bytes) -> int {      // (blocking copies from pageable memory: the plan goes when this call returns)
         const hipError_t e = hipMalloc(dev, bytes ? bytes : 16);
         if (e != hipSuccess) { (void)hipGetLastError(); FAIL(c, LIG_E_NOMEM, std::string("lig_rows_set_derived: ") + hipGetErrorString(e)); }
@@ -153,6 +178,7 @@ int lig_internal_derive_create(lig_ctx* c, const lig_linear_system* sys, const u
         return LIG_OK;
     };
     TRY(put((void**)&D->targets, p.targets.data(), p.targets.size() * sizeof(lig::DeriveTarget)));
+    TRY(put((void**)&D->products, p.products.data(), p.products.size() * sizeof(lig::DeriveProduct)));
     TRY(put((void**)&D->terms, p.terms.data(), p.terms.size() * sizeof(lig_lin_term)));
     TRY(put((void**)&D->coef_mont, p.coefs.data(), p.coefs.size()));
     lig::launch_lin_coefs_mont(c->stream, D->coef_mont, p.coefs.size() / 32);      // once per call; the waves run on the same stream
@@ -169,9 +195,10 @@ int lig_internal_derive_run(lig_ctx* c, const lig_derive* D, fr* msgs, hipStream
     for (size_t w = 0; w + 1 < D->wave_begin.size(); w++) {
         const uint32_t first = D->wave_begin[w], n_all = D->wave_begin[w + 1] - first, n_light = D->wave_light[w], n_heavy = n_all - n_light;
         const uint32_t light_blocks = std::min((n_light + lig::LIN_WG - 1) / lig::LIN_WG, lig::DERIVE_MAX_BLOCKS), heavy_blocks = std::min(n_heavy, lig::DERIVE_MAX_BLOCKS);
-        if (!(light_blocks + heavy_blocks)) continue;
-        hipLaunchKernelGGL(lig::k_derive_wave, dim3(light_blocks + heavy_blocks), dim3(lig::LIN_WG), 0, st, D->targets + first, n_light, n_heavy, light_blocks,
-                           D->terms, msgs, c->l, c->k, l_recip, D->coef_mont);
+        if (light_blocks + heavy_blocks)
+            hipLaunchKernelGGL(lig::k_derive_wave, dim3(light_blocks + heavy_blocks), dim3(lig::LIN_WG), 0, st, D->targets + first, n_light, n_heavy, light_blocks,
+                               D->terms, msgs, c->l, c->k, l_recip, D->coef_mont);
+        lig::launch_derive_products(st, D->products + D->prod_begin[w], D->prod_begin[w + 1] - D->prod_begin[w], msgs, c->k);
     }
     HIP_TRY(c, hipGetLastError());
     return LIG_OK;
@@ -180,8 +207,9 @@ int lig_internal_derive_run(lig_ctx* c, const lig_derive* D, fr* msgs, hipStream
 // ---- a rows shard: one rank's program of lig_shard_rows_set_derived; nothing writes it after the call has returned
 struct lig_derive_shard {
     int device = 0;
-    std::vector<uint32_t> wave_begin, wave_light, block, import_begin, export_begin;
+    std::vector<uint32_t> wave_begin, wave_light, prod_begin, block, import_begin, export_begin;
     lig::DeriveShardTarget* targets = nullptr;
+    lig::DeriveProduct* products = nullptr;
     lig_lin_term* terms = nullptr;
     uint32_t* exports = nullptr;
     fr* coef_mont = nullptr;
@@ -193,10 +221,10 @@ static void derived_shard_info_fill(lig_derived_shard_info* info, const lig::Der
     std::memset(info, 0, sizeof *info);
     info->struct_bytes = struct_bytes;
     info->n_slots = n;
-    info->n_terms = p.terms.size();
+    info->n_terms = p.n_terms();
     info->n_waves = p.n_waves;
     info->n_exchanges = sp.n_exchanges;
-    info->local_targets = sp.targets.size();
+    info->local_targets = sp.local_targets();
     info->local_terms = sp.local_terms;
     info->imported_terms = sp.imported_terms;
     info->imports = sp.n_imports;
@@ -222,7 +250,7 @@ int lig_internal_derive_shard_count(const lig_linear_system* sys, const uint8_t*
 void lig_internal_derive_shard_destroy(lig_derive_shard* D) {
     if (!D) return;
     (void)hipSetDevice(D->device);
-    (void)hipFree(D->targets); (void)hipFree(D->terms); (void)hipFree(D->exports); (void)hipFree(D->coef_mont);
+    (void)hipFree(D->targets); (void)hipFree(D->products); (void)hipFree(D->terms); (void)hipFree(D->exports); (void)hipFree(D->coef_mont);
     delete D;
 }
 
@@ -235,7 +263,7 @@ int lig_internal_derive_shard_create(lig_ctx* c, const lig_linear_system* sys, c
     if (const char* why = derive_shard_plan(sys, kinds, rows, c->l, elem_bytes, d, n, owner, rank, world, p, sp)) FAIL(c, LIG_E_ARG, std::string("lig_shard_rows_set_derived: ") + why);
     std::unique_ptr<lig_derive_shard, void (*)(lig_derive_shard*)> D(new lig_derive_shard(), lig_internal_derive_shard_destroy);
     D->device = c->device;
-    D->wave_begin = sp.wave_begin; D->wave_light = sp.wave_light; D->block = sp.block; D->import_begin = sp.import_begin; D->export_begin = sp.export_begin;
+    D->wave_begin = sp.wave_begin; D->wave_light = sp.wave_light; D->prod_begin = sp.prod_begin; D->block = sp.block; D->import_begin = sp.import_begin; D->export_begin = sp.export_begin;
     auto put = [&](void** dev, const void* host, size_t bytes) -> int {      // (blocking copies from pageable memory: the plan goes when this call returns)
         const hipError_t e = hipMalloc(dev, bytes ? bytes : 16);
         if (e != hipSuccess) { (void)hipGetLastError(); FAIL(c, LIG_E_NOMEM, std::string("lig_shard_rows_set_derived: ") + hipGetErrorString(e)); }
@@ -243,6 +271,7 @@ int lig_internal_derive_shard_create(lig_ctx* c, const lig_linear_system* sys, c
         return LIG_OK;
     };
     TRY(put((void**)&D->targets, sp.targets.data(), sp.targets.size() * sizeof(lig::DeriveShardTarget)));
+    TRY(put((void**)&D->products, sp.products.data(), sp.products.size() * sizeof(lig::DeriveProduct)));
     TRY(put((void**)&D->terms, sp.terms.data(), sp.terms.size() * sizeof(lig_lin_term)));
     TRY(put((void**)&D->exports, sp.exports.data(), sp.exports.size() * sizeof(uint32_t)));
     TRY(put((void**)&D->coef_mont, p.coefs.data(), p.coefs.size()));
@@ -272,9 +301,10 @@ int lig_internal_derive_shard_run(lig_ctx* c, const lig_derive_shard* D, fr* msg
         }
         const uint32_t first = D->wave_begin[w], n_all = D->wave_begin[w + 1] - first, n_light = D->wave_light[w], n_heavy = n_all - n_light;
         const uint32_t light_blocks = std::min((n_light + lig::LIN_WG - 1) / lig::LIN_WG, lig::DERIVE_MAX_BLOCKS), heavy_blocks = std::min(n_heavy, lig::DERIVE_MAX_BLOCKS);
-        if (!(light_blocks + heavy_blocks)) continue;
-        hipLaunchKernelGGL(lig::k_derive_wave_shard, dim3(light_blocks + heavy_blocks), dim3(lig::LIN_WG), 0, st, D->targets + first, n_light, n_heavy, light_blocks,
-                           D->terms, msgs, imported, c->l, c->k, l_recip, D->coef_mont);
+        if (light_blocks + heavy_blocks)
+            hipLaunchKernelGGL(lig::k_derive_wave_shard, dim3(light_blocks + heavy_blocks), dim3(lig::LIN_WG), 0, st, D->targets + first, n_light, n_heavy, light_blocks,
+                               D->terms, msgs, imported, c->l, c->k, l_recip, D->coef_mont);
+        lig::launch_derive_products(st, D->products + D->prod_begin[w], D->prod_begin[w + 1] - D->prod_begin[w], msgs, c->k);
     }
     HIP_TRY(c, hipGetLastError());
     return LIG_OK;

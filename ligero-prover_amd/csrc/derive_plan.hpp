@@ -1,6 +1,8 @@
 // derive_plan.hpp -- the host-side rules of derived slots (lig_hip.h: lig_derived_check, lig_rows_set_derived): which lists are accepted,
 // the wave of every listed slot, and the compact constraint-major program the kernels of derive.hip walk -- per wave the targets (slot,
 // sign, right-hand-side index, term range) and their OTHER terms as (slot, coefficient index) -- next to a copy of the coefficient table.
+// An entry {slot, LIG_DERIVED_PRODUCT} is a PRODUCT entry: column i of a LIG_ELEM_PRODUCT row, which reads the two operand slots in front
+// of it instead of the terms of a constraint; it shares the wave numbering and is laid out in a list of its own (DeriveProduct).
 // The system has passed lig_linear_check against the same kinds: every term's slot lies on a LINEAR / QX / QY / QZ row below `rows`,
 // every coefficient index is one of the two specials or < n_coefs, rows * l < 2^32.
 // Host only: nothing but lig_hip.h and the standard library, so that a plain host compiler builds it (tests/cpp/derive_plan_prog.cpp).
@@ -26,15 +28,25 @@ static constexpr uint32_t DERIVE_RHS_ZERO = 0xFFFFFFFDu;      // DeriveTarget.rh
 struct DeriveTarget { uint32_t slot, negate, rhs, begin, end; };
 static_assert(sizeof(DeriveTarget) == 20, "the kernel of derive.hip reads these 20 bytes");
 
+// one PRODUCT entry of the program ({slot, LIG_DERIVED_PRODUCT}): column `col` of the LIG_ELEM_PRODUCT row `row`, re-formed from the
+// expanded matrix as w[row - 2][col] * w[row - 1][col].  row is global in DerivePlan and local in DeriveShardPlan (the deal never splits
+// a triple: the operand rows are the two local rows in front).  Checked here: 2 <= row < rows, col < l.
+struct DeriveProduct { uint32_t row, col; };
+static_assert(sizeof(DeriveProduct) == 8, "the kernel of derive.hip reads these 8 bytes");
+
 struct DerivePlan {
     uint32_t n_waves = 0;
-    std::vector<uint32_t> wave_of;        // per entry of the caller's list: 1 .. n_waves
+    std::vector<uint32_t> wave_of;        // per entry of the caller's list, linear and product alike: 1 .. n_waves
     // wave w (0-based) owns targets [wave_begin[w], wave_begin[w + 1]): first its wave_light[w] targets with at most DERIVE_LANE_MAX other
-    // terms, then the heavy ones; within each class in the order of the caller's list
+    // terms, then the heavy ones; within each class in the order of the caller's list.  Linear entries only.
     std::vector<uint32_t> wave_begin, wave_light;
     std::vector<DeriveTarget> targets;
     std::vector<lig_lin_term> terms;      // the other terms of every target, in the order of its constraint
     std::vector<uint8_t> coefs;           // sys.coefs as passed: n_coefs x 32 bytes, canonical
+    // the product entries: wave w owns products [prod_begin[w], prod_begin[w + 1]), in the order of the caller's list (n_waves + 1 offsets)
+    std::vector<uint32_t> prod_begin;
+    std::vector<DeriveProduct> products;
+    uint64_t n_terms() const { return terms.size() + 2 * (uint64_t)products.size(); }      // lig_derived_info.n_terms: a product reads its two operands
 };
 
 // nullptr = accepted (out is the program), else why not (out is unspecified).  d may be in any order; n == 0 is the empty program.
@@ -43,6 +55,7 @@ inline const char* plan_derived(const lig_linear_system& sys, const uint8_t* kin
                                 const lig_derived_slot* d, uint64_t n, DerivePlan& out) {
     out = DerivePlan{};
     out.wave_begin.assign(1, 0);
+    out.prod_begin.assign(1, 0);
     if (!n) return nullptr;
     if (!d) return "null list";
     if (n >= (1ull << 32)) return "too many derived slots";
@@ -50,8 +63,23 @@ inline const char* plan_derived(const lig_linear_system& sys, const uint8_t* kin
     index.reserve((size_t)n * 2);
     for (uint64_t i = 0; i < n; i++)
         if (!index.emplace(d[i].slot, (uint32_t)i).second) return "a slot is listed twice";
-    std::vector<uint32_t> at(n);                        // the term of the defining constraint that is the target
+    auto is_product = [&](uint64_t i) { return d[i].constraint == LIG_DERIVED_PRODUCT; };
+    // is column `col` of the LIG_ELEM_PRODUCT row `row` re-formed by a product entry of this list?
+    auto reformed = [&](uint64_t row, uint32_t col) {
+        const auto it = index.find((uint32_t)(row * l + col));
+        return it != index.end() && is_product(it->second);
+    };
+    std::vector<uint32_t> at(n);                        // the term of the defining constraint that is the target (linear entries)
     for (uint64_t i = 0; i < n; i++) {
+        const uint64_t row = d[i].slot / l;
+        const uint32_t col = d[i].slot % l;
+        if (is_product(i)) {
+            if (row >= rows) return "a product entry beyond the rows";
+            if (!elem_bytes || elem_bytes[row] != LIG_ELEM_PRODUCT) return "a product entry on a row that is not LIG_ELEM_PRODUCT";
+            if (row < 2 || (kinds[row] & 0x7f) != LIG_ROW_QZ || (kinds[row - 2] & 0x7f) != LIG_ROW_QX || (kinds[row - 1] & 0x7f) != LIG_ROW_QY)
+                return "a product entry on a row that is not the QZ row of a triple";
+            continue;
+        }
         if (d[i].constraint >= sys.n_constraints) return "a defining constraint is not a constraint of the system";
         const uint32_t b = sys.term_begin[d[i].constraint], e = sys.term_begin[d[i].constraint + 1];
         uint32_t hits = 0;
@@ -60,36 +88,41 @@ inline const char* plan_derived(const lig_linear_system& sys, const uint8_t* kin
         if (hits != 1) return hits ? "a target occurs more than once in its defining constraint" : "a target does not occur in its defining constraint";
         const uint32_t coef = sys.terms[at[i]].coef;
         if (coef != LIG_COEF_ONE && coef != LIG_COEF_NEG_ONE) return "the coefficient of a target must be LIG_COEF_ONE or LIG_COEF_NEG_ONE";
-        const uint64_t row = d[i].slot / l;             // < rows: the slot is a term of a checked system
-        if (row >= rows) return "a target beyond the rows";
+        if (row >= rows) return "a target beyond the rows";      // (< rows: the slot is a term of a checked system)
         if (elem_bytes) {
             if (elem_bytes[row] == LIG_ELEM_PRODUCT) return "a target on a LIG_ELEM_PRODUCT row";
-            // the operands of a derived product are read from their packed sources: a value derived here would not reach the product
+            // the row's own product is formed from the PACKED operand rows: a value derived here reaches it only through a product entry
+            // of the same column, which re-forms it from the matrix
             const uint8_t kd = kinds[row] & 0x7f;
-            if (kd == LIG_ROW_QX && row + 2 < rows && elem_bytes[row + 2] == LIG_ELEM_PRODUCT) return "a target is an operand slot of a LIG_ELEM_PRODUCT row";
-            if (kd == LIG_ROW_QY && row + 1 < rows && elem_bytes[row + 1] == LIG_ELEM_PRODUCT) return "a target is an operand slot of a LIG_ELEM_PRODUCT row";
+            if (kd == LIG_ROW_QX && row + 2 < rows && elem_bytes[row + 2] == LIG_ELEM_PRODUCT && !reformed(row + 2, col)) return "a target is an operand slot of a LIG_ELEM_PRODUCT row";
+            if (kd == LIG_ROW_QY && row + 1 < rows && elem_bytes[row + 1] == LIG_ELEM_PRODUCT && !reformed(row + 1, col)) return "a target is an operand slot of a LIG_ELEM_PRODUCT row";
         }
     }
-    // waves: 1 + the largest wave among the derived slots a target reads (0 for a slot that is not derived); depth-first with an explicit
+    // what entry i reads, as a range of positions: the terms of its defining constraint (its own term skipped), or the two operands of a
+    // product entry
+    auto reads_begin = [&](uint32_t i) { return is_product(i) ? 0u : sys.term_begin[d[i].constraint]; };
+    auto reads_end = [&](uint32_t i) { return is_product(i) ? 2u : sys.term_begin[d[i].constraint + 1]; };
+    auto read_slot = [&](uint32_t i, uint32_t t) { return is_product(i) ? d[i].slot - (2 - t) * l : sys.terms[t].slot; };
+    // waves: 1 + the largest wave among the derived slots an entry reads (0 for a slot that is not derived); depth-first with an explicit
     // stack, a slot met again while it is still open closes a cycle
     out.wave_of.assign(n, 0);
     std::vector<uint8_t> state(n, 0);                   // 0 untouched, 1 open, 2 done
-    std::vector<std::pair<uint32_t, uint32_t>> stack;   // (entry, next term to look at)
+    std::vector<std::pair<uint32_t, uint32_t>> stack;   // (entry, next position to look at)
     for (uint64_t root = 0; root < n; root++) {
         if (state[root]) continue;
         state[root] = 1;
-        stack.emplace_back((uint32_t)root, sys.term_begin[d[root].constraint]);
+        stack.emplace_back((uint32_t)root, reads_begin((uint32_t)root));
         while (!stack.empty()) {
-            const uint32_t i = stack.back().first, e = sys.term_begin[d[i].constraint + 1];
+            const uint32_t i = stack.back().first, e = reads_end(i);
             uint32_t& t = stack.back().second;
             bool descended = false;
             for (; t < e; t++) {
-                if (t == at[i]) continue;
-                const auto it = index.find(sys.terms[t].slot);
+                if (!is_product(i) && t == at[i]) continue;
+                const auto it = index.find(read_slot(i, t));
                 if (it == index.end()) continue;
                 const uint32_t j = it->second;
                 if (state[j] == 1) return "the derived slots form a cycle";
-                if (state[j] == 0) { state[j] = 1; stack.emplace_back(j, sys.term_begin[d[j].constraint]); descended = true; break; }      // (t stays: looked at again when j is done)
+                if (state[j] == 0) { state[j] = 1; stack.emplace_back(j, reads_begin(j)); descended = true; break; }      // (t stays: looked at again when j is done)
                 out.wave_of[i] = std::max(out.wave_of[i], out.wave_of[j]);
             }
             if (descended) continue;
@@ -100,27 +133,33 @@ inline const char* plan_derived(const lig_linear_system& sys, const uint8_t* kin
         }
     }
     for (uint64_t i = 0; i < n; i++) out.n_waves = std::max(out.n_waves, out.wave_of[i]);
-    // the program: wave-major, light targets in front of the heavy ones
+    // the program: wave-major, light targets in front of the heavy ones; the product entries of a wave in a list of their own
     auto others = [&](uint64_t i) { return sys.term_begin[d[i].constraint + 1] - sys.term_begin[d[i].constraint] - 1; };
     out.wave_begin.assign((size_t)out.n_waves + 1, 0);
     out.wave_light.assign(out.n_waves, 0);
+    out.prod_begin.assign((size_t)out.n_waves + 1, 0);
+    uint64_t n_linear = 0;
     for (uint64_t i = 0; i < n; i++) {
+        if (is_product(i)) { out.prod_begin[out.wave_of[i]]++; continue; }
+        n_linear++;
         out.wave_begin[out.wave_of[i]]++;
         if (others(i) <= DERIVE_LANE_MAX) out.wave_light[out.wave_of[i] - 1]++;
     }
-    for (uint32_t w = 0; w < out.n_waves; w++) out.wave_begin[w + 1] += out.wave_begin[w];
-    std::vector<uint32_t> light_at(out.n_waves), heavy_at(out.n_waves);
+    for (uint32_t w = 0; w < out.n_waves; w++) { out.wave_begin[w + 1] += out.wave_begin[w]; out.prod_begin[w + 1] += out.prod_begin[w]; }
+    std::vector<uint32_t> light_at(out.n_waves), heavy_at(out.n_waves), prod_at(out.prod_begin.begin(), out.prod_begin.end() - 1);
     for (uint32_t w = 0; w < out.n_waves; w++) { light_at[w] = out.wave_begin[w]; heavy_at[w] = out.wave_begin[w] + out.wave_light[w]; }
-    out.targets.resize(n);
-    std::vector<uint32_t> entry_of(n);                  // program position -> entry of d
+    out.targets.resize(n_linear);
+    out.products.resize(n - n_linear);
+    std::vector<uint32_t> entry_of(n_linear);           // program position -> entry of d
+    uint64_t total = 0;
     for (uint64_t i = 0; i < n; i++) {
         const uint32_t w = out.wave_of[i] - 1;
+        if (is_product(i)) { out.products[prod_at[w]++] = DeriveProduct{d[i].slot / l, d[i].slot % l}; continue; }
         entry_of[others(i) <= DERIVE_LANE_MAX ? light_at[w]++ : heavy_at[w]++] = (uint32_t)i;
+        total += others(i);
     }
-    uint64_t total = 0;
-    for (uint64_t i = 0; i < n; i++) total += others(i);
     out.terms.reserve(total);
-    for (uint64_t p = 0; p < n; p++) {
+    for (uint64_t p = 0; p < n_linear; p++) {
         const uint32_t i = entry_of[p], c = d[i].constraint;
         DeriveTarget tg;
         tg.slot = d[i].slot;
@@ -178,6 +217,11 @@ struct DeriveShardPlan {
     std::vector<uint32_t> send_begin, sends;
     std::vector<uint32_t> export_begin, exports;           // E_rank(w) as local slots (n_waves + 1 offsets): what k_derive_export reads
     uint64_t local_terms = 0, imported_terms = 0, n_imports = 0, n_exports = 0;      // n_imports: distinct foreign slots this rank reads
+    // THIS rank's product entries per wave (n_waves + 1 offsets), local rows: a triple is dealt whole, so a product entry is formed by the
+    // rank that holds its row from two local operands and never imports; local_terms counts it as 2
+    std::vector<uint32_t> prod_begin;
+    std::vector<DeriveProduct> products;
+    uint64_t local_targets() const { return targets.size() + products.size(); }
     uint64_t import_elems() const { return import_begin.empty() ? 0 : import_begin.back(); }
 };
 
@@ -193,6 +237,7 @@ inline const char* plan_derived_shard(const DerivePlan& P, const DeriveDeal& dea
     out.import_begin.assign((size_t)NW + 1, 0);
     out.send_begin.assign((size_t)world * NW + 1, 0);
     out.export_begin.assign((size_t)NW + 1, 0);
+    out.prod_begin.assign((size_t)NW + 1, 0);
     if (!world || rank >= world) return "rank >= world";
     const size_t rows = deal.owner.size();
     auto row_of = [&](uint32_t slot) { return (size_t)(slot / l); };
@@ -260,6 +305,20 @@ inline const char* plan_derived_shard(const DerivePlan& P, const DeriveDeal& dea
             out.targets.push_back(st);
         }
         out.wave_begin[w + 1] = (uint32_t)out.targets.size();
+        // the product entries of the wave: both operands lie on the two local rows in front of the target's (a re-formed slot that a target
+        // of another rank reads travels like any other slot, in the first wave that reads it across ranks -- a later one than this)
+        for (uint32_t p = P.prod_begin[w]; p < P.prod_begin[w + 1]; p++) {
+            const DeriveProduct pr = P.products[p];
+            if (pr.row >= rows || pr.row < 2) return "a product entry beyond the deal";
+            const uint32_t holder = deal.owner[pr.row];
+            if (holder >= world) return "a row dealt to a rank >= world";
+            if (deal.owner[pr.row - 2] != holder || deal.owner[pr.row - 1] != holder || deal.local_of[pr.row] != deal.local_of[pr.row - 2] + 2)
+                return "the deal splits the triple of a product entry";
+            if (holder != rank) continue;
+            out.products.push_back(DeriveProduct{deal.local_of[pr.row], pr.col});
+            out.local_terms += 2;
+        }
+        out.prod_begin[w + 1] = (uint32_t)out.products.size();
     }
     for (size_t i = 0; i < sends_of.size(); i++) {
         out.sends.insert(out.sends.end(), sends_of[i].begin(), sends_of[i].end());
